@@ -22,6 +22,9 @@ already resident in HBM.  Workloads (SURVEY.md section 8d / BASELINE.md):
                           train.py:230-246, darts_model.py:159-324) of the 4-slot super-net (n_step 2) on a GLOBAL batch
                           of 32 train + 32 val 256x256 patches, sharded 32/N per rank, gradients averaged over RCCL
                           (strong scaling of a fixed job); the same job on one GPU is timed beside it
+A plain run sets up, warms up and times the K headline steps only; --full adds every other workload and figure
+(back-to-back kernel times, pointwise, cnn, search, BASELINE configs 3 / 5, the CPU baselines).  --dump-outputs DIR
+writes what the last timed step computed (dump_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -66,7 +69,7 @@ def build_pipeline(arch, device, which='IspUniversal'):
     return net
 
 
-def timed(fn, steps, warmup, device, world):
+def timed(fn, steps, warmup, device, world, period=1):
     # The cyclic GC is collected once BEFORE the warm-up and paused until the timed region ends (as timeit does): a
     # collection of this process's heap is a ~40 ms host stall, and 40 ms of idle GPU right before the timed region
     # drops the device into its low-power clocks, which the first ~2 ms of timed launches then pay for.
@@ -75,7 +78,8 @@ def timed(fn, steps, warmup, device, world):
     # Spin-up (untimed, before the W warm-up steps): ~50 ms of the same work issued WITHOUT intermediate synchronisation.
     # After an idle period - and while launches are interleaved with host synchronisations - the device runs slower for a
     # few hundred launches (tools/diag_ramp.py, diag_ramp2.py: 46 -> 60 us per step); without this a short timed window
-    # (K = 200) measures that transient, not the throughput.
+    # (K = 200) measures that transient, not the throughput.  Rounded up to a multiple of `period` (the resident batches a
+    # step rotates over), so the timed steps meet the same batches in every run whatever the estimate.
     ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev_a.record()
     for _ in range(3):
@@ -83,7 +87,7 @@ def timed(fn, steps, warmup, device, world):
     ev_b.record()
     ev_b.synchronize()
     est_ms = max(ev_a.elapsed_time(ev_b) / 3, 1e-3)
-    timed.spin_up_launches = 3 + min(4000, int(50.0 / est_ms) + 1)
+    timed.spin_up_launches = -(-(3 + min(4000, int(50.0 / est_ms) + 1)) // period) * period
     for _ in range(timed.spin_up_launches - 3):
         fn()
     for _ in range(warmup):
@@ -556,6 +560,39 @@ def config5_leg(device, tile_batch=21, reps=3):
     return res
 
 
+DUMP_BYTES = 64 * 10 ** 6
+NPY_HEADER_BYTES = 1024        # allowance per file for np.save's header (128 bytes for these shapes)
+
+
+def dump_sample(n, m):
+    """The images of a batch of ``n`` that --dump-outputs writes when only ``m`` fit: a fixed, seeded choice, sorted."""
+    return torch.randperm(n, generator=torch.Generator().manual_seed(0))[:m].sort().values
+
+
+def dump_outputs(out_dir, y, stages, names):
+    """``--dump-outputs``: the arrays a caller of the timed forward receives from its last step, as float32 .npy files, at
+    most DUMP_BYTES in all, headers included - ``output.npy``, the forward's return value, and ``stage<k>_<name>.npy`` for
+    every earlier stage output (``intermediate_results``).  The output is written whole, leaving room for one image of
+    each earlier stage; those stages (and the output, if the batch is too large for that) are written on the images
+    dump_sample() picks, as many as fit (64 x 256 x 256: the output whole, the four earlier stages on 4 images)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rest = [(k, s) for k, s in enumerate(stages, start=1) if s.data_ptr() != y.data_ptr()]
+    per_image = lambda t: t[0].numel() * 4
+    rest_image = sum(per_image(s) for _, s in rest)
+    n = y.shape[0]
+    budget = DUMP_BYTES - NPY_HEADER_BYTES * (1 + len(rest))
+    n_out = min(n, (budget - rest_image) // per_image(y))
+    n_rest = min(n, (budget - n_out * per_image(y)) // max(rest_image, 1))
+    if n_out < 1 or n_rest < 1:
+        raise SystemExit('bench.py: one image of every stage output is more than --dump-outputs may write (%d bytes)' % DUMP_BYTES)
+    save = lambda name, t, m: np.save(os.path.join(out_dir, name + '.npy'),
+                                      (t if m == n else t[dump_sample(n, m).to(t.device)]).float().cpu().numpy())
+    save('output', y, n_out)
+    for k, s in rest:
+        save('stage%d_%s' % (k, names[k - 1]), s, n_rest)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -577,6 +614,12 @@ def main():
     ap.add_argument('--no-search', action='store_true', help='skip the distributed search-step leg (BASELINE config 4)')
     ap.add_argument('--search-batch', type=int, default=32, help='GLOBAL batch of the search-step leg')
     ap.add_argument('--no-configs', action='store_true', help='skip BASELINE configs 3 / 5 and the shipped search geometry')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (back-to-back kernel times, the point-wise, CNN, search-step and '
+                         'BASELINE-config legs, the CPU baselines, the one-rank figure at N > 1); without it only the headline '
+                         'steps are timed.  The --no-* switches pick legs within --full')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/*.npy (float32; see dump_outputs)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -622,11 +665,11 @@ def main():
     batches = [bay] + [make_batch(args.batch, args.size, args.size, seed=100 + 10 * rank + k)[0].to(device)
                        for k in range(1, queue)]
 
-    def rotating(fwd):          # step k runs the registry forward on resident batch k mod queue
-        state = [0]
+    def rotating(fwd):          # step k runs the registry forward on resident batch k mod queue; step.last: what it returned
         def step():
-            fwd(batches[state[0] % queue])
-            state[0] += 1
+            step.last = fwd(batches[step.count % queue])
+            step.count += 1
+        step.count, step.last = 0, None
         return step
 
     with torch.no_grad():
@@ -634,12 +677,18 @@ def main():
             gq = GraphedQueue(net, batches)
             wall, dev_ms = timed(lambda: gq(), args.steps // queue, args.warmup // queue, device, world)
             dev_ms /= queue
+            last, last_stages = gq.outputs[-1], gq.stage_outputs[-1]          # the last step = the last slot of the last replay
         else:
-            wall, dev_ms = timed(rotating(net), args.steps, args.warmup, device, world)
+            isp_step = rotating(net)
+            wall, dev_ms = timed(isp_step, args.steps, args.warmup, device, world, period=queue)
+            last, last_stages = isp_step.last, list(net.intermediate_results)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last, last_stages, net.step_names)
         host_us = timed.host_us / (queue if graph else 1)
         spin_up = timed.spin_up_launches * (queue if graph else 1)
-        b2b_ms = kernel_time_ms(net, batches[:queue], max(args.steps, 100), device, True)
-        b2b_ms_cached = kernel_time_ms(net, batches[:1], max(args.steps, 100), device, True)
+        if args.full:
+            b2b_ms = kernel_time_ms(net, batches[:queue], max(args.steps, 100), device, True)
+            b2b_ms_cached = kernel_time_ms(net, batches[:1], max(args.steps, 100), device, True)
     value = world * pix_per_step * args.steps / wall / 1e6
     ms_per_step = wall / args.steps * 1e3
     # The dominant kernel's average launch duration = HIP events on the launch stream over the SAME timed region as
@@ -649,30 +698,32 @@ def main():
     kernel_within_step = bool(kernel_ms <= ms_per_step * 1.001)      # reported, not asserted: a diagnostic must not cost the line
     achieved = BYTES_PER_PIX_ISP * pix_per_step / (kernel_ms * 1e-3) / 1e9
 
-    pw = build_pipeline(ARCH_HBM, device)
-    with torch.no_grad():
-        pstep = GraphedForward(pw, bay) if graph else rotating(pw)
-        wall_p, dev_ms_p = timed(lambda: pstep(), args.steps, args.warmup, device, world)
-        host_us_p = timed.host_us
-        kernel_ms_p = kernel_time_ms(pw, batches[:queue], max(args.steps, 100), device, False)
     hbm = lambda bpp, ms: bpp * pix_per_step / (ms * 1e-3) / 1e9          # GB/s
     extra = {'kernel_ms': round(kernel_ms, 5), 'kernel_ms_within_step': kernel_within_step, 'kernel_ms_source': 'HIP events on the launch stream around the timed region / steps',
              'host_issue_us_per_step': round(host_us, 1),
              'resident_batches': queue,
+             'spin_up_launches': spin_up,       # untimed, before the W warm-up steps: ~50 ms of the same launches (see timed())
+             'launch': ('hipGraph replay, %d resident batches (steps) per replay' % queue) if graph else
+                       ('one Python forward() per step on the stream, rotating over %d resident batches' % queue)}
+    if args.full:
+        pw = build_pipeline(ARCH_HBM, device)
+        with torch.no_grad():
+            pstep = GraphedForward(pw, bay) if graph else rotating(pw)
+            wall_p, dev_ms_p = timed(lambda: pstep(), args.steps, args.warmup, device, world)
+            host_us_p = timed.host_us
+            kernel_ms_p = kernel_time_ms(pw, batches[:queue], max(args.steps, 100), device, False)
+        extra.update({
              'kernel_ms_back_to_back_c_abi': round(b2b_ms, 5),
              'hbm_frac_back_to_back_c_abi': round(hbm(BYTES_PER_PIX_ISP, b2b_ms) / HBM_PEAK_GBS, 4),
              'kernel_ms_one_batch_cache_assisted': round(b2b_ms_cached, 5),
              'hbm_frac_one_batch_cache_assisted': round(hbm(BYTES_PER_PIX_ISP, b2b_ms_cached) / HBM_PEAK_GBS, 4),
-             'spin_up_launches': spin_up,       # untimed, before the W warm-up steps: ~50 ms of the same launches (see timed())
-             'launch': ('hipGraph replay, %d resident batches (steps) per replay' % queue) if graph else
-                       ('one Python forward() per step on the stream, rotating over %d resident batches' % queue),
              'pointwise_arch': ARCH_HBM,
              'pointwise_MPix_s': round(world * pix_per_step * args.steps / wall_p / 1e6, 1),
              'pointwise_kernel_ms': round(dev_ms_p, 5), 'pointwise_kernel_ms_back_to_back_c_abi': round(kernel_ms_p, 5),
              'pointwise_host_issue_us_per_step': round(host_us_p, 1), 'pointwise_host_issue_us_med_max': [round(timed.host_med_us, 1), round(timed.host_max_us, 1)],
              'pointwise_hbm_GBs': round(hbm(BYTES_PER_PIX_FUSED, dev_ms_p), 1),
-             'pointwise_hbm_frac': round(hbm(BYTES_PER_PIX_FUSED, dev_ms_p) / HBM_PEAK_GBS, 4)}
-    if not args.no_cnn:
+             'pointwise_hbm_frac': round(hbm(BYTES_PER_PIX_FUSED, dev_ms_p) / HBM_PEAK_GBS, 4)})
+    if args.full and not args.no_cnn:
         import reconfigisp_amd.convnets as CN
         cnn = build_pipeline(ARCH_CNN, device)
         steps_c = max(3, args.steps // 20)
@@ -711,7 +762,7 @@ def main():
             wall_f, dev_ms_f, issued_f, _ = cnn_leg('f32')
             extra.update(cnn_f32_MPix_s=round(world * pix_per_step * steps_c / wall_f / 1e6, 1), cnn_f32_ms_per_step=round(dev_ms_f, 3),
                          cnn_f32_mfma_issued_frac=round(tf(issued_f, dev_ms_f) / MFMA_F32_PEAK_TFLOPS, 4))
-    if not args.no_search:
+    if args.full and not args.no_search:
         # a secondary leg must never cost the headline line: at N = 1 a failure is reported instead of raised.  At N > 1 a
         # failure can be rank-local (out of memory on one GPU, an RCCL error) while the peers sit in a collective: the ranks
         # cannot agree on anything any more, so the exception goes up and the launcher ends the job (launch_ranks also
@@ -732,7 +783,7 @@ def main():
             leg = {'error': '%s: %s' % (type(e).__name__, e)}
         if rank == 0:
             extra['search_step_shipped'] = leg
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         # BASELINE configs 3 and 5, driver-run (every rank runs them on its own GPU, after the collectives of the legs above: no
         # rank waits in a collective meanwhile; rank 0's figures are reported)
         for key, fn in (('config3', config3_leg), ('config5', config5_leg)):
@@ -756,7 +807,7 @@ def main():
         ranks = [None] * world
         dist.all_gather_object(ranks, me)
         solo = None
-        if rank == 0:
+        if rank == 0 and args.full:
             with torch.no_grad():
                 wall_1, _ = timed(rotating(net), args.steps, args.warmup, device, 1)
             solo = round(pix_per_step * args.steps / wall_1 / 1e6, 1)
@@ -784,7 +835,7 @@ def main():
             line['proof_of_ranks'] = proof
         if one_device and world > 1:
             line['dry_run_all_ranks_on_one_device'] = True
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             line['cpu_baseline'] = cpu_baseline(bay_cpu, ARCH_DENOISE)
             line['cpu_baseline_config1'] = cpu_baseline_config1(args.size)
         print(json.dumps(line))

@@ -14,6 +14,16 @@ import torch.multiprocessing as mp
 from conftest import ROOT
 
 
+@pytest.fixture(autouse=True)
+def _product_impl_afterwards():
+    # _make_model / _frame_job bind the operator seam to the CPU oracle in this process too: the tests that follow in the same
+    # session (GPU tests among them) must find the product's binding again
+    import reconfigisp_amd.functional as F
+    impl = F._IMPL
+    yield
+    F._IMPL = impl
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))

@@ -168,10 +168,10 @@ def test_file_backed_rggb2bgr_datasets(tmp_path):
         create_dataset(dict(base, mode='S7ISP_RGGB2BGR', data_type='mc'))
 
 
-REF_OPTIONS = '/root/reference/codes/options'
+# the reference's nine shipped option files (settings only), kept as fixtures
+REF_OPTIONS = os.path.join(ROOT, 'tests', 'golden', 'option_files')
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OPTIONS), reason='dev container only: the nine shipped YAMLs live under /root/reference')
 def test_reference_option_files_parse_like_the_reference(monkeypatch, capsys):
     """options/options.py:8-62 on the reference's own nine option files: the mirror's parse must derive the same fields (phase,
     data_type, mode after '_mc' stripping, meta_device, every path.*, the debug overrides) and leave the same tree as the
@@ -194,7 +194,6 @@ def test_reference_option_files_parse_like_the_reference(monkeypatch, capsys):
     assert 'export CUDA_VISIBLE_DEVICES=' in capsys.readouterr().out          # every machine but the authors' cluster (:13-17)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OPTIONS), reason='dev container only: the nine shipped YAMLs live under /root/reference')
 @pytest.mark.filterwarnings('ignore:Detected call of')
 def test_reference_option_files_build_their_models(monkeypatch, tmp_path):
     """create_model(opt) from each shipped YAML on the operator seam (CPU): the six image-loss files construct their networks,

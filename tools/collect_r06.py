@@ -55,7 +55,7 @@ old = json.load(open('profiles/traffic.json'))
 alg = 64 * 64 * 256 * 256                       # bench.py: BYTES_PER_PIX_ISP x the pixels of one launch (batch 64 of 256 x 256)
 traffic = {
     '_comment': 'HBM bytes per launch of the dominant kernel from the rocprofv3 PMC passes of round 6 (tools/profile_bench.sh r06 through tools/profile_r06.sh: separate '
-                '--pmc FETCH_SIZE and --pmc WRITE_SIZE runs of `bench.py --steps 200 --warmup 20 --no-cpu --no-cnn`; summary in profiles/r06_bench_rocprofv3_summary.txt), '
+                '--pmc FETCH_SIZE and --pmc WRITE_SIZE runs of `bench.py --full --steps 200 --warmup 20 --no-cpu --no-cnn --no-search`; summary in profiles/r06_bench_rocprofv3_summary.txt), '
                 'written by tools/collect_r06.py.  Counter units are KiB.  WRITE_SIZE is exact for 16-byte-per-lane stores (MI355X_MICROARCH.md, HBM section); FETCH_SIZE is '
                 'multiplied by 2 (calibrated on this chip with tools/fetch_calib.hip: factor 2.000 for 4-, 8- and 16-byte loads and for the two-row quad pattern the kernel '
                 'stages its mosaic with, profiles/r02_fetch_size_calibration.txt).  `kernel` is what risp_bilateral_chain_kernel() names for the bench launch: bench.py '

@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/r04
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line: default window, then the round driver's flags
-timeout 900 python3 "$REPO/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python3 "$REPO/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout 900 python3 "$REPO/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_flags.json" 2> "$OUT/bench_driver_flags.err"
 # 2. kernel trace + HBM counters of the bench command
 timeout 1200 bash "$REPO/tools/profile_bench.sh" r04 > "$OUT/profile_bench.log" 2>&1

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 WANT=" ${*:-1 2 3 4 5 6 7 8 9} "
 want() { [[ "$WANT" == *" $1 "* ]]; }
 if want 1; then   # the bench line: default window, then the round driver's flags
-  timeout 900 python3 "$REPO/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout 900 python3 "$REPO/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   timeout 900 python3 "$REPO/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_flags.json" 2> "$OUT/bench_driver_flags.err"
 fi
 if want 2; then   # kernel trace + HBM counters of the bench command (-> gpurun_out/prof_r06; tools/collect_r06.py writes profiles/traffic.json from it)
