@@ -609,6 +609,34 @@ int risp_origin_fastnlm(const float *x, float *y, const int32_t *block_size, con
 size_t risp_origin_tonemap_scratch_floats(int N);
 int risp_origin_tonemap(const float *x, float *y, int mode, const float *a, const float *b, const float *stats,
                         float *scratch, int N, int HW, float in_scale, float out_div, void *stream);
+/* 'bm3d' (sRGB index 15; the reference has only a proxy net for it) - OPSPEC, restated in float64 in
+ * tests/bm3d_reference.py.  Per-image device arrays: sigma (= 2.55 * cff, codes), n1 (4 | 8), cspace (0 orthonormal
+ * opponent Y=(R+G+B)/sqrt3 U=(R-B)/sqrt2 V=(R-2G+B)/sqrt6, 1 BT.601 full-range YCbCr without offsets; inverse = the
+ * float64 matrix inverse as fp32 constants), wtransform (0 orthonormal DCT-II, 1 orthonormal Haar, full
+ * decomposition), radius R (0..9).
+ *  1 codes q = floor(clamp(x*in_scale, 0, 255) + 0.5); sigma < 1e-3: the result is q / |out_div| (both output forms).
+ *  2 reference blocks n1 x n1 at corners {0, 3, 6, ...} u {H-n1} x the same for W, row-major (no padding).
+ *  3 matching on S = B+G+R of the codes: every corner within +-R (clamped to the image) gets D = sum (S_c - S_ref)^2
+ *    (int32); kept if D <= 22500 n1^2; ordered by (D, y, x) with the reference forced to rank 0; N2 = the largest
+ *    power of two <= min(#kept, 16).  Both filtering steps use this one group.
+ *  4 step 1, per colour channel c with sigma_c = sigma * |row_c|: 2D transform of each block, orthonormal Haar along
+ *    the group, keep |coef| > 2.7 sigma_c (N_c kept), invert; weight w1 = 1 / sum_c sigma_c^2 max(N_c, 1).
+ *  5 aggregation: estimate = sum w K.block / sum w K per pixel and channel, K = outer(kaiser(n1, beta 2)), summed in
+ *    (reference index, rank) order - deterministic, no atomics.
+ *  6 step 2 on the same groups: pilot P = basic estimate, Z = noisy; W = T(P)^2 / (T(P)^2 + sigma_c^2), estimate
+ *    T^-1(W T(Z)), w2 = 1 / sum_c sigma_c^2 max(sum W_c^2, 1) (the floor keeps an all-black group finite); aggregate.
+ *  7 inverse colour transform, then the Origin output convention above.
+ * The batch runs in chunks of as many images as scratch holds (>= risp_origin_bm3d_scratch_bytes(1, H, W), 256-byte
+ * aligned).  groups (nullable): (N, rows, 17) int32 with rows = the grid size for n1 = 4 - count N2, the member
+ * corners y*W+x (reference first), -1 padded; rows past an n1 = 8 image's grid are (0, -1, ...).
+ * The per-image values are the caller's to validate (functional.origin_denoise refuses bad ones): on the device an
+ * n1 other than 4 runs as 8 (as 4 on images smaller than 8), R is clamped to 0..9 - nothing is read or written
+ * outside the image, the table and the scratch.  4 <= H, W <= 65535 and 3 H W < 2^31 (anything else is refused, and
+ * risp_origin_bm3d_scratch_bytes returns 0 for it). */
+size_t risp_origin_bm3d_scratch_bytes(int N, int H, int W);
+int risp_origin_bm3d(const float *x, float *y, const float *sigma, const int32_t *n1, const int32_t *cspace,
+                     const int32_t *wtransform, const int32_t *radius, int N, int H, int W, float in_scale, float out_div,
+                     void *scratch, size_t scratch_bytes, int32_t *groups, void *stream);
 
 /* Fused stencil segment (inference): [nearest demosaic ->] bilateral -> element-wise chain in one launch;
  * the BGR halo tile is staged in LDS (straight from the mosaic when from_bayer), every stage output is

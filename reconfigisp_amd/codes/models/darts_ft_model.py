@@ -4,6 +4,7 @@ On top of DartsModel: every weight step appends the detached sRGB-domain slot ou
 memory (:194-201); ``finetune_proxies()`` (called by the driver every proxy_ft_params.ft_interval iterations)
 trains each flagged proxy of the LAST sRGB slot for ft_steps Adam steps on a random memory entry with random
 parameters against its classical teacher (the Origin* HIP stencils), then copies the weights into every slot.
+``proxy_ft_params.bm3d_teacher: true`` adds the bm3d proxy, taught by the classical BM3D (off by default).
 The proxies' weight gradients come from risp_conv2d_wgrad.  Distributed: the reference wraps each proxy in DDP;
 here its ~0.5 MB gradient is averaged with one flat all-reduce per step (RCCL)."""
 import random
@@ -16,7 +17,7 @@ from .modules import tools_origin as T
 _TEACHERS = {'reinhard': (T.OriginToneReinhard, 2), 'crysisengine': (T.OriginToneCrysis, 1),
              'filmic': (T.OriginToneFilmic, 2), 'whiteworld': (T.OriginWbWhiteworld, 1),
              'bilateral': (T.OriginNoiseBilateral, 3), 'median': (T.OriginNoiseMedian, 1),
-             'fastnlm': (T.OriginNoiseFastnlm, 3)}
+             'fastnlm': (T.OriginNoiseFastnlm, 3), 'bm3d': (T.OriginNoiseBm3d, 5)}
 
 
 class DartsFtModel(DartsModel):
@@ -27,6 +28,9 @@ class DartsFtModel(DartsModel):
             return
         ft = opt['proxy_ft_params']
         self.memory_size, self.ft_steps = ft['memory_size'], ft['ft_steps']
+        if 'bm3d_teacher' in ft and ft['bm3d_teacher']:
+            # opt-in: the classical BM3D (OriginNoiseBm3d) teaches the bm3d proxy; absent, the reference's set
+            self.netG_attr.enable_proxy_ft('bm3d')
         self.param_num_dict = {name: p for name, (_, p) in _TEACHERS.items()}
         t = opt['train']
         for (name, enabled), proxy in zip(self.netG_attr.proxy_ft_flag, self.netG_attr.all_modules[-1]):

@@ -20,7 +20,7 @@ class _FixedPipeline(nn.Module):
     srgb_names = R.NAMES_SRGB
     use_origin_kernels = False
 
-    def _build(self, module_path, architecture, indiv_module_paths=None, conditional=None):
+    def _build(self, module_path, architecture, indiv_module_paths=None, conditional=None, classical_bm3d=False):
         conditional = conditional or {}
         self.architecture = architecture
         self.all_modules, self.all_params, self.is_conditional, self.step_names = [], [], [], []
@@ -28,7 +28,7 @@ class _FixedPipeline(nn.Module):
             override = indiv_module_paths[step - 1] if indiv_module_paths is not None and name in R.PROXY_NETS else None
             cond_ch = conditional.get(R.CONDITIONAL_KW.get(name))
             op = R.make_op(name, module_path, origin=self.use_origin_kernels, weight_override=override,
-                           conditional_channels=cond_ch)
+                           conditional_channels=cond_ch, classical_bm3d=classical_bm3d)
             init = list(R.PARAM_INIT[name])
             if name in R.CONDITIONAL_KW:
                 # FC weights ~ N(0, 0.01^2), then the 'global' module parameters (isp_universal.py:185-190)

@@ -75,9 +75,12 @@ def weight_path(name, module_path, override=None):
     return None if module_path is None else module_path + PROXY_NETS[name][1]
 
 
-def make_op(name, module_path, origin=False, weight_override=None, conditional_channels=None):
+def make_op(name, module_path, origin=False, weight_override=None, conditional_channels=None, classical_bm3d=False):
     """Instantiate registry entry `name`.  origin=True selects the classical (non-proxy) kernels
-    where they exist (OriginUniversal); otherwise the differentiable proxies."""
+    where they exist (OriginUniversal); otherwise the differentiable proxies.  classical_bm3d=True adds the
+    classical BM3D to that set (opt-in: the reference's OriginUniversal keeps its proxy)."""
+    if origin and classical_bm3d and name == 'bm3d':
+        return T.OriginNoiseBm3d()
     if name in _PLAIN_CLASS:
         return _PLAIN_CLASS[name]()
     if name == 'gtmmanual':

@@ -16,6 +16,10 @@ class SuperPruneFifteenDemosFourBayerTwoFt(SuperPruneFifteenDemosFourBayerTwo):
         self.n_step = n_step
         self.proxy_ft_flag = [(name, int(name in _FT_ENABLED)) for name in _FT_NAMES]
 
+    def enable_proxy_ft(self, name):
+        """flag one more entry for fine-tuning (DartsFtModel: proxy_ft_params.bm3d_teacher)"""
+        self.proxy_ft_flag = [(nm, 1 if nm == name else on) for nm, on in self.proxy_ft_flag]
+
     def load_proxy_nets(self, name_net_dict):
         """name -> fine-tuned proxy; its weights replace that entry in all n_step sRGB slots."""
         for idx, (name, enabled) in enumerate(self.proxy_ft_flag):

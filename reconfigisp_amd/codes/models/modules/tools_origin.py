@@ -250,3 +250,15 @@ class OriginNoiseFastnlm(_OriginOp):
         desc.update(block_size=(p[:, 0].int() * 7) * 2 + 3, search_block=(p[:, 1].int() * 7) * 2 + 3,
                     decay_factor=p[:, 2] * 99 + 1)
         return desc
+
+
+class OriginNoiseBm3d(_OriginOp):
+    """Classical BM3D in place of the proxy of sRGB index 15 (the reference has none: origin_universal.py:12).  The
+    mapping reproduces the reference's initial values (cff 1.5, n1 8, cspace 0, wtransform 0, neighborhood 8) at the
+    initial probabilities .125 .75 .25 .25 .9375 (registry.PARAM_INIT['bm3d'])."""
+    kernel_cls, option = snr.SpatialNoiseReduction, 'bm3d'
+
+    def _params(self, p, desc):
+        desc.update(cff=p[:, 0] * 12, n1=torch.where(p[:, 1] < 0.5, 4, 8).int(), cspace=(p[:, 2] >= 0.5).int(),
+                    wtransform=(p[:, 3] >= 0.5).int(), neighborhood=torch.clamp((p[:, 4] * 8).floor().int() + 1, max=9))
+        return desc

@@ -31,5 +31,6 @@ def define_G(opt):
                             architecture=opt_net['architecture'], **(cond or {}))
     if which == 'OriginUniversal':
         from .modules.origin_universal import OriginUniversal
-        return OriginUniversal(module_path=module_path, architecture=opt_net['architecture'])
+        classical_bm3d = bool(opt_net['classical_bm3d']) if 'classical_bm3d' in opt_net else False
+        return OriginUniversal(module_path=module_path, architecture=opt_net['architecture'], classical_bm3d=classical_bm3d)
     raise NotImplementedError('Generator model [{:s}] not recognized'.format(which))

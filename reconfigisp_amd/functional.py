@@ -1000,6 +1000,9 @@ def _hip_origin_whiteworld(x, ratio, scales=(1.0, 1.0)):
 
 def _hip_origin_denoise(x, option, params, scales=(1.0, 1.0)):
     x = _dev(x.detach(), 'img')
+    if option == 'bm3d':                  # any H, W >= n1
+        return _hip_origin_bm3d(x, 2.55 * _vec(params['cff'], x.shape[0], x.device), params['n1'], params['cspace'],
+                                params['wtransform'], params['neighborhood'], scales)[0]
     _check_bgr(x)
     n, _, h, w = x.shape
     y = torch.empty_like(x)
@@ -1023,6 +1026,72 @@ def _hip_origin_denoise(x, option, params, scales=(1.0, 1.0)):
     else:
         raise ValueError('unknown denoiser %r' % (option,))
     return y
+
+
+BM3D_N1 = (4, 8)
+BM3D_RADIUS_MAX = 9
+BM3D_SCRATCH_CAP = 4 << 30        # bytes of BM3D scratch a batch may take before it runs in chunks
+# (device, stream) -> uint8 buffer, grown on demand and kept: it holds at least one image (89 MB at 256 x 256, about
+# 16 GB for a 4000 x 3000 frame, whatever the cap) until release_bm3d_scratch() drops it
+_bm3d_scratch = {}
+
+
+def bm3d_table_rows(h, w):
+    """rows of the BM3D group table: the reference-block grid of n1 = 4 (risp.h 'bm3d')"""
+    return ((h - 2) // 3 + 1) * ((w - 2) // 3 + 1)
+
+
+def release_bm3d_scratch():
+    """Drop the cached BM3D scratch of every device and stream (the memory returns to PyTorch's caching allocator;
+    torch.cuda.empty_cache() hands it back to the device).  The next BM3D call allocates again."""
+    _bm3d_scratch.clear()
+
+
+def _bm3d_workspace(device, nbytes):
+    key = (device, _stream().value)
+    buf = _bm3d_scratch.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _bm3d_scratch[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return buf
+
+
+def _hip_origin_bm3d(x, sigma, n1, cspace, wtransform, radius, scales=(1.0, 1.0), scratch_bytes=None,
+                     want_groups=False):
+    """risp_origin_bm3d on a (N,3,H,W) batch; per-image parameters as in risp.h.  scratch_bytes: the scratch the batch
+    may use (>= one image; default: the whole batch up to BM3D_SCRATCH_CAP); it is cached per (device, stream) until
+    release_bm3d_scratch().  Returns (y, groups or None)."""
+    x = _dev(x.detach(), 'img')
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError('expected a (N,3,H,W) BGR tensor, got %s' % (tuple(x.shape),))
+    n, _, h, w = x.shape
+    sig = _vec(sigma, n, x.device)
+    blk, cs, wt, rad = (_vec(v, n, x.device, torch.int32) for v in (n1, cspace, wtransform, radius))
+    host = torch.stack([blk, cs, wt, rad]).cpu()
+    if not all(int(v) in BM3D_N1 for v in host[0]):
+        raise ValueError('bm3d: n1 must be 4 or 8, got %s' % (host[0].tolist(),))
+    if int(host[0].max()) > min(h, w):
+        raise ValueError('bm3d: an n1 x n1 block does not fit a %d x %d image' % (h, w))
+    if int(host[3].min()) < 1 or int(host[3].max()) > BM3D_RADIUS_MAX:
+        raise ValueError('bm3d: the search radius must lie in 1..%d, got %s' % (BM3D_RADIUS_MAX, host[3].tolist()))
+    lib = L.load()
+    per = lib.risp_origin_bm3d_scratch_bytes(1, h, w)
+    if per == 0:
+        raise ValueError('bm3d: a %d x %d image is outside 4 <= H, W <= 65535, 3 H W < 2^31' % (h, w))
+    if scratch_bytes is None:
+        scratch_bytes = max(per, min(n * per, BM3D_SCRATCH_CAP // per * per))
+    ws = _bm3d_workspace(x.device, scratch_bytes)
+    y = torch.empty_like(x)
+    groups = torch.empty((n, bm3d_table_rows(h, w), 17), device=x.device, dtype=torch.int32) if want_groups else None
+    L.call('risp_origin_bm3d', _p(x), _p(y), _p(sig), _p(blk), _p(cs), _p(wt), _p(rad), n, h, w, scales[0], scales[1],
+           _p(ws), scratch_bytes, _p(groups), _stream())
+    return y, groups
+
+
+def origin_bm3d(x, sigma, n1, cspace, wtransform, radius, scales=(1.0, 1.0), scratch_bytes=None, want_groups=False):
+    """The classical BM3D of risp.h on a (N,3,H,W) BGR batch (0..255 after scales[0]); sigma in codes, the other
+    parameters per image or scalar.  Returns (y, groups): groups (N, bm3d_table_rows(H, W), 17) int32 when
+    want_groups, else None."""
+    return _hip_origin_bm3d(x, sigma, n1, cspace, wtransform, radius, scales, scratch_bytes, want_groups)
 
 
 def origin_demosaic(x, option, scales=(1.0, 1.0)):

@@ -170,6 +170,8 @@ SIGNATURES = {
     'risp_origin_fastnlm': (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _fl, _fl, _s]),
     'risp_origin_tonemap_scratch_floats': (C.c_size_t, [_i]),
     'risp_origin_tonemap': (_i, [_f, _f, _i, _f, _f, _f, _f, _i, _i, _fl, _fl, _s]),
+    'risp_origin_bm3d_scratch_bytes': (_z, [_i, _i, _i]),
+    'risp_origin_bm3d': (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _fl, _fl, _f, _z, _f, _s]),
     'risp_bilateral_chain_fwd': (_i, [_f, _i, _f, _f, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _pp, _i, _i, _i, _s]),
     'risp_raw_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _fl, _s]),
     'risp_gt_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
