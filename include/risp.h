@@ -638,6 +638,40 @@ int risp_origin_bm3d(const float *x, float *y, const float *sigma, const int32_t
                      const int32_t *wtransform, const int32_t *radius, int N, int H, int W, float in_scale, float out_div,
                      void *scratch, size_t scratch_bytes, int32_t *groups, void *stream);
 
+/* DemosaicNet (demosaic index 04, tools_origin.py:289-308) - OPSPEC, restated in float64 in tests/demosaicnet_reference.py:
+ * Gharbi et al. 2016, Bayer model, depth 15, width 64, in the layout of the public `demosaicnet` package (BayerDemosaick).
+ * x (N,1,H,W): an RGGB mosaic in [0,1]; m3 = the masked mosaic, 3 channels (RGB), x at the channel's own CFA sites and 0
+ * elsewhere (never materialised: every consumer reads x and the site parity).
+ *  1 half resolution (H/2 x W/2): p = pack_mosaic(m3) (2x2 stride-2 conv 3 -> 4, no ReLU); f = relu(conv15(... relu(conv1(p))))
+ *    with 3x3 zero-padded convs 4 -> 64, 64 -> 64 (x13), 64 -> 128; filters, masks = f[:, :64], f[:, 64:];
+ *    r = residual_predictor(filters * masks) (1x1 64 -> 12).
+ *  2 up = upsampler(r): ConvTranspose2d(12, 3, 2, stride 2, groups 3), up[c](2y+dy, 2x+dx) = b[c] + sum_j Wup[4c+j][dy][dx] r[4c+j].
+ *  3 full resolution: h = relu(post_conv(cat(m3, up))) (3x3 6 -> 64, zero padding), y = output(h) (1x1 64 -> 3).
+ *  4 y (N,3,H,W) fp32 in BGR order, neither clipped nor quantised.
+ * The host folds pack_mosaic into conv1 (a selection on the 1-channel mosaic, its bias as border-case planes), the BGR order
+ * into the rows of `output` and, for weights trained on GRBG, a mirror along x; the body runs on risp_conv2d*.  Weights here:
+ * w_rp (12,64), b_rp (12), w_up (12,2,2), b_up (3), w_post (64,6,3,3) (input channels m3 R G B, up R G B), b_post (64),
+ * w_out (3,64) and b_out (3) in OUTPUT order (BGR after the fold).
+ * Limits (anything else is refused): 1 <= N <= 65535; H, W even and >= 4; H W 4 < 2^31 (one full-resolution plane below
+ * 2^31 bytes; the 64-channel half-resolution tensors are addressed with 64-bit offsets).  up, y, g_up, g_x, add 8-byte
+ * aligned.  Deterministic: no atomics, every sum in a fixed order, nothing depends on the batch position.
+ *   tail_fwd: filt, mask (N,64,H/2,W/2) post-ReLU halves of conv15 -> up (N,3,H,W); r stays in registers.
+ *   tail_bwd: g_up (N,3,H,W) -> the gradients at conv15's pre-activations: g_filt = (W_rp^T g_r) * mask * [filt > 0],
+ *             g_mask = (W_rp^T g_r) * filt * [mask > 0], g_r[4c+j](y,x) = sum_{dy,dx} Wup[4c+j][dy][dx] g_up[c](2y+dy, 2x+dx).
+ *   head_fwd: (x, up) -> y in one launch (the 64 hidden values of a pixel stay in registers; a 32 x 32 tile plus halo of the
+ *             mosaic and the three up planes staged in LDS; fp32).
+ *   head_bwd: g_y (N,3,H,W) -> g_up (N,3,H,W) and g_x (N,1,H,W) = add + the direct mosaic term (the m3 channel of each
+ *             site); h is recomputed on the tile plus halo and g_h = (W_out^T g_y) * [h > 0] walks LDS 8 hidden channels
+ *             at a time.  add (N,1,H,W) is nullable. */
+int risp_dmnet_tail_fwd(const float *filt, const float *mask, const float *w_rp, const float *b_rp, const float *w_up,
+                        const float *b_up, float *up, int N, int H, int W, void *stream);
+int risp_dmnet_tail_bwd(const float *g_up, const float *filt, const float *mask, const float *w_rp, const float *w_up,
+                        float *g_filt, float *g_mask, int N, int H, int W, void *stream);
+int risp_dmnet_head_fwd(const float *x, const float *up, const float *w_post, const float *b_post, const float *w_out,
+                        const float *b_out, float *y, int N, int H, int W, void *stream);
+int risp_dmnet_head_bwd(const float *g_y, const float *x, const float *up, const float *w_post, const float *b_post,
+                        const float *w_out, const float *add, float *g_up, float *g_x, int N, int H, int W, void *stream);
+
 /* Fused stencil segment (inference): [nearest demosaic ->] bilateral -> element-wise chain in one launch;
  * the BGR halo tile is staged in LDS (straight from the mosaic when from_bayer), every stage output is
  * written ([0,1] domain; the bilateral works on x255 values and returns codes/255 like the reference

@@ -182,10 +182,11 @@ class SuperPruneFifteenDemosFourBayerTwo(nn.Module):
                 jobs.append((pos, fn))
                 taken.update(pos)
         heavy = [i for i in range(len(index)) if i not in taken and isinstance(mods[index[i]], (TP.PathRestore14lBgr,
-                                                                                                  TP.PathRestore14lBayer))]
+                                                                                                  TP.PathRestore14lBayer,
+                                                                                                  T.DemosaicNet))]
         rest = [i for i in range(len(index)) if i not in taken and i not in heavy]
         for i in heavy:
-            self._record(slot, index[i], token, mods[index[i]])      # read by F.path14l_* through the module
+            self._record(slot, index[i], token, mods[index[i]])      # read by F.path14l_* / T.DemosaicNet through the module
         single = [([i], (lambda xj, i=i: [mods[index[i]](xj, args[i])])) for i in heavy + rest]
         # group, Path-Restore, then the light ops: with two streams the two heavy jobs land on different streams
         return jobs[:1] + single[:len(heavy)] + jobs[1:] + single[len(heavy):]

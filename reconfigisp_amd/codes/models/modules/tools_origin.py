@@ -81,6 +81,9 @@ class DemosaicNet(_PluginOp):
 
     def forward(self, img, params=None):
         desc = _io_desc(img.shape[3], img.shape[2], 'RGGB', 10)
+        rec = self.__dict__.get('_risp_reuse')          # set by the super-net inside a reuse scope (the op has no parameters)
+        if rec is not None:
+            desc['reuse_record'] = rec
         return self.kernel.run(img, 'demosaicnet', desc)
 
 

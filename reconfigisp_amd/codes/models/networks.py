@@ -9,8 +9,22 @@ logger = logging.getLogger('base')
 DEFAULT_MODULE_PATH = '/DATA/module/'
 
 
+def demosaicnet_options(opt_net):
+    """(weights path or None, cfa phase) of the optional keys network_G.demosaicnet_weights / demosaicnet_cfa (default 'rggb')"""
+    path = opt_net['demosaicnet_weights'] if 'demosaicnet_weights' in opt_net else None
+    cfa = opt_net['demosaicnet_cfa'] if 'demosaicnet_cfa' in opt_net and opt_net['demosaicnet_cfa'] else 'rggb'
+    return (path or None), cfa
+
+
 def define_G(opt):
     opt_net = opt['network_G']
+    # DemosaicNet (demosaic index 04) is unavailable unless weights are given: then the built-in HIP implementation is registered
+    # for every network kind (the super-net stops masking the op, the fixed pipelines can evaluate Demosaic_04)
+    dmnet_path, dmnet_cfa = demosaicnet_options(opt_net)
+    if dmnet_path is not None:
+        from ...isp_kernels import demosaic as _dm
+        _dm.load_demosaicnet(dmnet_path, dmnet_cfa)
+        logger.info('DemosaicNet: weights %s (cfa %s)', dmnet_path, dmnet_cfa)
     module_path = opt_net['module_path'] if 'module_path' in opt_net else DEFAULT_MODULE_PATH
     which = opt_net['which_model_G']
 

@@ -1353,3 +1353,104 @@ def srcnn_demosaic_group(x, packs_list, cache, record=None):
     if gp is None or gp[0] != key:
         gp = cache['srcnn_demosaic'] = (key, SrcnnDemosaicGroup(packs_list))
     return list(_SrcnnDemosaicGroupFn.apply(x, gp[1], GROUP_LAUNCH, not torch.is_grad_enabled(), record))
+
+
+# --------------------------------------------------------------------------- DemosaicNet (demosaic index 04, tools_origin.py:289-308)
+class DemosaicNetPacks:
+    """The device form of a folded DemosaicNet (demosaicnet.fold): conv1 (pack_mosaic folded in) as a space-to-depth first layer
+    with its border-case bias table, conv2..14, conv15 as TWO 64-cout layers (filters half, masks half: both stay on the
+    split-precision kernel, ``route`` rule 2), and the fp32 weights of the tail and head kernels (risp_dmnet.hip)."""
+
+    def __init__(self, fd, device):
+        t = {k: v.to(device=device, dtype=torch.float32).contiguous() for k, v in fd.items()}
+        self.first = PackedConv(t['conv1.weight'], t['conv1.bias'])
+        self.first.small_bwd = SmallConv(t['conv1.weight'], None, transpose=True, keep=4)     # 64 -> 4 planes, backward-data
+        self.case = t['conv1.case'].unsqueeze(0)                                             # (1, 64, 3, 3)
+        self.body = [PackedConv(t['conv%d.weight' % i], t['conv%d.bias' % i]) for i in range(2, 15)]
+        w15, b15 = t['conv15.weight'], t['conv15.bias']
+        self.filters, self.masks = PackedConv(w15[:64], b15[:64]), PackedConv(w15[64:], b15[64:])
+        self.rp_w, self.rp_b, self.up_w, self.up_b = t['rp.weight'], t['rp.bias'], t['up.weight'], t['up.bias']
+        self.post_w, self.post_b, self.out_w, self.out_b = t['post.weight'], t['post.bias'], t['out.weight'], t['out.bias']
+
+
+def build_demosaicnet_packs(fd, device):
+    return DemosaicNetPacks(fd, device)
+
+
+def demosaicnet_check(x):
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError('DemosaicNet: expected a (N,1,H,W) RGGB mosaic, got %s' % (tuple(x.shape),))
+    n, _, hh, ww = x.shape
+    if hh % 2 or ww % 2 or hh < 4 or ww < 4 or hh * ww * 4 >= (1 << 31) or n > 65535:
+        raise ValueError('DemosaicNet: H and W must be even and at least 4, H*W*4 < 2^31, N <= 65535; got %s' % (tuple(x.shape),))
+
+
+class _DemosaicNet(torch.autograd.Function):
+    """Forward: conv1 .. conv15 at half resolution on the convolution kernels, then risp_dmnet_tail_fwd (gate, 1x1 64 -> 12, grouped
+    2x2 transposed conv) and risp_dmnet_head_fwd (3x3 6 -> 64, ReLU, 1x1 64 -> 3).  Backward: backward-data to the mosaic only (the
+    op has no trainable parameters) - head, tail, conv15's halves (the second adds onto the first through EPI_ADD, conv14's ReLU
+    through EPI_MASK), conv14 .. conv2, conv1 through its space-to-depth load (a PixelShuffle store), plus the head's direct mosaic
+    term.  ``record``: step-level reuse, as in ``_Path14l``."""
+
+    @staticmethod
+    def forward(ctx, x, packs, infer, record=None):
+        x = _dev(x, 'img')
+        demosaicnet_check(x)
+        n, _, hh, ww = x.shape
+        h, w = hh // 2, ww // 2
+        ctx.packs, ctx.dims = packs, (n, hh, ww)
+        if record is not None and 'y' in record:
+            ctx.save_for_backward(*record['saved'])
+            return record['y'].detach()
+        keep = not infer or record is not None
+        cvals = packs.case.expand(n, -1, -1, -1).contiguous()
+        f = conv(x, packs.first, n, h, w, load=LOAD_UNSHUFFLE2, cvals=cvals, epi=EPI_RELU | EPI_CASEBIAS, infer=infer)
+        acts = [f] if keep else []
+        for pc in packs.body:
+            f = conv(f, pc, n, h, w, epi=EPI_RELU, infer=infer)
+            if keep:
+                acts.append(f)
+        fa = conv(f, packs.filters, n, h, w, epi=EPI_RELU, infer=infer)
+        fb = conv(f, packs.masks, n, h, w, epi=EPI_RELU, infer=infer)
+        up = torch.empty((n, 3, hh, ww), device=x.device, dtype=torch.float32)
+        L.call('risp_dmnet_tail_fwd', _p(fa), _p(fb), _p(packs.rp_w), _p(packs.rp_b), _p(packs.up_w), _p(packs.up_b), _p(up),
+               n, hh, ww, _stream())
+        y = torch.empty((n, 3, hh, ww), device=x.device, dtype=torch.float32)
+        L.call('risp_dmnet_head_fwd', _p(x), _p(up), _p(packs.post_w), _p(packs.post_b), _p(packs.out_w), _p(packs.out_b), _p(y),
+               n, hh, ww, _stream())
+        saved = [x] + acts + [fa, fb, up] if keep else []
+        ctx.save_for_backward(*saved)
+        if record is not None:
+            record['y'], record['saved'] = y.detach(), saved
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        saved = ctx.saved_tensors
+        x, acts, (fa, fb, up) = saved[0], saved[1:-3], saved[-3:]
+        packs = ctx.packs
+        n, hh, ww = ctx.dims
+        h, w = hh // 2, ww // 2
+        gy = _dev(gy, 'grad')
+        g_up = torch.empty_like(up)
+        g_direct = torch.empty_like(x)
+        L.call('risp_dmnet_head_bwd', _p(gy), _p(x), _p(up), _p(packs.post_w), _p(packs.post_b), _p(packs.out_w), None,
+               _p(g_up), _p(g_direct), n, hh, ww, _stream())
+        ga, gb = torch.empty_like(fa), torch.empty_like(fb)
+        L.call('risp_dmnet_tail_bwd', _p(g_up), _p(fa), _p(fb), _p(packs.rp_w), _p(packs.up_w), _p(ga), _p(gb), n, hh, ww, _stream())
+        t = conv(ga, packs.filters, n, h, w, transpose=True)
+        g = conv(gb, packs.masks, n, h, w, transpose=True, epi=EPI_ADD | EPI_MASK, add=t, add_c=64, mask=acts[-1])
+        for k in range(len(packs.body) - 1, -1, -1):
+            g = conv(g, packs.body[k], n, h, w, transpose=True, epi=EPI_MASK, mask=acts[k])
+        gx = conv_small(g, packs.first.small_bwd, n, h, w, epi=EPI_SHUFFLE2)
+        # the mosaic gradient = the body's term + the head's direct term, in this order (the head's pass comes first: the body
+        # needs its g_up)
+        return gx.add_(g_direct), None, None, None
+
+
+def demosaicnet(x, packs, record=None):
+    """(N,1,H,W) RGGB mosaic -> (N,3,H,W) BGR (include/risp.h "DemosaicNet").  Inference launches when autograd is off
+    (see ``path14l``)."""
+    return _DemosaicNet.apply(x, packs, not torch.is_grad_enabled(), record)

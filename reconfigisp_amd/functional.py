@@ -803,6 +803,11 @@ class _HipImpl:
         packs = _packs(module, lambda: CN.build_path14l_packs(module.path_restore_14l, True))
         return CN.path14l(x, packs, False, module.__dict__.get('_risp_reuse'))
 
+    @staticmethod
+    def demosaicnet(x, net, record=None):
+        from . import convnets as CN
+        return CN.demosaicnet(x, net.packs(x.device), record)
+
 
 def _packs(module, build):
     from . import convnets as CN
@@ -935,6 +940,12 @@ def path14l_bayer(x, module):
 
 def path14l_bgr(x, module):
     return _IMPL.path14l_bgr(x, module)
+
+
+def demosaicnet(x, net, record=None):
+    """DemosaicNet (include/risp.h): (N,1,H,W) RGGB mosaic in [0,1] -> (N,3,H,W) BGR, differentiable in x.  ``net``: a
+    ``reconfigisp_amd.load_demosaicnet`` result; ``record``: step-level reuse (convnets._Path14l)."""
+    return _IMPL.demosaicnet(x, net, record)
 
 
 # ---------------------------------------------------------------------------

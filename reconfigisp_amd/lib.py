@@ -172,6 +172,10 @@ SIGNATURES = {
     'risp_origin_tonemap': (_i, [_f, _f, _i, _f, _f, _f, _f, _i, _i, _fl, _fl, _s]),
     'risp_origin_bm3d_scratch_bytes': (_z, [_i, _i, _i]),
     'risp_origin_bm3d': (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _fl, _fl, _f, _z, _f, _s]),
+    'risp_dmnet_tail_fwd': (_i, [_f] * 7 + [_i, _i, _i, _s]),
+    'risp_dmnet_tail_bwd': (_i, [_f] * 7 + [_i, _i, _i, _s]),
+    'risp_dmnet_head_fwd': (_i, [_f] * 7 + [_i, _i, _i, _s]),
+    'risp_dmnet_head_bwd': (_i, [_f] * 9 + [_i, _i, _i, _s]),
     'risp_bilateral_chain_fwd': (_i, [_f, _i, _f, _f, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _pp, _i, _i, _i, _s]),
     'risp_raw_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _fl, _s]),
     'risp_gt_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
