@@ -704,6 +704,26 @@ int risp_resize_rggb(const uint16_t *src, uint16_t *dst, int H0, int W0, int H, 
 size_t risp_sse_uint8_doubles(void);
 int risp_sse_uint8(const float *a, const float *b, double *sse, size_t sse_doubles, size_t numel, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * SSIM (risp_ssim.hip): get_ssim of the reference (utils/util_path_restore.py:27-44 - scikit-image's compare_ssim with
+ * multichannel=True and its defaults): uniform 7 x 7 window, K1 = 0.01, K2 = 0.03, C1 = (K1 L)^2, C2 = (K2 L)^2, sample
+ * covariance (49 / 48), S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) averaged over the windows that
+ * lie wholly inside the image, then over the channels.  x, y: planar fp32 (N,C,H,W), H, W >= 7, N C H W < 2^31,
+ * N C <= 65535.  L: data_range[n] (N floats ON THE DEVICE, no host read) or, data_range == NULL, data_range_scalar.
+ * ------------------------------------------------------------------------- */
+/* ssim[n], n < N.  quantise != 0: both images first go through tensor2bgr's arithmetic (utils/util.py:130-131,
+ * clip(v * 255, 0, 255) truncated, as risp_sse_uint8) and L is in codes (255 for the drivers' metric).  scratch:
+ * risp_ssim_scratch_floats(N, C, H, W) floats (one partial sum per workgroup; a finishing launch adds them in index order in
+ * fp64: no atomics, the same bits on every run).  Two launches. */
+size_t risp_ssim_scratch_floats(int N, int C, int H, int W);
+int risp_ssim_fwd(const float *x, const float *y, const float *data_range, float data_range_scalar, int quantise, float *ssim,
+                  float *scratch, size_t scratch_floats, int N, int C, int H, int W, void *stream);
+/* gx = d (sum_n gs[n] ssim[n]) / dx of the unquantised form (gs: N floats on the device; gx (N,C,H,W), every element
+ * written).  One launch that recomputes the window terms from x and y: nothing is kept from the forward call and no
+ * scratch is needed.  The target y receives no gradient. */
+int risp_ssim_bwd(const float *x, const float *y, const float *data_range, float data_range_scalar, const float *gs, float *gx,
+                  int N, int C, int H, int W, void *stream);
+
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments, named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic);

@@ -23,7 +23,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from ... import functional as F
-from ..utils.util_loss import latency_loss, local_global_loss
+from ..utils.util_loss import SSIM_KINDS, latency_loss, local_global_loss, ssim_criterion
 from . import networks
 from .base_model import BaseModel
 from .isp_model import make_schedulers
@@ -52,6 +52,8 @@ class PixelLoss(nn.Module):
 def _criterion(kind, train_opt, device):
     if kind == 'l1':
         return PixelLoss('l1').to(device)
+    if kind in SSIM_KINDS:
+        return ssim_criterion(kind, train_opt, PixelLoss).to(device)
     mse = PixelLoss('l2').to(device)
     if kind == 'l2':
         return mse

@@ -1,5 +1,5 @@
 """IspModel - trains / tests ONE fixed pipeline (mirror of models/isp_model.py:14-151):
-Adam on the pipeline parameters, L1 / L2 pixel loss, ``test()`` returning
+Adam on the pipeline parameters, L1 / L2 pixel loss (and, beyond the reference, SSIM and its mixtures with them), ``test()`` returning
 ``(output, intermediate_results)``.  Single device, as in the reference (:19-24)."""
 import logging
 from collections import OrderedDict
@@ -7,6 +7,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
+from ..utils.util_loss import SSIM_KINDS, ssim_criterion
 from . import lr_scheduler, networks
 from .base_model import BaseModel
 
@@ -26,11 +27,13 @@ def make_schedulers(optimizers, train_opt):
     raise NotImplementedError('MultiStepLR learning rate scheme is enough.')
 
 
-def pixel_criterion(kind, device):
+def pixel_criterion(kind, device, train_opt=None):
     if kind == 'l1':
         return nn.L1Loss().to(device)
     if kind == 'l2':
         return nn.MSELoss().to(device)
+    if kind in SSIM_KINDS:           # no fused training step for these: FusedIspStep.build takes nn.MSELoss / nn.L1Loss alone
+        return ssim_criterion(kind, train_opt, lambda name: nn.L1Loss() if name == 'l1' else nn.MSELoss()).to(device)
     raise NotImplementedError('pixel_criterion [{}]'.format(kind))
 
 
@@ -47,8 +50,8 @@ class IspModel(BaseModel):
         if self.is_train:
             train_opt = opt['train']
             self.netG.train()
-            self.cri_pix = pixel_criterion(train_opt['pixel_criterion'], self.device)
-            self.cri_pix_v = pixel_criterion(train_opt['pixel_criterion'], self.device)
+            self.cri_pix = pixel_criterion(train_opt['pixel_criterion'], self.device, train_opt)
+            self.cri_pix_v = pixel_criterion(train_opt['pixel_criterion'], self.device, train_opt)
             self.optimizer_G = torch.optim.Adam(self.netG.trainable_parameters, train_opt['lr_G'],
                                                 (train_opt['beta1'], train_opt['beta2']))
             self.optimizers.append(self.optimizer_G)

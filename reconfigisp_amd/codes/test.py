@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-image test driver (reference test.py:22-107): ``python test.py --opt options/test/X.yml``.
 Runs model.test() on every image, reports PSNR of input and output against the ground truth with the
-reference's truncating-uint8 metric, and writes [input | every stage | gt] side by side as one PNM
+reference's truncating-uint8 metric (``report_ssim: true`` in the option file adds the SSIM of the same images), and writes [input | every stage | gt] side by side as one PNM
 file per image (cv2 is not required)."""
 import argparse
 import logging
@@ -24,6 +24,13 @@ from .utils import util
 
 def as_three(img):
     return np.concatenate([img] * 3, axis=2) if img.shape[2] == 1 else img
+
+
+def report_ssim(img, gt, device):
+    """SSIM of the truncated 8-bit images the PSNR lines use (a one-plane Bayer input repeated over the three channels, as
+    ``as_three`` does), on the device"""
+    img, gt = img.to(device), gt.to(device)
+    return util.ssim_tensors(img.expand_as(gt) if img.shape[1] == 1 else img, gt)
 
 
 def write_ppm(path, bgr):
@@ -59,7 +66,7 @@ def main(argv=None):
         logger.info('\nTesting [{:s}]...'.format(name))
         out_dir = osp.join(opt['path']['results_root'], name)
         util.mkdir(out_dir)
-        psnr_in, psnr_out = [], []
+        psnr_in, psnr_out, ssim_in, ssim_out = [], [], [], []
         for idx, data in enumerate(loader):
             print('Image No. {}'.format(idx + 1))
             model.feed_data((data['noisy'], data['gt']))
@@ -67,10 +74,16 @@ def main(argv=None):
             img_in, img_gt = as_three(util.tensor2bgr(data['noisy'])), util.tensor2bgr(data['gt'])
             psnr_in.append(util.psnr(img_in, img_gt))
             psnr_out.append(util.psnr(util.tensor2bgr(out), img_gt))
+            if opt.get('report_ssim'):
+                ssim_in.append(report_ssim(data['noisy'], data['gt'], out.device))
+                ssim_out.append(report_ssim(out, data['gt'], out.device))
             panels = [img_in] + [as_three(util.tensor2bgr(m)) for m in mids] + [img_gt]
             write_ppm(osp.join(out_dir, '{:03d}.ppm'.format(idx + 1)), np.concatenate(panels, axis=1))
         for tag, v in (('in', np.asarray(psnr_in)), ('out', np.asarray(psnr_out))):
             print('PSNR {}: min {}, max {}, mean {}, std {}'.format(tag, v.min(), v.max(), v.mean(), v.std()))
+        if opt.get('report_ssim'):
+            for tag, v in (('in', np.asarray(ssim_in)), ('out', np.asarray(ssim_out))):
+                print('SSIM {}: min {}, max {}, mean {}, std {}'.format(tag, v.min(), v.max(), v.mean(), v.std()))
 
 
 if __name__ == '__main__':

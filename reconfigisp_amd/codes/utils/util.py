@@ -119,3 +119,15 @@ def psnr_tensors(a, b):
     L.call('risp_sse_uint8', F._p(a), F._p(b), C.c_void_p(sse.data_ptr()), sse.numel(), a.numel(), F._stream())
     mse = sse[0].item() / a.numel()
     return float('inf') if mse == 0 else 10 * math.log10(1. / mse)     # identical images: inf, like numpy's 1./0.
+
+
+def ssim_tensors(a, b):
+    """get_ssim's measure on tensor2bgr(a) against tensor2bgr(b) with data range 255, for device tensors in [0, 1] of equal
+    shape ((C,H,W) or (N,C,H,W)), without leaving the GPU (risp_ssim_fwd, quantised form): a float, or a list for N > 1."""
+    from ... import functional as F
+    if a.shape != b.shape:
+        raise ValueError('shape mismatch %s vs %s' % (tuple(a.shape), tuple(b.shape)))
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    v = F.ssim_quantised(a, b).tolist()
+    return v[0] if len(v) == 1 else v

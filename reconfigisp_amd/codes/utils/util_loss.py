@@ -2,7 +2,36 @@
 criterion runs on the device in one call (risp_local_global_l2: no boolean indexing, no host read of the flags); any other criterion, and
 tensors the kernel does not take, follow the reference's torch formulation."""
 import torch
+import torch.nn as nn
 import torch.nn.functional as TF
+
+SSIM_KINDS = {'ssim': None, 'l1_ssim': 'l1', 'l2_ssim': 'l2'}       # pixel_criterion -> the pixel term mixed in
+
+
+class SsimLoss(nn.Module):
+    """pixel_criterion ssim / l1_ssim / l2_ssim: (1 - w) * pixel(out, gt) + w * (1 - mean SSIM(out, gt)) with the SSIM of
+    get_ssim at data range 1 (functional.ssim_loss: forward and backward on the device).  ``pixel`` None: the SSIM term alone."""
+
+    def __init__(self, pixel=None, weight=1.0):
+        super().__init__()
+        self.pixel, self.weight = pixel, float(weight)
+
+    def forward(self, out, gt):
+        from ... import functional as F
+        loss = F.ssim_loss(out, gt)
+        if self.pixel is None:
+            return loss
+        return (1.0 - self.weight) * self.pixel(out, gt) + self.weight * loss
+
+
+def ssim_criterion(kind, train_opt, pixel):
+    """the criterion of an SSIM kind; ``pixel(name)`` builds the l1 / l2 term.  The mixed kinds need train.ssim_weight."""
+    if SSIM_KINDS[kind] is None:
+        return SsimLoss()
+    weight = train_opt.get('ssim_weight') if hasattr(train_opt, 'get') else None
+    if weight is None:
+        raise KeyError('pixel_criterion [{}] needs train.ssim_weight (the weight of the SSIM term, 0 .. 1)'.format(kind))
+    return SsimLoss(pixel(SSIM_KINDS[kind]), weight)
 
 
 def latency_loss(img_in, img_gt, latency, target_latency, w, fidelity_loss):

@@ -1,4 +1,4 @@
-"""Overlapped tiling for full-frame inference - mirror of utils/util_path_restore.py:47-134.
+"""Image-quality measures and overlapped tiling for full-frame inference - mirror of utils/util_path_restore.py:6-134.
 
 ``whole2patch`` / ``patch2whole`` / ``create_patch_mask`` keep the reference's numpy signatures
 (HWC arrays, positions, count map) but the gather / blend run on the GPU
@@ -22,6 +22,23 @@ def get_mse_psnr(x, y):
         mse = np.mean((x - y) ** 2)
         return mse, 10 * np.log10(1. / mse)
     raise ValueError('Invalid data!')
+
+
+def get_ssim(x, y):
+    """SSIM of the image(s) x against the reference(s) y (:27-44): HWC arrays -> a float, NHWC arrays -> an array with one
+    value per image.  The reference's call, compare_ssim(y, x, data_range=x.max() - x.min(), multichannel=True): the data
+    range is that of the INPUT image x, per image.  Evaluated on the GPU (risp_ssim_fwd); arrays of any real dtype are
+    taken as their values (uint8 codes stay codes)."""
+    x, y = np.asarray(x), np.asarray(y)
+    if x.ndim == 3:
+        return float(get_ssim(x[None], y[None])[0])
+    if x.ndim != 4:
+        raise ValueError('Invalid data!')
+    ranges = np.asarray([float(img.max()) - float(img.min()) for img in x], dtype=np.float32)
+    if not (ranges > 0).all():          # C1 = C2 = 0: flat windows are 0 / 0 (the package warns and returns NaN)
+        raise ValueError('get_ssim: a constant input image has data range 0, its SSIM is undefined')
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.transpose(a, (0, 3, 1, 2)), dtype=np.float32)).cuda()
+    return F.ssim(dev(x), dev(y), torch.from_numpy(ranges).cuda()).cpu().numpy().astype(np.float64)
 
 
 def tile_positions(full, size, stride):

@@ -588,6 +588,58 @@ class _LocalGlobalL2(torch.autograd.Function):
         return (g * gl if g is not None else None), None, None
 
 
+def _ssim_args(x, y, data_range):
+    """checked (x, y, per-image range tensor or None, scalar range) of the SSIM entry points"""
+    if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)) or x.dim() != 4 or x.shape != y.shape:
+        raise ValueError('ssim: expected two (N,C,H,W) tensors of one shape, got %s / %s' % (
+            tuple(getattr(x, 'shape', ())), tuple(getattr(y, 'shape', ()))))
+    if x.shape[2] < 7 or x.shape[3] < 7:
+        raise ValueError('ssim: the 7 x 7 window needs H, W >= 7, got H=%d W=%d' % (x.shape[2], x.shape[3]))
+    x, y = _dev(x, 'image'), _dev(y, 'target')
+    if isinstance(data_range, torch.Tensor):
+        dr = _dev(data_range, 'data_range').reshape(-1)
+        if dr.numel() == 1:
+            dr = dr.expand(x.shape[0]).contiguous()
+        if dr.numel() != x.shape[0]:
+            raise ValueError('ssim: data_range must hold one value or one per image (N=%d), got %d' % (x.shape[0], dr.numel()))
+        return x, y, dr, 0.0
+    return x, y, None, float(data_range)
+
+
+def _ssim_forward(x, y, dr, dr_scalar, quantise):
+    n, c, h, w = x.shape
+    out = torch.empty(n, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(L.load().risp_ssim_scratch_floats(n, c, h, w), device=x.device, dtype=torch.float32)
+    L.call('risp_ssim_fwd', _p(x), _p(y), _p(dr), dr_scalar, int(quantise), _p(out), _p(scratch), scratch.numel(), n, c, h, w,
+           _stream())
+    return out
+
+
+class _Ssim(torch.autograd.Function):
+    """ssim[n] of (N,C,H,W) images (risp_ssim_fwd) with the gradient with respect to the first one (risp_ssim_bwd, one launch
+    that recomputes the window terms: nothing but x and y is kept).  The target and the data range receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, data_range):
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError('ssim: the target receives no gradient (risp_ssim_bwd forms d/dx only); detach it')
+        x, y, dr, dr_scalar = _ssim_args(x, y, data_range)
+        ctx.save_for_backward(x, y, dr)
+        ctx.dr_scalar = dr_scalar
+        return _ssim_forward(x, y, dr, dr_scalar, False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gs):
+        x, y, dr = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        n, c, h, w = x.shape
+        gx = torch.empty_like(x)
+        L.call('risp_ssim_bwd', _p(x), _p(y), _p(dr), ctx.dr_scalar, _p(_dev(gs, 'gradient')), _p(gx), n, c, h, w, _stream())
+        return gx, None, None
+
+
 def _written(tensors):
     """The C ABI wrote these tensors in place: bump their version counters as a torch in-place op would - the mixture-weight
     cache and the step-level reuse of the super-net key on them (a shifted parameter must miss)."""
@@ -626,6 +678,15 @@ class _HipImpl:
     @staticmethod
     def local_global_l2(y, gt, flag):
         return _LocalGlobalL2.apply(y, gt, flag)
+
+    @staticmethod
+    def ssim(x, y, data_range):
+        return _Ssim.apply(x, y, data_range)
+
+    @staticmethod
+    def ssim_quantised(x, y):
+        x, y, dr, dr_scalar = _ssim_args(x, y, 255.0)
+        return _ssim_forward(x, y, dr, dr_scalar, True)
 
     @staticmethod
     def darts_virtual_step(rows, momentum, lr_meta):
@@ -874,6 +935,24 @@ def pixel_loss(y, gt, kind='l2'):
 def local_global_l2(y, gt, flag):
     """local_global_loss(y, gt, flag, nn.MSELoss()) of the reference (utils/util_loss.py:26-64): a 0-dim tensor"""
     return _IMPL.local_global_l2(y, gt, flag)
+
+
+def ssim(x, y, data_range=1.0):
+    """SSIM of every image of x against y, (N,C,H,W) -> (N,): get_ssim of the reference (utils/util_path_restore.py:27-44 -
+    7 x 7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance, valid windows, mean over channels).  ``data_range``: a
+    number, or a device tensor with one value per image.  Differentiable once with respect to x."""
+    return _IMPL.ssim(x, y, data_range)
+
+
+def ssim_loss(x, y, data_range=1.0):
+    """1 - mean_n ssim(x, y)[n]: a 0-dim tensor"""
+    return 1.0 - ssim(x, y, data_range).mean()
+
+
+def ssim_quantised(x, y):
+    """ssim of tensor2bgr(x) against tensor2bgr(y) (truncated 8-bit codes, data range 255) without leaving the GPU: (N,), no
+    gradient - the twin of utils.util.psnr_tensors"""
+    return _IMPL.ssim_quantised(x, y)
 
 
 def darts_virtual_step(rows, momentum, lr_meta):

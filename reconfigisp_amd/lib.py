@@ -183,6 +183,9 @@ SIGNATURES = {
     'risp_bilateral_chain_kernel': (C.c_char_p, [_i, _i, _i]),
     'risp_sse_uint8_doubles': (_z, []),
     'risp_sse_uint8': (_i, [_f, _f, _f, _z, _z, _s]),
+    'risp_ssim_scratch_floats': (_z, [_i, _i, _i, _i]),
+    'risp_ssim_fwd': (_i, [_f, _f, _f, _fl, _i, _f, _f, _z, _i, _i, _i, _i, _s]),
+    'risp_ssim_bwd': (_i, [_f, _f, _f, _fl, _f, _f, _i, _i, _i, _i, _s]),
     'risp_prune_softmax_fwd': (_i, [_f, _f, _fl, _i, _f, _f, _f, _s]),
     'risp_prune_softmax_bwd': (_i, [_f, _f, _f, _i, _f, _s]),
     'risp_param_blocks_fwd': (_i, [C.POINTER(ParamBlocksDesc), _s]),
