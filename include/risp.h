@@ -675,7 +675,9 @@ int risp_dmnet_head_bwd(const float *g_y, const float *x, const float *up, const
 /* Fused stencil segment (inference): [nearest demosaic ->] bilateral -> element-wise chain in one launch;
  * the BGR halo tile is staged in LDS (straight from the mosaic when from_bayer), every stage output is
  * written ([0,1] domain; the bilateral works on x255 values and returns codes/255 like the reference
- * wrapper, tools_origin.py:690,716).  ops/params/outs as in risp_chain_fwd (no demosaic op). W % 4 == 0. */
+ * wrapper, tools_origin.py:690,716).  ops/params/outs as in risp_chain_fwd (no demosaic op). W % 4 == 0.
+ * from_bayer with max_window == 3 and a 16-byte aligned mosaic runs without LDS and without a barrier: a thread
+ * owns two mosaic quads (2 x 4 pixels) and loads the ring of quads around them itself; same bits either way. */
 int risp_bilateral_chain_fwd(const float *in, int from_bayer, float *out_demosaic, float *out_bilateral,
                              const int32_t *window, const float *sigma_color, const float *sigma_space,
                              int max_window, int n_ops, const int *ops, const float *const *params,
@@ -724,7 +726,7 @@ int risp_ssim_fwd(const float *x, const float *y, const float *data_range, float
 int risp_ssim_bwd(const float *x, const float *y, const float *data_range, float data_range_scalar, const float *gs, float *gx,
                   int N, int C, int H, int W, void *stream);
 
-/* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments, named as rocprofv3 prints it
+/* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic);
 

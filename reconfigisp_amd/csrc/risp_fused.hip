@@ -12,6 +12,10 @@
 // thread then owns 4 consecutive pixels: bilateral from LDS, 8-bit rounding, back to [0,1], the
 // element-wise stages in registers, and 16-byte stores of every stage's planes.
 //
+// The instance the headline benchmark launches (nearest demosaic, 3 x 3 window) has a second form without LDS and
+// without a barrier, bilateral_chain_quad_kernel below: a thread owns two mosaic quads (2 x 4 pixels) and loads the
+// ring of quads around them itself.
+//
 // Arithmetic: oracle/isp_oracle.py origin_denoise('bilateral') (build-defined OPSPEC, parity unpinned;
 // call site tools_origin.py:686-710) and the element-wise contexts of risp_ops.h.
 #include "risp_common.h"
@@ -46,10 +50,36 @@ __device__ __forceinline__ void st4_nt(float *p, v4f v) {
 #ifndef RISP_STREAM_POLICY
 #define RISP_STREAM_POLICY "nt"            // tools/ab_fused.py: "sc1", "sc0 sc1", "sc1 nt" measured against it
 #endif
-    asm volatile("global_store_dwordx4 %0, %1, off " RISP_STREAM_POLICY ::"v"(p), "v"(v) : "memory");
+    // s_nop 1: a VALU write of the data registers needs two wait states after a store of more than 8 bytes, and the
+    // compiler's hazard recogniser does not see a store inside an asm statement
+    asm volatile("global_store_dwordx4 %0, %1, off " RISP_STREAM_POLICY "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+// the same policy through the compiler (hazards, wait counts and scheduling are its own).  The empty asm makes the
+// value opaque: a streamed and a plain store of one value in two branches would otherwise be merged into one plain store
+__device__ __forceinline__ void st4_stream(float *p, v4f v) {
+    asm("" : "+v"(v));
+    __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(p));
 }
 __device__ __forceinline__ float q8f(float v) {
     return floorf(__builtin_amdgcn_fmed3f(v, 0.f, 255.f) + 0.5f);   // clamp in one instruction (v is never NaN here)
+}
+
+// XCD-aware tile order: the hardware deals consecutive workgroups round-robin to the 8 XCDs, so tile neighbours -
+// which share a halo ring - land on 8 different L2s.  Remapped, XCD k works through the k-th contiguous eighth of
+// the tile list and the neighbours' halo reads hit its own L2 (tools/ab_fused.py, 2000 launches rotating over 4
+// resident batches: 46.2 -> 45.5 us; -DRISP_FUSED_NO_XCD_MAP restores the plain order for A/B).
+__device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz) {
+    bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+#ifndef RISP_FUSED_NO_XCD_MAP
+    const unsigned total = gridDim.x * gridDim.y * gridDim.z;
+    if ((total & 7u) == 0) {
+        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+        const unsigned t = (lin & 7u) * (total >> 3) + (lin >> 3);
+        bx = t % gridDim.x;
+        by = (t / gridDim.x) % gridDim.y;
+        bz = t / (gridDim.x * gridDim.y);
+    }
+#endif
 }
 
 // RT: compile-time halo radius (1 = the 3x3 window every reference configuration produces, because
@@ -62,26 +92,9 @@ __global__ __launch_bounds__(256, RISP_FUSED_WAVES) void bilateral_chain_kernel(
     extern __shared__ float lds[];
     const int R = RT > 0 ? RT : a.R, H = a.H, W = a.W;
     const int tw = FX + 2 * R, th = FY + 2 * R, per = tw * th;
-#ifndef RISP_FUSED_NO_XCD_MAP
-    // XCD-aware tile order: the hardware deals consecutive workgroups round-robin to the 8 XCDs, so tile neighbours -
-    // which share a halo ring - land on 8 different L2s.  Remapped, XCD k works through the k-th contiguous eighth of
-    // the tile list and the neighbours' halo reads hit its own L2 (tools/ab_fused.py, 2000 launches rotating over 4
-    // resident batches: 46.2 -> 45.5 us; -DRISP_FUSED_NO_XCD_MAP restores the plain order for A/B).
-    int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
-    {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if ((total & 7u) == 0) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned t = (lin & 7u) * (total >> 3) + (lin >> 3);
-            bxi = t % gridDim.x;
-            byi = (t / gridDim.x) % gridDim.y;
-            bzi = t / (gridDim.x * gridDim.y);
-        }
-    }
+    int bxi, byi, bzi;
+    xcd_tile(bxi, byi, bzi);
     const int n = bzi, x0 = bxi * FX, y0 = byi * FY;
-#else
-    const int n = blockIdx.z, x0 = blockIdx.x * FX, y0 = blockIdx.y * FY;
-#endif
     const size_t plane = (size_t)H * W;
 
     // ---- stage the BGR halo tile (raw [0,1] samples; the x255 of the bilateral's domain is applied on read).
@@ -257,7 +270,150 @@ __global__ __launch_bounds__(256, RISP_FUSED_WAVES) void bilateral_chain_kernel(
     }
 }
 
+// ---------------------------------------------------------------- barrier-free quad form (nearest demosaic, 3 x 3 window)
+// After the nearest demosaic the four pixels of a 2 x 2 mosaic quad share B and R and carry one of two greens (G1 on
+// the even row, G2 on the odd row), and the 3 x 3 window of a pixel reaches only its own quad and three adjacent ones.
+// A thread owns a 2 x 4 pixel patch (two quads) and loads the 3 x 4 quads around it from the mosaic itself - 6 mosaic
+// rows x (8 + 16 + 8 bytes), all issued before the first use; the ring is the neighbours' own data and comes from L1 /
+// the XCD's L2 - so there is no LDS, no barrier, and the stores of a wave start as soon as ITS loads are back.
+// Reflect-101 maps the pixel one step outside the image onto the same row parity of the border quad, i.e. it is a
+// clamp of the quad index.  Per pixel the taps are the expressions of bilateral_chain_kernel in the same order:
+// the two forms give the same bits (tests/test_gpu_fused_quad.py).
+#ifndef RISP_QUAD_TX
+#define RISP_QUAD_TX 16                     // threads across a workgroup; tile = (4 TX) x (2 * 256 / TX) pixels
+#endif
+constexpr int QTX = RISP_QUAD_TX, QTY = 256 / QTX;
+static_assert(QTX * QTY == 256, "RISP_QUAD_TX must divide 256");
+
+template <bool WBQ>
+__global__ __launch_bounds__(256) void bilateral_chain_quad_kernel(const FusedArgs a) {
+    const int H = a.H, W = a.W;
+    int bxi, byi, bzi;
+    xcd_tile(bxi, byi, bzi);
+    const int n = bzi;
+    const int px = (bxi * QTX + (int)(threadIdx.x % QTX)) * 4, py = (byi * QTY + (int)(threadIdx.x / QTX)) * 2;
+    if (px >= W || py >= H) return;                     // W % 4 == 0, H % 2 == 0: a patch is in or out as a whole
+    const size_t plane = (size_t)H * W;
+
+    // ---- the 3 x 4 quads around the patch: quad rows j-1, j, j+1 and quad columns i-1 .. i+2, clamped to the image
+    const float *bay = a.in + (size_t)n * plane;
+    const int j = py >> 1, i = px >> 1, qh = H >> 1, qw = W >> 1;
+    const int jr[3] = {j > 0 ? j - 1 : 0, j, j + 1 < qh ? j + 1 : qh - 1};
+    const int xl = 2 * (i > 0 ? i - 1 : 0), xr = 2 * (i + 2 < qw ? i + 2 : qw - 1);
+    float2 ml[6], mr[6];
+    float4 mc[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float *row = bay + (size_t)(2 * jr[k >> 1] + (k & 1)) * W;
+        ml[k] = *reinterpret_cast<const float2 *>(row + xl);
+        mc[k] = *reinterpret_cast<const float4 *>(row + px);
+        mr[k] = *reinterpret_cast<const float2 *>(row + xr);
+    }
+    // RGGB: R (even row, even column), G1 (even, odd), G2 (odd, even), B (odd, odd); qg[..][p] is the green of row parity p
+    float qb[3][4], qg[3][4][2], qr[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float2 e[4] = {ml[2 * k], make_float2(mc[2 * k].x, mc[2 * k].y), make_float2(mc[2 * k].z, mc[2 * k].w), mr[2 * k]};
+        const float2 o[4] = {ml[2 * k + 1], make_float2(mc[2 * k + 1].x, mc[2 * k + 1].y),
+                             make_float2(mc[2 * k + 1].z, mc[2 * k + 1].w), mr[2 * k + 1]};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            qr[k][c] = e[c].x;
+            qg[k][c][0] = e[c].y;
+            qg[k][c][1] = o[c].x;
+            qb[k][c] = o[c].y;
+        }
+    }
+    const size_t o = (size_t)n * 3 * plane + (size_t)py * W + px;
+
+    // ---- the demosaic stage output: the mosaic samples themselves
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const v4f vb = {qb[1][1], qb[1][1], qb[1][2], qb[1][2]}, vg = {qg[1][1][p], qg[1][1][p], qg[1][2][p], qg[1][2][p]},
+                  vr = {qr[1][1], qr[1][1], qr[1][2], qr[1][2]};
+        st4_stream(a.out_dem + o + (size_t)p * W, vb);
+        st4_stream(a.out_dem + o + (size_t)p * W + plane, vg);
+        st4_stream(a.out_dem + o + (size_t)p * W + 2 * plane, vr);
+    }
+
+    // ---- bilateral on the 8 pixels, in the 0..255 domain
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            qb[k][c] *= 255.f; qg[k][c][0] *= 255.f; qg[k][c][1] *= 255.f; qr[k][c] *= 255.f;
+        }
+    const bool full = a.win[n] / 2 >= 1;               // wave-uniform; the radius is clamped to [0, 1] as in the LDS form
+    const float ks = -1.f / (2.f * a.sig_s[n] * a.sig_s[n]), kc = -1.f / (2.f * a.sig_c[n] * a.sig_c[n]);
+    const float ks2 = ks * 1.4426950408889634f, kc2 = kc * 1.4426950408889634f;     // base-2 exponent coefficients
+    f3 pix[2][PXT];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int c = 0; c < PXT; ++c) {
+            // pixel (p, c) of the patch sits at row 2 + p, column 2 + c of the 6 x 8 pixels the 3 x 4 quads cover
+            const float cb = qb[1][1 + c / 2], cg = qg[1][1 + c / 2][p], cr = qr[1][1 + c / 2];
+            float nb = 0.f, ng = 0.f, nr = 0.f, den = 0.f;
+            auto tap = [&](int dy, int dx) {           // bilateral_chain_kernel's tap(), the neighbour read from registers
+                if (dy == 0 && dx == 0) {
+                    nb += cb; ng += cg; nr += cr; den += 1.f;
+                    return;
+                }
+                const int ty = 2 + p + dy, tx = 2 + c + dx;
+                const float tb = qb[ty / 2][tx / 2], tg = qg[ty / 2][tx / 2][ty & 1], tr = qr[ty / 2][tx / 2];
+                const float dist = fabsf(tb - cb) + fabsf(tg - cg) + fabsf(tr - cr);
+                const float wgt = __builtin_amdgcn_exp2f(__builtin_fmaf(dist * dist, kc2, (float)(dy * dy + dx * dx) * ks2));
+                nb = __builtin_fmaf(wgt, tb, nb); ng = __builtin_fmaf(wgt, tg, ng); nr = __builtin_fmaf(wgt, tr, nr); den += wgt;
+            };
+            if (full) {
+#pragma unroll
+                for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                    for (int dx = -1; dx <= 1; ++dx) tap(dy, dx);
+            } else {
+                tap(0, 0);                              // window 1: the weighted mean of one tap, then the 8-bit rounding
+            }
+            const float inv255 = 1.f / 255.f, rden = 1.f / den;
+            pix[p][c] = {q8f(nb * rden) * inv255, q8f(ng * rden) * inv255, q8f(nr * rden) * inv255};
+        }
+    auto store = [&](float *dst, bool stream) {        // same policies as the LDS form: stream all but the segment's result
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const v4f vb = {pix[p][0].b, pix[p][1].b, pix[p][2].b, pix[p][3].b}, vg = {pix[p][0].g, pix[p][1].g, pix[p][2].g, pix[p][3].g},
+                      vr = {pix[p][0].r, pix[p][1].r, pix[p][2].r, pix[p][3].r};
+            float *d = dst + o + (size_t)p * W;
+            if (stream) {
+                st4_stream(d, vb);
+                st4_stream(d + plane, vg);
+                st4_stream(d + 2 * plane, vr);
+            } else {
+                *reinterpret_cast<v4f *>(d) = vb;
+                *reinterpret_cast<v4f *>(d + plane) = vg;
+                *reinterpret_cast<v4f *>(d + 2 * plane) = vr;
+            }
+        }
+    };
+    store(a.out_bil, a.last_out >= 0);
+
+    // ---- element-wise stages
+    for (int k = 0; k < a.n_ops; ++k) {
+        apply_op<2 * PXT, WBQ>(a.ops[k], a.params[k], n, &pix[0][0]);
+        if (a.outs[k]) store(a.outs[k], k < a.last_out);
+    }
+}
+
 }  // namespace
+
+// Which arguments take the barrier-free quad form.  -DRISP_FUSED_LDS_FORM restores the LDS form everywhere (A/B builds:
+// tools/ab_fused.py).
+static bool quad_form(int from_bayer, int max_window) {
+#ifdef RISP_FUSED_LDS_FORM
+    (void)from_bayer, (void)max_window;
+    return false;
+#else
+    return from_bayer && max_window / 2 == 1;
+#endif
+}
 
 extern "C" {
 
@@ -315,7 +471,12 @@ int risp_bilateral_chain_fwd(const float *in, int from_bayer, float *out_demosai
         if (wbq) hipLaunchKernelGGL((bilateral_chain_kernel<FB, RTV, true>), grid, dim3(256), lds, s, a);     \
         else hipLaunchKernelGGL((bilateral_chain_kernel<FB, RTV, false>), grid, dim3(256), lds, s, a);        \
     } while (0)
-    if (a.R == 1) {
+    if (quad_form(from_bayer, max_window) && reinterpret_cast<uintptr_t>(in) % 16 == 0) {
+        // 16-byte loads of the patch's own mosaic columns: a mosaic that is only 8-byte aligned takes the LDS form below
+        const dim3 qgrid((W / 4 + QTX - 1) / QTX, (H / 2 + QTY - 1) / QTY, N);
+        if (wbq) hipLaunchKernelGGL((bilateral_chain_quad_kernel<true>), qgrid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((bilateral_chain_quad_kernel<false>), qgrid, dim3(256), 0, s, a);
+    } else if (a.R == 1) {
         if (from_bayer) RISP_FUSED_LAUNCH(true, 1);
         else RISP_FUSED_LAUNCH(false, 1);
     } else {
@@ -328,7 +489,10 @@ int risp_bilateral_chain_fwd(const float *in, int from_bayer, float *out_demosai
 }
 
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic) {
-    // the instance the dispatch above launches for these arguments, as a profiler prints it (profiles/traffic.json is keyed on it)
+    // the instance the dispatch above launches for these arguments (16-byte aligned input), as a profiler prints it
+    // (profiles/traffic.json is keyed on it)
+    if (quad_form(from_bayer, max_window))
+        return with_wb_quadratic ? "bilateral_chain_quad_kernel<true>" : "bilateral_chain_quad_kernel<false>";
     static const char *names[2][2][2] = {
         {{"bilateral_chain_kernel<false,0,false>", "bilateral_chain_kernel<false,0,true>"},
          {"bilateral_chain_kernel<false,1,false>", "bilateral_chain_kernel<false,1,true>"}},

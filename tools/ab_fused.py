@@ -1,5 +1,14 @@
 #!/usr/bin/env python3
-"""GPU box: in-process A/B of builds of risp_fused.hip with different -D flags (interleaved rounds)."""
+"""GPU box: in-process A/B of builds of risp_fused.hip with different -D flags (interleaved rounds).
+
+    python tools/ab_fused.py [variant ...]
+a variant is '' (the source as it is), '-Dflag[,-Dflag]', 'other_fused.hip[,-Dflag]' or a library built beforehand
+('path/to/lib.so').  The barrier-free quad form against the LDS form it replaces, and its workgroup shapes:
+
+    RISP_AB_REPS=2000 python tools/ab_fused.py '' -DRISP_FUSED_LDS_FORM -DRISP_QUAD_TX=32 -DRISP_QUAD_TX=64
+
+Per variant: the time per launch of each of the 7 rounds, then median and minimum - the spread between the rounds of
+ONE variant is the noise a difference between two variants has to clear."""
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -11,6 +20,9 @@ default_src = os.path.join(ROOT, 'reconfigisp_amd/csrc/risp_fused.hip')
 import torch  # before dlopen: the library must bind to the HIP runtime PyTorch already loaded
 libs = {}
 for i, v in enumerate(variants):
+    if v.endswith('.so'):                # built beforehand
+        libs[v] = C.CDLL(os.path.join(ROOT, v))
+        continue
     so = '/tmp/fused_%d.so' % i
     # a variant is "-Dflags" (current source) or "path/to/other_fused.hip[,-Dflags]" (another source file)
     parts = v.split(',') if v else []
@@ -63,4 +75,5 @@ for nsets in (1, NSETS):
             e1.record(); e1.synchronize()
             res[name].append(e0.elapsed_time(e1) / REPS * 1e3)
     for k, v in res.items():
-        print('%d set(s) %-40s median %.1f us  min %.1f' % (nsets, k, sorted(v)[len(v) // 2], min(v)))
+        print('%d set(s) %-40s rounds %s' % (nsets, k, ' '.join('%.2f' % t for t in v)))
+        print('%d set(s) %-40s median %.2f us  min %.2f  spread %.2f' % (nsets, k, sorted(v)[len(v) // 2], min(v), max(v) - min(v)))
