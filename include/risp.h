@@ -677,7 +677,15 @@ int risp_dmnet_head_bwd(const float *g_y, const float *x, const float *up, const
  * written ([0,1] domain; the bilateral works on x255 values and returns codes/255 like the reference
  * wrapper, tools_origin.py:690,716).  ops/params/outs as in risp_chain_fwd (no demosaic op). W % 4 == 0.
  * from_bayer with max_window == 3 and a 16-byte aligned mosaic runs without LDS and without a barrier: a thread
- * owns two mosaic quads (2 x 4 pixels) and loads the ring of quads around them itself; same bits either way. */
+ * owns two mosaic quads (2 x 4 pixels) and loads the ring of quads around them itself; same bits either way.
+ * Rules (anything else is refused before a launch): max_window odd, 1 .. 17 (1: radius 0, the 8-bit rounding alone);
+ * window[n] is clamped to [1, max_window]; 1 <= N <= 65535, H even, W % 4 == 0, H and W > max_window / 2 (one
+ * reflection reaches every tap).  0 <= n_ops <= RISP_MAX_CHAIN, ops[k] one of SKIP, WB_MANUAL, GAMMA, GTM_MANUAL,
+ * WB_QUADRATIC, GAIN3 in ANY order and any number of times each (every stage has its own parameter block and output);
+ * a SKIP stage needs neither params[k] nor outs[k] and may stand anywhere - the last stage that is not a SKIP holds the
+ * segment's result.  Alignment: every output 16-byte aligned; the input at any float.  A mosaic with max_window == 3 is
+ * read in vectors where it allows them - 16-byte aligned: the quad form, 8-byte: the LDS form with radius 1, otherwise
+ * the run-time-radius LDS form, which reads single floats like every other input; the same bits in all three. */
 int risp_bilateral_chain_fwd(const float *in, int from_bayer, float *out_demosaic, float *out_bilateral,
                              const int32_t *window, const float *sigma_color, const float *sigma_space,
                              int max_window, int n_ops, const int *ops, const float *const *params,

@@ -476,7 +476,8 @@ int risp_bilateral_chain_fwd(const float *in, int from_bayer, float *out_demosai
         const dim3 qgrid((W / 4 + QTX - 1) / QTX, (H / 2 + QTY - 1) / QTY, N);
         if (wbq) hipLaunchKernelGGL((bilateral_chain_quad_kernel<true>), qgrid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((bilateral_chain_quad_kernel<false>), qgrid, dim3(256), 0, s, a);
-    } else if (a.R == 1) {
+    } else if (a.R == 1 && (!from_bayer || reinterpret_cast<uintptr_t>(in) % 8 == 0)) {
+        // 8-byte loads of the mosaic's quad rows: a mosaic at an odd float offset takes the run-time-radius form (single floats)
         if (from_bayer) RISP_FUSED_LAUNCH(true, 1);
         else RISP_FUSED_LAUNCH(false, 1);
     } else {

@@ -1,8 +1,9 @@
 """GPU: the barrier-free quad form of the fused stencil segment (bilateral_chain_quad_kernel, risp_fused.hip) must give
 the bits of the stage-by-stage path: nearest demosaic, bilateral (3 x 3 window), then the element-wise tail, each as
-its own launch.  The shapes walk through every border case of the 2 x 4 patch and its ring of neighbour quads: one
-quad row, one patch column, tiles cut by the image edge, a tile count that is not a multiple of 8 (plain tile order
-instead of the XCD-aware one), and the headline batch."""
+its own launch.  The shapes walk through border cases of the 2 x 4 patch and its ring of neighbour quads: one
+quad row, two patch columns, tiles cut by the image edge, a tile count that is not a multiple of 8 (plain tile order
+instead of the XCD-aware one), and the headline batch.  (One patch column - W = 4, both neighbour columns clamped - and
+the rest of the argument space: tests/test_gpu_fused_segment.py.)"""
 import pytest
 import torch
 
