@@ -58,8 +58,13 @@ class LazyScalar:
 class FusedIspStep:
     def __init__(self, net, stages, from_bayer, loss_kind, optimizer):
         self.net, self.stages, self.from_bayer, self.loss_kind, self.opt = net, stages, from_bayer, loss_kind, optimizer
-        self.group = optimizer.param_groups[0]
         self._plan = None
+
+    @property
+    def group(self):
+        # read at every step: optimizer.load_state_dict() replaces the param_groups list and the dicts in it, and a
+        # reference kept from the constructor would go on reading the learning rate of the discarded one
+        return self.opt.param_groups[0]
 
     # ------------------------------------------------------------------ applicability
     @staticmethod

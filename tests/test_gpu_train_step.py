@@ -1,6 +1,8 @@
 """GPU: the fused fixed-pipeline training step (risp_chain_train_step: forward + pixel loss + backward + Adam in two
 launches) against the op-by-op autograd path it replaces (IspModel.optimize_parameters, models/isp_model.py:128-142)
 and against the reference golden (tests/golden/isp_model.npz case a runs through it in test_host_logic)."""
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -83,3 +85,155 @@ def test_fused_step_is_bit_repeatable_and_not_taken_for_cnn_pipelines():
     cnn.feed_data((img[:1], gt[:1]))
     cnn.optimize_parameters()
     assert cnn._fused is False and isinstance(cnn.log_dict['loss'], float)
+
+
+# ---------------------------------------------------------------------------------------------------- the host side
+# What FusedIspStep does around the launch: the optimiser stays the owner of its state, the per-image blocks follow the
+# parameters' version counters, the learning rate is read every step.  (The kernel itself: test_gpu_train_step_space.py.)
+_ARCH = 'Demosaic_01_sRGB_11_01_13_14'                         # mosaic | wbmanual gamma wbquadratic gtmmanual
+
+
+def _batches(count, n=3, h=32, w=48, seed=20):
+    return [O.synthetic_raw(n, h, w, seed=seed + i) for i in range(count)]
+
+
+def _step(model, it, batch):
+    model.feed_data(batch)
+    model.update_learning_rate(it, warmup_iter=-1)
+    model.optimize_parameters()
+    assert model._fused, 'the fused path was not taken'
+    state = model.optimizer_G.state_dict()['state']
+    return dict(output=model.output.clone(), loss=torch.tensor(float(model.log_dict['loss'])),
+                params=[p.detach().clone() for p in model.netG.parameters() if p.numel()],
+                grads=[p.grad.clone() for p in model.netG.parameters() if p.numel()],
+                steps=[torch.as_tensor(float(s['step'])) for s in state.values()],
+                exp_avg=[s['exp_avg'].clone() for s in state.values()], exp_avg_sq=[s['exp_avg_sq'].clone() for s in state.values()])
+
+
+def _assert_same_bits(a, b, what):
+    assert a.keys() == b.keys()
+    for key in a:
+        xs, ys = (a[key], b[key]) if isinstance(a[key], list) else ([a[key]], [b[key]])
+        assert len(xs) == len(ys) and len(xs) > 0
+        for k, (x, y) in enumerate(zip(xs, ys)):
+            assert torch.equal(x, y), '%s: %s[%d] differs (max %g)' % (what, key, k, (x.double() - y.double()).abs().max().item())
+
+
+def _fresh_copy(model, arch=_ARCH, crit='l2'):
+    """a fresh model put into ``model``'s state through the state dicts of its net and its optimiser (a resumed run:
+    its FusedIspStep is built anew at its first step)"""
+    twin = _model(arch, crit, True)
+    twin.netG.load_state_dict(model.netG.state_dict())
+    # a copy, as a checkpoint on disk is: Optimizer.load_state_dict keeps tensors that already have the right device and
+    # dtype, and the two models would share their moments
+    twin.optimizer_G.load_state_dict(copy.deepcopy(model.optimizer_G.state_dict()))
+    assert twin._fused is None
+    return twin
+
+
+@pytest.mark.filterwarnings('ignore:Detected call of')
+def test_resumed_run_gives_the_bits_of_the_uninterrupted_run():
+    data = _batches(6)
+    whole = _model(_ARCH, 'l2', True)
+    want = [_step(whole, it, b) for it, b in enumerate(data)]
+    first = _model(_ARCH, 'l2', True)
+    for it in range(3):
+        _assert_same_bits(_step(first, it, data[it]), want[it], 'step %d' % (it + 1))
+    resumed = _fresh_copy(first)
+    for it in range(3, 6):
+        _assert_same_bits(_step(resumed, it, data[it]), want[it], 'resumed, step %d' % (it + 1))
+    assert [float(s['step']) for s in resumed.optimizer_G.state_dict()['state'].values()] == [6.0] * 4
+
+
+@pytest.mark.filterwarnings('ignore:Detected call of')
+@pytest.mark.parametrize('event', ['zero_grad', 'batch size', 'parameter edit', 'optimizer reload'])
+def test_events_between_steps_equal_a_fresh_model_in_that_state(event):
+    data = _batches(2) + [O.synthetic_raw(2, 32, 48, seed=31)]
+    model = _model(_ARCH, 'l1', True)
+    _step(model, 0, data[0])
+    if event == 'zero_grad':
+        model.optimizer_G.zero_grad(set_to_none=True)
+        assert all(p.grad is None for p in model.netG.parameters())
+        nxt = data[1]
+    elif event == 'batch size':                                # another N: the plan (blocks, scratch) is rebuilt
+        nxt = data[2]
+    elif event == 'optimizer reload':                          # load_state_dict into the optimiser of a RUNNING model replaces
+        model.optimizer_G.load_state_dict(model.optimizer_G.state_dict())      # its param_groups; then a scheduler halves the rate
+        model.optimizer_G.param_groups[0]['lr'] *= 0.5
+        nxt = data[1]
+    else:                                                      # the version counters move: the blocks are rebuilt
+        with torch.no_grad():
+            for p in model.netG.parameters():
+                if p.numel():
+                    p.mul_(0.9).add_(0.05)
+        nxt = data[1]
+    twin = _fresh_copy(model, crit='l1')
+    got, want = _step(model, 1, nxt), _step(twin, 1, nxt)
+    _assert_same_bits(got, want, event)
+    assert got['output'].shape[0] == nxt[0].shape[0] and all(float(s) == 2.0 for s in got['steps'])
+    moved = [(a - b).abs().max().item() for a, b in zip(got['params'], [p.detach() for p in twin.netG.parameters() if p.numel()])]
+    assert max(moved) == 0.0
+
+
+@pytest.mark.filterwarnings('ignore:Detected call of')
+def test_a_milestone_inside_the_run_is_seen_by_the_next_step():
+    """MultiStepLR with a milestone at 3: the third step runs at half the rate.  Every step against the float64
+    restatement of tests/train_step_reference.py started from the model's own state, with the rate the SCHEDULE gives
+    (not the one read back from the optimiser), by conftest.ErrorBudget."""
+    import train_step_reference as R
+    from conftest import ErrorBudget
+    from reconfigisp_amd.codes.models import create_model
+    opt = isp_opt(torch.device('cuda'), 'OriginUniversal', _ARCH, 'l2')
+    opt['train']['lr_steps'] = [3]
+    opt['train']['lr_G'] = lr0 = 4e-2                          # updates well above the ulp of the parameters they move
+    torch.manual_seed(1)
+    model = create_model(opt)
+    ops = [R.OP_WB_MANUAL, R.OP_GAMMA, R.OP_WB_QUADRATIC, R.OP_GTM_MANUAL]
+    pars = [p for p in model.netG.parameters() if p.numel()]
+    zeros = lambda: [torch.zeros(p.numel()) for p in pars]
+    raw, m, v = [p.detach().cpu().clone() for p in pars], zeros(), zeros()
+    budget = ErrorBudget()
+    for it, (img, gt) in enumerate(_batches(4)):
+        lr = lr0 * (0.5 if it + 1 >= 3 else 1.0)
+        got = _step(model, it, (img, gt))
+        assert model.get_current_learning_rate() == lr
+        r32, r64 = [R.reference_step(ops, True, R.LOSS_MSE, img, gt, raw, m, v, it + 1, lr, (0.9, 0.99), 1e-8, dt)
+                    for dt in (torch.float32, torch.float64)]
+        for k in range(len(ops)):
+            budget(got['params'][k].cpu().double() - raw[k].double(), r32[3][k].double() - raw[k].double(), r64[3][k] - raw[k].double(),
+                   'it%d update %d' % (it, k), 'updates')
+            budget(got['grads'][k], r32[2][k], r64[2][k], 'it%d grad %d' % (it, k), 'param grads')
+        budget(got['output'], r32[0], r64[0], 'it%d output' % it, 'outputs')
+        raw, m, v = [t.cpu() for t in got['params']], [t.cpu() for t in got['exp_avg']], [t.cpu() for t in got['exp_avg_sq']]
+    budget.finish()
+
+
+@pytest.mark.filterwarnings('ignore:Detected call of')
+def test_inputs_the_fused_step_does_not_accept_take_the_autograd_path():
+    model = _model('sRGB_11_01_14', 'l2', True)
+    g = np.random.Generator(np.random.PCG64(8))
+    rnd = lambda *s: torch.from_numpy(g.random(s).astype(np.float32))
+    model.feed_data((rnd(2, 3, 16, 16), rnd(2, 3, 16, 16)))
+    model.optimize_parameters()
+    fused = model._fused
+    assert fused and fused.accepts(model.img, model.gt)
+    cases = {'odd H': (rnd(2, 3, 15, 16), rnd(2, 3, 15, 16)), 'odd W': (rnd(2, 3, 16, 17), rnd(2, 3, 16, 17)),
+             'float64 input': (rnd(2, 3, 16, 16).double(), rnd(2, 3, 16, 16))}
+    assert not fused.accepts(rnd(2, 3, 16, 16), rnd(2, 3, 16, 16))                   # CPU tensors (feed_data moves a batch to the
+    assert not fused.accepts(rnd(2, 3, 16, 16).cuda(), rnd(2, 3, 16, 16))            # device, so a model never hands these over)
+    assert not fused.accepts(rnd(2, 1, 16, 16).cuda(), rnd(2, 3, 16, 16).cuda())     # a mosaic into a BGR pipeline
+    assert not fused.accepts(rnd(2, 3, 16, 16).cuda(), rnd(2, 3, 16, 18).cuda())
+    for what, (img, gt) in cases.items():
+        assert not fused.accepts(img.cuda(), gt.cuda()), what
+        before = [p.detach().clone() for p in model.netG.parameters() if p.numel()]
+        steps = [float(s['step']) for s in model.optimizer_G.state_dict()['state'].values()]
+        model.feed_data((img, gt))
+        model.optimize_parameters()
+        assert isinstance(model.log_dict['loss'], float) and np.isfinite(model.log_dict['loss']), what     # .item(): the autograd path
+        assert model.output.shape == gt.shape and model.output.requires_grad, what
+        after = [p.detach() for p in model.netG.parameters() if p.numel()]
+        assert all((a - b).abs().max().item() > 1e-4 for a, b in zip(after, before)), '%s: a parameter did not move' % what
+        assert [float(s['step']) for s in model.optimizer_G.state_dict()['state'].values()] == [s + 1 for s in steps], what
+    model.feed_data((rnd(2, 3, 16, 16), rnd(2, 3, 16, 16)))                          # and back on the fused path
+    model.optimize_parameters()
+    assert not isinstance(model.log_dict['loss'], float) and not model.output.requires_grad
