@@ -734,6 +734,29 @@ int risp_ssim_fwd(const float *x, const float *y, const float *data_range, float
 int risp_ssim_bwd(const float *x, const float *y, const float *data_range, float data_range_scalar, const float *gs, float *gx,
                   int N, int C, int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Serving path (risp_serve.hip): 8-bit images on the device.
+ * ------------------------------------------------------------------------- */
+/* tensor2bgr on the device (utils/util.py:87-94), batched: planar fp32 x (N,C,H,W) -> packed bytes out (N,H,W,C),
+ * out = clip(x * 255, 0, 255) truncated, the product in fp32 (the bytes risp_sse_uint8 scores).  C is 1 or 3; any N, H,
+ * W >= 1, odd sizes included.  reverse_channels != 0 stores the channels in reverse order (RGB from the library's BGR).
+ * x at any float, out at any byte (16-byte / 4-byte aligned buffers with H W % 4 == 0 take the vector form). */
+int risp_quantise_u8(const float *x, uint8_t *out, int N, int C, int H, int W, int reverse_channels, void *stream);
+/* A fixed pipeline as an ISP, one launch: raw (N,H,W) uint16 RGGB frames -> out (N,H,W,3) bytes.  Per pixel:
+ * (float)sample / divisor (risp_raw_crop's expression), nearest demosaic, the bilateral of risp_bilateral_chain_fwd
+ * (x255 domain, 8-bit rounding) when max_window is 1 or 3 - window[n] clamped to [1, max_window]; max_window == 0: no
+ * bilateral stage, window / sigma_color / sigma_space are ignored - then the element-wise stages ops[k] with params[k]
+ * as in risp_bilateral_chain_fwd, in registers, and the conversion of risp_quantise_u8.  Only the result is stored; its
+ * bytes are those of risp_raw_crop -> risp_bilateral_chain_fwd (risp_chain_fwd without a bilateral) -> risp_quantise_u8.
+ * No LDS, no barrier: a thread owns a 2 x 4 pixel patch.
+ * Rules (anything else is refused before a launch): raw and out not NULL, raw 8-byte and out 4-byte aligned, whole
+ * contiguous frames; divisor > 0; max_window 0, 1 or 3; 1 <= N <= 65535, H even and >= 2, W % 4 == 0 and >= 4;
+ * 0 <= n_ops <= RISP_MAX_CHAIN, ops[k] one of SKIP, WB_MANUAL, GAMMA, GTM_MANUAL, WB_QUADRATIC, GAIN3 in any order and
+ * any number of times each (no DEMOSAIC_NEAREST: the demosaic is implied); every stage but a SKIP needs params[k]. */
+int risp_serve_u8(const uint16_t *raw, float divisor, const int32_t *window, const float *sigma_color,
+                  const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params,
+                  uint8_t *out, int reverse_channels, int N, int H, int W, void *stream);
+
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic);

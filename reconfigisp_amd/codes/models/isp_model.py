@@ -122,3 +122,8 @@ class IspModel(BaseModel):
         with torch.no_grad():
             self.output = self._forward()
         return self.output, self.netG.intermediate_results
+
+    def serve(self, raw_u16, white_level, reverse_channels=False, out=None):
+        """(N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``)."""
+        with torch.no_grad():
+            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out)

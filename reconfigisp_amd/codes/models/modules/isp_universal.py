@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import fused_forward, wants_grad
+from .pipeline_fusion import fused_forward, serve, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -43,6 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
+        self.last_serve_route = None            # 'fused' | 'composed': what the last serve() call ran
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -91,6 +92,16 @@ class _FixedPipeline(nn.Module):
             x = op(x, par)
             self.intermediate_results.append(x)
         return x
+
+    def serve(self, raw_u16, white_level, reverse_channels=False, out=None):
+        """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
+        ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
+        ``pipeline_fusion.serve_plan`` says 'fused' and the learned bilateral window allows it; ``last_serve_route`` records
+        the route taken.  ``intermediate_results`` is left as it was."""
+        with torch.no_grad():
+            pars = self._stage_params(raw_u16.size(0))
+            out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out)
+        return out
 
     @property
     def trainable_parameters(self):

@@ -78,8 +78,8 @@ def _flush(x, ops, params, results, out_last=None):
     return outs[-1]
 
 
-def _bilateral_segment(mod, par, x, from_bayer, tail_ops, tail_params):
-    """[demosaic ->] bilateral -> element-wise tail as one launch; returns the stage outputs."""
+def _bilateral_args(mod, par):
+    """(window int32, sigma_color, sigma_space, largest window) of a bilateral stage, derived once per parameter version."""
     key = (par.data_ptr(), par._version, tuple(par.shape))
     cached = mod.__dict__.get('_risp_bilateral_args')
     if cached is None or cached[0] != key:
@@ -87,7 +87,12 @@ def _bilateral_segment(mod, par, x, from_bayer, tail_ops, tail_params):
         cached = mod.__dict__['_risp_bilateral_args'] = (
             key, d['window_length'].to(torch.int32).contiguous(), d['sigma_color'].contiguous(),
             d['sigma_space'].contiguous(), int(d['window_length'].max().item()))
-    _, win, sc, ss, wmax = cached
+    return cached[1:]
+
+
+def _bilateral_segment(mod, par, x, from_bayer, tail_ops, tail_params):
+    """[demosaic ->] bilateral -> element-wise tail as one launch; returns the stage outputs."""
+    win, sc, ss, wmax = _bilateral_args(mod, par)
     return F.BilateralChainPlan(x, from_bayer, win, sc, ss, wmax, tail_ops, tail_params).launch()
 
 
@@ -142,6 +147,60 @@ def fused_forward(modules, param_tensors, x, final_out=None):
         final_out.copy_(x)
         x = results[-1] = final_out
     return x, results
+
+
+def _serve_split(modules):
+    """(index of the bilateral stage or None, indices of the chain stages) when the pipeline, Skips stripped, is
+    DemosaicNearest [-> OriginNoiseBilateral] -> at most MAX_CHAIN element-wise stages; None otherwise."""
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) is not T.DemosaicNearest:
+        return None
+    rest = idx[1:]
+    bil = None
+    if rest and type(modules[rest[0]]) is T.OriginNoiseBilateral:
+        bil, rest = rest[0], rest[1:]
+    if len(rest) > MAX_CHAIN or any(type(modules[k]) not in _CHAIN_OP for k in rest):
+        return None
+    return bil, rest
+
+
+def serve_plan(modules):
+    """What ``serve`` does with this module list (a pure function of it, no GPU needed): ``'fused'`` - one launch,
+    uint16 in and packed bytes out - when the pipeline, Skips stripped, is the nearest demosaic, an optional classical
+    bilateral and at most MAX_CHAIN WbManual / Gamma / GtmManual / WbQuadratic stages; ``'composed'`` otherwise - the
+    uint16 -> fp32 input kernel, the ordinary ``fused_forward`` and ``quantise_u8`` on the last stage.  Gray-world and
+    the conditional heads (a whole-image quantity first), CNN stages and the other classical stencils compose.  (A
+    bilateral whose learned window exceeds 3 composes too: known only from the parameters, ``serve`` checks it.)"""
+    return 'fused' if _serve_split(modules) is not None else 'composed'
+
+
+def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None):
+    """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes
+    are ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on either route."""
+    F._need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3:
+        raise ValueError('expected (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    raw_u16 = raw_u16.contiguous()
+    n, h, w = raw_u16.shape
+    split = _serve_split(modules)
+    if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+        bil, chain = split
+        # (the bilateral joins a launch under fused_forward's own conditions, so both routes run the same kernel arithmetic)
+        args = _bilateral_args(modules[bil], param_tensors[bil]) if bil is not None else None
+        if args is None or (args[3] <= 3 and min(h, w) > 8):
+            ops = [_CHAIN_OP[type(modules[k])] for k in chain]
+            params = [_chain_param(modules[k], param_tensors[k]) for k in chain]
+            return F.serve_u8(raw_u16, white_level, ops, params, args, reverse_channels, out), 'fused'
+    from ...data.gpu_input import raw_crops
+    sel = torch.zeros((n, 3), device=raw_u16.device, dtype=torch.int32)
+    sel[:, 0] = torch.arange(n, device=raw_u16.device, dtype=torch.int32)
+    x = raw_crops(raw_u16, sel, (h, w), white_level)
+    if h % 2 == 0 and w % 2 == 0:
+        x, _ = fused_forward(modules, param_tensors, x)
+    else:
+        for mod, par in zip(modules, param_tensors):
+            x = mod(x, par)
+    return F.quantise_u8(x, reverse_channels, out), 'composed'
 
 
 def wants_grad(x, raw_params):

@@ -94,6 +94,14 @@ def tensor2bgr(tensor, is_uint8=True):
     return np.array(hwc)        # C-ordered copy
 
 
+def tensor2bgr_device(tensor, reverse_channels=False):
+    """tensor2bgr's uint8 form without leaving the GPU, for the whole batch: (N,C,H,W) or (C,H,W) device tensor in
+    [0,1] -> (N,H,W,C) ``torch.uint8`` on the device (the same bytes, image by image); ``reverse_channels``: RGB."""
+    from ... import functional as F
+    t = tensor.detach()
+    return F.quantise_u8(t[None] if t.dim() == 3 else t, reverse_channels)
+
+
 def _unit_range(img):
     if img.dtype == np.uint8:
         return img.astype(np.float32) / 255.

@@ -30,10 +30,14 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _dev(t, what='tensor'):
+def _need_gpu(t, what='tensor'):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError('reconfigisp_amd: %s must be a CUDA/HIP tensor (got %s); the ops are GPU-only '
                            'and there is no CPU fallback' % (what, getattr(t, 'device', type(t))))
+
+
+def _dev(t, what='tensor'):
+    _need_gpu(t, what)
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
@@ -508,6 +512,59 @@ class BilateralChainPlan:
     def launch(self):
         L.call('risp_bilateral_chain_fwd', *self._args, _stream())
         return self.outs
+
+
+def _u8_out(out, shape, device, align):
+    """the caller's byte buffer when it fits (uint8, contiguous, on the device, ``align``-byte aligned), else a new one"""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.uint8)
+    if (out.dtype != torch.uint8 or out.device != device or tuple(out.shape) != tuple(shape) or not out.is_contiguous()
+            or out.data_ptr() % align):
+        raise ValueError('out must be a contiguous uint8 %s tensor on %s, %d-byte aligned; got %s %s'
+                         % (tuple(shape), device, align, out.dtype, tuple(out.shape)))
+    return out
+
+
+def quantise_u8(x, reverse_channels=False, out=None):
+    """``util.tensor2bgr`` on the device, batched: planar (N,C,H,W) in [0,1] -> packed (N,H,W,C) ``torch.uint8`` =
+    clip(x * 255, 0, 255) truncated.  C is 1 or 3; ``reverse_channels`` stores RGB.  One launch (``risp_quantise_u8``); with
+    ``out`` given nothing is allocated and the host does not wait."""
+    x = _dev(x, 'img')
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError('expected a (N,1|3,H,W) tensor, got %s' % (tuple(x.shape),))
+    n, c, h, w = x.shape
+    out = _u8_out(out, (n, h, w, c), x.device, 1)
+    L.call('risp_quantise_u8', _p(x), _p(out), n, c, h, w, int(bool(reverse_channels)), _stream())
+    return out
+
+
+def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=False, out=None):
+    """A fixed pipeline as an ISP in ONE launch (``risp_serve_u8``): (N,H,W) ``torch.uint16`` RGGB frames on the device ->
+    (N,H,W,3) ``torch.uint8``.  sample / divisor, nearest demosaic, the bilateral when ``bilateral = (window_i32,
+    sigma_color, sigma_space, max_window)`` is given (max_window 1 or 3), the element-wise stages ``ops`` (OP_*) with their
+    per-image blocks ``params`` (None for OP_SKIP), then ``quantise_u8``'s conversion; only the result is stored, and its
+    bytes are those of the fp32 kernels followed by ``tensor2bgr``.  H even, W % 4 == 0.  With ``out`` given nothing is
+    allocated and the host does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    n, h, w = raw_u16.shape
+    out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
+    keep = [_dev(p) if p is not None else None for p in params]
+    if bilateral is not None:
+        win, sc, ss, wmax = bilateral
+        if win.dtype != torch.int32 or not win.is_cuda:
+            raise ValueError('window must be an int32 device tensor')
+        keep += [win.contiguous(), _dev(sc), _dev(ss)]
+        bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
+    else:
+        bil = (None, None, None, 0)
+    L.call('risp_serve_u8', _p(raw_u16), float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
+           _p(out), int(bool(reverse_channels)), n, h, w, _stream())
+    return out
 
 
 class _FanOut(torch.autograd.Function):

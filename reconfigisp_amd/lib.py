@@ -181,6 +181,8 @@ SIGNATURES = {
     'risp_gt_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
     'risp_resize_rggb': (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bilateral_chain_kernel': (C.c_char_p, [_i, _i, _i]),
+    'risp_quantise_u8': (_i, [_f, _f, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_u8': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _s]),
     'risp_sse_uint8_doubles': (_z, []),
     'risp_sse_uint8': (_i, [_f, _f, _f, _z, _z, _s]),
     'risp_ssim_scratch_floats': (_z, [_i, _i, _i, _i]),
