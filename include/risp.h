@@ -699,6 +699,20 @@ int risp_bilateral_chain_fwd(const float *in, int from_bayer, float *out_demosai
  * data/oneplus_rggb2obj_dataset.py:201, data/sid_sony_ratio_rggb2bgr_dataset.py:121-134) */
 int risp_raw_crop(const uint16_t *frames, float *out, const int32_t *sel, int N, int H0, int W0, int h, int w,
                   float divisor, void *stream);
+/* Bayer phase of a sensor, by the mirror that makes its mosaic (even H and W) an RGGB one: cfa = flip_x | flip_y << 1.  The
+ * serving entry points below (risp_raw_crop_cfa, risp_serve_u8_cfa, risp_quantise_u8_flip) take it; every other entry point
+ * of the library is RGGB. */
+#define RISP_CFA_RGGB 0
+#define RISP_CFA_GRBG 1 /* mirrored along x */
+#define RISP_CFA_GBRG 2 /* mirrored along y */
+#define RISP_CFA_BGGR 3 /* mirrored along both */
+/* risp_raw_crop for a sensor with a black level and any phase: out (N,1,h,w) is the RGGB window
+ * out[n][i][j] = (float)max(s - black_level, 0) / divisor (the subtraction in integers) with
+ * s = frames[frame][row + (fy ? h-1-i : i)][col + (fx ? w-1-j : j)], fx = cfa & 1, fy = cfa >> 1.
+ * Rules: those of risp_raw_crop; cfa 0 .. 3; 0 <= black_level <= 65535; w even where fx is set and h even where fy is set
+ * (row / col even, as for every crop).  black_level 0 and cfa 0 give risp_raw_crop's values. */
+int risp_raw_crop_cfa(const uint16_t *frames, float *out, const int32_t *sel, int N, int H0, int W0, int h, int w,
+                      float divisor, int black_level, int cfa, void *stream);
 /* uint8 HWC BGR ground truth (F,H0,W0,3) -> (N,3,h,w) fp32 / 255 */
 int risp_gt_crop(const uint8_t *frames, float *out, const int32_t *sel, int N, int H0, int W0, int h, int w,
                  void *stream);
@@ -742,6 +756,12 @@ int risp_ssim_bwd(const float *x, const float *y, const float *data_range, float
  * W >= 1, odd sizes included.  reverse_channels != 0 stores the channels in reverse order (RGB from the library's BGR).
  * x at any float, out at any byte (16-byte / 4-byte aligned buffers with H W % 4 == 0 take the vector form). */
 int risp_quantise_u8(const float *x, uint8_t *out, int N, int C, int H, int W, int reverse_channels, void *stream);
+/* risp_quantise_u8 of the mirrored image: output pixel (y, x) takes input (fy ? H-1-y : y, fx ? W-1-x : x), fx = flip & 1,
+ * fy = flip >> 1 (the RISP_CFA_* bits: it puts the result of an RGGB pipeline run on a mirrored mosaic back in the sensor's
+ * orientation).  Rules: those of risp_quantise_u8 - any N, H, W >= 1, C 1 or 3 - and flip 0 .. 3; flip 0 is risp_quantise_u8.
+ * (16-byte / 4-byte aligned buffers with W % 4 == 0 take the vector form: a mirrored vector is four pixels of one row.) */
+int risp_quantise_u8_flip(const float *x, uint8_t *out, int N, int C, int H, int W, int reverse_channels, int flip,
+                          void *stream);
 /* A fixed pipeline as an ISP, one launch: raw (N,H,W) uint16 RGGB frames -> out (N,H,W,3) bytes.  Per pixel:
  * (float)sample / divisor (risp_raw_crop's expression), nearest demosaic, the bilateral of risp_bilateral_chain_fwd
  * (x255 domain, 8-bit rounding) when max_window is 1 or 3 - window[n] clamped to [1, max_window]; max_window == 0: no
@@ -756,6 +776,19 @@ int risp_quantise_u8(const float *x, uint8_t *out, int N, int C, int H, int W, i
 int risp_serve_u8(const uint16_t *raw, float divisor, const int32_t *window, const float *sigma_color,
                   const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params,
                   uint8_t *out, int reverse_channels, int N, int H, int W, void *stream);
+
+/* risp_serve_u8 for a sensor with a black level and any Bayer phase, still one launch and no other pass: raw (N,H,W) is the
+ * sensor's mosaic, out (N,H,W,3) the image in the sensor's orientation.  The input expression is
+ * (float)(s > black_level ? s - black_level : 0) / divisor, the subtraction in integers (divisor: white level - black level),
+ * and the kernel mirrors its addresses (loads at W-1-x / H-1-y, stores at the un-mirrored place) so that its arithmetic is
+ * risp_serve_u8's on the RGGB image:
+ *     out == unflip(risp_serve_u8(flip(max(raw - black_level, 0)), divisor, ...))   byte for byte,
+ * flip mirroring x where cfa & 1 and y where cfa & 2 (RISP_CFA_*).  black_level 0 and cfa 0 give risp_serve_u8's bytes.
+ * Rules: those of risp_serve_u8 (H even and W % 4 == 0 make every mirror a phase change), plus cfa 0 .. 3 and
+ * 0 <= black_level <= 65535; anything else is refused before a launch and the message names the value. */
+int risp_serve_u8_cfa(const uint16_t *raw, float divisor, const int32_t *window, const float *sigma_color,
+                      const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params,
+                      uint8_t *out, int reverse_channels, int N, int H, int W, int black_level, int cfa, void *stream);
 
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */

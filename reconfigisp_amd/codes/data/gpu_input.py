@@ -24,14 +24,27 @@ def _frames(t, dtype, ndim):
     return t.contiguous()
 
 
-def raw_crops(frames_u16, sel, size, white_level=1023.0):
-    """frames (F,H0,W0) uint16 on the GPU, sel (N,3) int32 -> (N,1,h,w) fp32 = sample / white_level."""
+def raw_crops(frames_u16, sel, size, white_level=1023.0, black_level=0, cfa='rggb'):
+    """frames (F,H0,W0) uint16 on the GPU, sel (N,3) int32 -> (N,1,h,w) fp32 = sample / white_level.
+
+    ``black_level`` / ``cfa`` (a key of ``functional.CFA``): the frames of a sensor with a pedestal and another Bayer
+    phase (``risp_raw_crop_cfa``).  The values are max(sample - black_level, 0) / (white_level - black_level), the
+    subtraction in integers, and the window (even offsets, even on every mirrored axis) is read mirrored, which makes it
+    RGGB: ``torch.flip`` of ``raw_crops`` on the clamped frames, without the passes."""
     frames = _frames(frames_u16, torch.uint16, 3)
     sel = sel.to(device=frames.device, dtype=torch.int32).contiguous()
     n = sel.shape[0]
+    code = F.cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535 or not black_level < white_level:
+        raise ValueError('black_level %r: an integer in 0 .. 65535 below the white level %r' % (black_level, white_level))
+    F._check_mirror(code, size[0], size[1])
     out = torch.empty((n, 1, size[0], size[1]), device=frames.device, dtype=torch.float32)
-    L.call('risp_raw_crop', C.c_void_p(frames.data_ptr()), F._p(out), C.c_void_p(sel.data_ptr()), n, frames.shape[1],
-           frames.shape[2], size[0], size[1], float(white_level), F._stream())
+    args = (C.c_void_p(frames.data_ptr()), F._p(out), C.c_void_p(sel.data_ptr()), n, frames.shape[1], frames.shape[2], size[0],
+            size[1], float(white_level - black_level))
+    if code or black_level:
+        L.call('risp_raw_crop_cfa', *args, int(black_level), code, F._stream())
+    else:
+        L.call('risp_raw_crop', *args, F._stream())
     return out
 
 

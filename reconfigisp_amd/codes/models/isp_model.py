@@ -123,7 +123,8 @@ class IspModel(BaseModel):
             self.output = self._forward()
         return self.output, self.netG.intermediate_results
 
-    def serve(self, raw_u16, white_level, reverse_channels=False, out=None):
-        """(N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``)."""
+    def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+        """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
+        describe the sensor)."""
         with torch.no_grad():
-            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out)
+            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa)

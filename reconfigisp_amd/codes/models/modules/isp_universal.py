@@ -93,14 +93,17 @@ class _FixedPipeline(nn.Module):
             self.intermediate_results.append(x)
         return x
 
-    def serve(self, raw_u16, white_level, reverse_channels=False, out=None):
+    def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_plan`` says 'fused' and the learned bilateral window allows it; ``last_serve_route`` records
-        the route taken.  ``intermediate_results`` is left as it was."""
+        the route taken.  ``intermediate_results`` is left as it was.  ``black_level`` and ``cfa`` ('rggb' | 'grbg' | 'gbrg'
+        | 'bggr') describe the sensor (``pipeline_fusion.serve``): the pedestal is subtracted in integers, the divisor is
+        white_level - black_level, and another phase is served by mirrored addresses, without a further pass."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
-            out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out)
+            out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
+                                                    black_level, cfa)
         return out
 
     @property

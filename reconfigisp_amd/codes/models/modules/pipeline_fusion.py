@@ -174,14 +174,26 @@ def serve_plan(modules):
     return 'fused' if _serve_split(modules) is not None else 'composed'
 
 
-def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None):
-    """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes
-    are ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on either route."""
+def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+    """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
+    ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on either route.
+
+    ``black_level`` (integer, 0 <= black_level < white_level) and ``cfa`` ('rggb' | 'grbg' | 'gbrg' | 'bggr') describe the
+    sensor: the input becomes max(raw - black_level, 0) / (white_level - black_level) and the mosaic of another phase is
+    read mirrored - which makes it RGGB for every stage, learned ones included - and the image stored un-mirrored.  No
+    extra pass on either route: the kernels mirror their addresses (``risp_serve_u8_cfa``; ``risp_raw_crop_cfa`` and
+    ``risp_quantise_u8_flip`` around the unchanged ``fused_forward``).  Byte for byte
+    ``unflip(serve(flip(clamp(raw - black_level)), white_level - black_level))``."""
     F._need_gpu(raw_u16, 'raw')
     if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3:
         raise ValueError('expected (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    code = F.cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level < white_level:
+        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
     raw_u16 = raw_u16.contiguous()
     n, h, w = raw_u16.shape
+    F._check_mirror(code, h, w)
+    divisor = white_level - black_level
     split = _serve_split(modules)
     if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         bil, chain = split
@@ -190,17 +202,17 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         if args is None or (args[3] <= 3 and min(h, w) > 8):
             ops = [_CHAIN_OP[type(modules[k])] for k in chain]
             params = [_chain_param(modules[k], param_tensors[k]) for k in chain]
-            return F.serve_u8(raw_u16, white_level, ops, params, args, reverse_channels, out), 'fused'
+            return F.serve_u8(raw_u16, divisor, ops, params, args, reverse_channels, out, black_level, cfa), 'fused'
     from ...data.gpu_input import raw_crops
     sel = torch.zeros((n, 3), device=raw_u16.device, dtype=torch.int32)
     sel[:, 0] = torch.arange(n, device=raw_u16.device, dtype=torch.int32)
-    x = raw_crops(raw_u16, sel, (h, w), white_level)
+    x = raw_crops(raw_u16, sel, (h, w), white_level, black_level, cfa)
     if h % 2 == 0 and w % 2 == 0:
         x, _ = fused_forward(modules, param_tensors, x)
     else:
         for mod, par in zip(modules, param_tensors):
             x = mod(x, par)
-    return F.quantise_u8(x, reverse_channels, out), 'composed'
+    return F.quantise_u8(x, reverse_channels, out, code), 'composed'
 
 
 def wants_grad(x, raw_params):

@@ -94,12 +94,13 @@ def tensor2bgr(tensor, is_uint8=True):
     return np.array(hwc)        # C-ordered copy
 
 
-def tensor2bgr_device(tensor, reverse_channels=False):
+def tensor2bgr_device(tensor, reverse_channels=False, flip=0):
     """tensor2bgr's uint8 form without leaving the GPU, for the whole batch: (N,C,H,W) or (C,H,W) device tensor in
-    [0,1] -> (N,H,W,C) ``torch.uint8`` on the device (the same bytes, image by image); ``reverse_channels``: RGB."""
+    [0,1] -> (N,H,W,C) ``torch.uint8`` on the device (the same bytes, image by image); ``reverse_channels``: RGB;
+    ``flip`` (bit 0: x, bit 1: y): the mirrored image, as ``functional.quantise_u8``."""
     from ... import functional as F
     t = tensor.detach()
-    return F.quantise_u8(t[None] if t.dim() == 3 else t, reverse_channels)
+    return F.quantise_u8(t[None] if t.dim() == 3 else t, reverse_channels, flip=flip)
 
 
 def _unit_range(img):

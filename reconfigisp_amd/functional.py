@@ -525,32 +525,67 @@ def _u8_out(out, shape, device, align):
     return out
 
 
-def quantise_u8(x, reverse_channels=False, out=None):
+# Bayer phase of a sensor, by the mirror that makes its mosaic an RGGB one (RISP_CFA_*): bit 0 mirrors x, bit 1 mirrors y
+CFA = {'rggb': 0, 'grbg': 1, 'gbrg': 2, 'bggr': 3}
+
+
+def cfa_code(cfa):
+    """'rggb' | 'grbg' | 'gbrg' | 'bggr' (any letter case) -> its RISP_CFA_* code"""
+    code = CFA.get(cfa.lower()) if isinstance(cfa, str) else None
+    if code is None:
+        raise ValueError('unknown cfa %r: one of %s' % (cfa, ', '.join(CFA)))
+    return code
+
+
+def _check_mirror(flip, h, w):
+    """a mirrored mosaic is RGGB only when the mirrored axis is even"""
+    if (flip & 1 and w % 2) or (flip & 2 and h % 2):
+        raise ValueError('a %d x %d mosaic mirrored along %s is not RGGB: the mirrored axis must be even'
+                         % (h, w, 'x' if flip & 1 and w % 2 else 'y'))
+
+
+def quantise_u8(x, reverse_channels=False, out=None, flip=0):
     """``util.tensor2bgr`` on the device, batched: planar (N,C,H,W) in [0,1] -> packed (N,H,W,C) ``torch.uint8`` =
-    clip(x * 255, 0, 255) truncated.  C is 1 or 3; ``reverse_channels`` stores RGB.  One launch (``risp_quantise_u8``); with
-    ``out`` given nothing is allocated and the host does not wait."""
+    clip(x * 255, 0, 255) truncated.  C is 1 or 3; ``reverse_channels`` stores RGB.  ``flip`` (bit 0: x, bit 1: y, the
+    ``CFA`` codes) stores the mirrored image: output pixel (y, x) takes input (H-1-y, W-1-x) on the set axes
+    (``risp_quantise_u8_flip``).  One launch (``risp_quantise_u8`` when ``flip`` is 0); with ``out`` given nothing is
+    allocated and the host does not wait."""
     x = _dev(x, 'img')
     if x.dim() != 4 or x.shape[1] not in (1, 3):
         raise ValueError('expected a (N,1|3,H,W) tensor, got %s' % (tuple(x.shape),))
+    if flip not in (0, 1, 2, 3):
+        raise ValueError('flip %r: 0 .. 3 (bit 0 mirrors x, bit 1 mirrors y)' % (flip,))
     n, c, h, w = x.shape
     out = _u8_out(out, (n, h, w, c), x.device, 1)
-    L.call('risp_quantise_u8', _p(x), _p(out), n, c, h, w, int(bool(reverse_channels)), _stream())
+    if flip:
+        L.call('risp_quantise_u8_flip', _p(x), _p(out), n, c, h, w, int(bool(reverse_channels)), flip, _stream())
+    else:
+        L.call('risp_quantise_u8', _p(x), _p(out), n, c, h, w, int(bool(reverse_channels)), _stream())
     return out
 
 
-def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=False, out=None):
+def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
     """A fixed pipeline as an ISP in ONE launch (``risp_serve_u8``): (N,H,W) ``torch.uint16`` RGGB frames on the device ->
     (N,H,W,3) ``torch.uint8``.  sample / divisor, nearest demosaic, the bilateral when ``bilateral = (window_i32,
     sigma_color, sigma_space, max_window)`` is given (max_window 1 or 3), the element-wise stages ``ops`` (OP_*) with their
     per-image blocks ``params`` (None for OP_SKIP), then ``quantise_u8``'s conversion; only the result is stored, and its
     bytes are those of the fp32 kernels followed by ``tensor2bgr``.  H even, W % 4 == 0.  With ``out`` given nothing is
-    allocated and the host does not wait."""
+    allocated and the host does not wait.
+
+    ``black_level`` (an integer, 0 .. 65535) and ``cfa`` (a key of ``CFA``) describe a real sensor: the input expression
+    becomes max(sample - black_level, 0) / divisor, the subtraction in integers (``divisor`` is then white level - black
+    level), and a GRBG / GBRG / BGGR mosaic is read mirrored and its image stored un-mirrored - still one launch
+    (``risp_serve_u8_cfa``) and byte for byte ``flip(serve_u8(flip(clamp(raw - black_level)), divisor, ...))``."""
     _need_gpu(raw_u16, 'raw')
     if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
         raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
     if len(ops) != len(params):
         raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
     n, h, w = raw_u16.shape
+    _check_mirror(code, h, w)
     out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
     keep = [_dev(p) if p is not None else None for p in params]
     if bilateral is not None:
@@ -561,9 +596,13 @@ def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=Fal
         bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
     else:
         bil = (None, None, None, 0)
-    L.call('risp_serve_u8', _p(raw_u16), float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
-           _p(out), int(bool(reverse_channels)), n, h, w, _stream())
+    args = (_p(raw_u16), float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+            L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
+            _p(out), int(bool(reverse_channels)), n, h, w)
+    if code or black_level:
+        L.call('risp_serve_u8_cfa', *args, int(black_level), code, _stream())
+    else:
+        L.call('risp_serve_u8', *args, _stream())
     return out
 
 

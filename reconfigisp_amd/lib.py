@@ -178,11 +178,14 @@ SIGNATURES = {
     'risp_dmnet_head_bwd': (_i, [_f] * 9 + [_i, _i, _i, _s]),
     'risp_bilateral_chain_fwd': (_i, [_f, _i, _f, _f, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _pp, _i, _i, _i, _s]),
     'risp_raw_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _fl, _s]),
+    'risp_raw_crop_cfa': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _fl, _i, _i, _s]),
     'risp_gt_crop': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
     'risp_resize_rggb': (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bilateral_chain_kernel': (C.c_char_p, [_i, _i, _i]),
     'risp_quantise_u8': (_i, [_f, _f, _i, _i, _i, _i, _i, _s]),
     'risp_serve_u8': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _s]),
+    'risp_quantise_u8_flip': (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_u8_cfa': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_sse_uint8_doubles': (_z, []),
     'risp_sse_uint8': (_i, [_f, _f, _f, _z, _z, _s]),
     'risp_ssim_scratch_floats': (_z, [_i, _i, _i, _i]),
