@@ -457,8 +457,9 @@ __global__ __launch_bounds__(256) void slot_mix_finish_kernel(const risp_slot_mi
 }
 
 int check_slot(const risp_slot_mix_desc *d, const char *who, bool &wbq, bool &pointwise) {
-    RISP_CHECK_ARG(d && d->K >= 1 && d->K <= RISP_MAX_MIX && d->N >= 1 && d->N <= 65535 && d->HW > 0 && d->HW % 4 == 0,
-                   "%s: bad descriptor", who);
+    RISP_CHECK_ARG(d, "%s: null descriptor", who);
+    RISP_CHECK_ARG(d->K >= 1 && d->K <= RISP_MAX_MIX && d->N >= 1 && d->N <= 65535 && d->HW > 0 && d->HW % 4 == 0,
+                   "%s: bad descriptor (K=%d of 1..%d operands, N=%d, HW=%d: a positive multiple of 4)", who, d->K, RISP_MAX_MIX, d->N, d->HW);
     int seen = 0;
     wbq = pointwise = false;
     for (int k = 0; k < d->K; ++k) {
