@@ -358,8 +358,9 @@ int risp_conv2d_toep_sums(const risp_conv_desc *d, float *psum, void *stream);
  * cin][kx][part: hi, lo][channel half][row m, 32][8 channels] _Float16 with row m = 4 ky + co (ky < 8) or 4 co + 3 (ky = 8)
  * (reconfigisp_amd/convnets.py::tapout_weights).  ksize 5 or 9, cout <= 3, cin % 16 == 0, W % 4 == 0, H * W < 2^24, cin * H * W < 2^30;
  * load_mode PLAIN; epilogue RELU | ADD (add_c <= cout) | NOBIAS; grouped launches.  seg_rows: rows of a work item's segment - 0 = chosen by the launch to fill
- * the chip (training launches), else a multiple of 4 fixed by the caller: an image's result then does not depend on the batch it
- * travels in (the scales follow the segment's row phase). */
+ * the chip (training launches), else fixed by the caller - a multiple of 4 (the scales follow the segment's row phase), or any value of at
+ * least H (the image kept whole: what risp_conv_tapout_seg_rows returns for a launch it does not cut, whatever H % 4): an image's result
+ * then does not depend on the batch it travels in. */
 size_t risp_conv_tapout_wpack_bytes(int cin, int ksize);
 int risp_conv_tapout_seg_rows(int N, int H, int W);          /* what seg_rows = 0 chooses for a launch of N images (a pure function) */
 int risp_conv2d_tapout(const risp_conv_desc *d, int seg_rows, void *stream);

@@ -433,17 +433,6 @@ def toep_grid_ok(images, h, w):
     return images * tiles >= TOEP_MIN_TILES
 
 
-def _tapout_ok(sc, h, w, epi=0):
-    return (CONV_ARITH == 'f16x2' and small_has_tapout(sc.k, sc.cin, sc.cout) and not (epi & EPI_SHUFFLE2) and w % 4 == 0
-            and sc.cin * h * w < (1 << 30) and h * w < (1 << 24))
-
-
-def _toep_ok(sc, h, w):
-    # (any width: planes of at most 128 pixels run with two rows folded into the 32 columns of the matrix instruction; the 12-cout
-    # form cannot fold and is ~20 % slower than the vector kernel there, but a layer keeps ONE arithmetic whatever the crop it sees)
-    return CONV_ARITH == 'f16x2' and small_has_toep(sc.k, sc.cout) and w % 4 == 0 and sc.cin * h * w < (1 << 30)
-
-
 # risp_conv2d_toep_first (9x9 first layers on the f16 matrix pipe): 'train' (default) = inference AND training forwards, the latter with
 # EXACT ReLU decisions (risp_conv2d_toep_first_exact: outputs whose pre-activation is within the arithmetic's own error of zero are
 # recomputed in double) - one first-layer kernel for model.test() and the training forward; 'infer' = inference launches only, training
@@ -473,6 +462,7 @@ def _tie_list(device):
 TOEP_MIN_TILES = 256                        # training launches: tiles below which the vector-FMA kernel with its channel split serves
 TAPOUT_MIN_ITEMS = 128                      # ... and work items (image, 128-column strip, 32-row segment) below which it serves instead of risp_conv2d_tapout
 TAPOUT_INFER_SEG = 64                       # rows of a work item's segment in inference launches (fixed: a result must not depend on the batch)
+SPLIT_BAND = -1                             # ``split`` of a per-member launch: the band kernel although the layer holds a tap-row pack (``small_group_split``)
 
 
 def tapout_grid_ok(images, h, w):
@@ -482,8 +472,35 @@ def tapout_grid_ok(images, h, w):
 
 def tapout_seg(images, h, w, infer):
     """rows of a work item's segment: fixed for inference, chosen by the grid of ALL the images of a (grouped) launch for training -
-    the per-member form of a grouped launch passes the grouped launch's value, so that both cut the planes alike (same bits)"""
-    return min(TAPOUT_INFER_SEG, h) if infer else L.load().risp_conv_tapout_seg_rows(images, h, w)
+    the per-member form of a grouped launch passes the grouped launch's value, so that both cut the planes alike (same bits)
+    (a height of at least H keeps the image whole, whatever H % 4: the library clamps it)"""
+    return TAPOUT_INFER_SEG if infer else L.load().risp_conv_tapout_seg_rows(images, h, w)
+
+
+def narrow3_addressable(cin, h, w):
+    """``risp_conv2d_narrow3`` reads an image through a buffer resource of 2^31 - 1 bytes (its entry point checks the same bound): a
+    64-channel tail on an untiled 3000 x 4000 frame is past it and stays on the vector kernel with its 64-bit addresses"""
+    return cin * h * w * 4 < (1 << 31)
+
+
+def small_packs(k, cin, cout, epi=0, has_add=False):
+    """(has_toep, has_tapout, has_narrow3) of ``route_small``: the matrix-pipe packs a ``SmallConv`` holds AND whose kernel has this
+    launch's epilogue (the band kernel has every epilogue of the layers that hold its pack; a mask is ``route_small``'s own rule)"""
+    return (small_has_toep(k, cout), small_has_tapout(k, cin, cout) and not (epi & EPI_SHUFFLE2),
+            small_has_narrow3(k, cin, cout) and not (epi & ~(EPI_RELU | EPI_SHUFFLE2 | EPI_NOBIAS)) and not has_add)
+
+
+def small_chain_groups(k, cin, images):
+    """Channel groups of a vector-kernel launch that its grid does not split: ``risp_conv2d_small`` adds every product of an output into
+    ONE fp32 accumulator, and on a 9x9 layer with 64 input channels that chain is 5184 products long - max error 2.2e-6 .. 3.4e-6 of the
+    output's magnitude against 0.9e-6 .. 1.2e-6 on the 5x5 32-channel layers (800 products) its 3e-6 bar was set on.  9x9 layers with 32
+    channels or more therefore always run as ``risp_conv2d_small_split`` with one group per 16 channels (at most 8): chains of 1296
+    products, added in index order (4e-7 .. 9e-7).  A function of the layer alone, never of the grid, so an inference result still does
+    not depend on the batch (the images of a launch only matter at the entry point's limit of 65535 groups x images).  Under the
+    default arithmetic these layers run on the matrix pipe; this is their route under RISP_CONV_ARITH=f32, with a mask, with
+    W % 4 != 0 and past the matrix kernels' size bounds."""
+    g = min(8, cin // 16) if k == 9 and cin >= 32 else 1
+    return g if images * g <= 65535 else 1
 
 
 def route_small(k, cin, cout, h, w, images, infer=False, has_mask=False, has_toep=True, split=None, has_tapout=False, has_narrow3=False):
@@ -491,18 +508,21 @@ def route_small(k, cin, cout, h, w, images, infer=False, has_mask=False, has_toe
     layers that hold a tap-row pack (at most 3 couts, cin % 16 == 0, 5 or 9 taps) run on risp_conv2d_tapout, the other 5- and 9-tap
     layers that hold a Toeplitz-band pack (4 couts, or 5 .. 12 with 5 taps, or odd channel counts) on risp_conv2d_toep (both: f16 matrix
     pipe, split precision) - ALWAYS for inference (a tile's result must not depend on the batch it travels in), for training when the
-    grid holds enough work (TAPOUT_MIN_ITEMS / TOEP_MIN_TILES; or the caller forces ``split`` = 0: the per-member form of a grouped
-    launch follows the grouped grid); everything else on risp_conv2d_small (vector FMAs; small training grids split their input
-    channels over several workgroups per tile: risp_conv2d_small_split, never for inference).  3x3 layers that hold a (filter row,
+    grid holds enough work (TAPOUT_MIN_ITEMS / TOEP_MIN_TILES; or the caller forces ``split`` = 0, or SPLIT_BAND for the band kernel
+    where the layer holds both packs: the per-member form of a grouped launch follows the grouped grid, ``small_group_split``);
+    everything else on risp_conv2d_small (vector FMAs; small training grids split their input
+    channels over several workgroups per tile: risp_conv2d_small_split - by the grid never for inference; 9x9 layers with 32 channels
+    or more always, by ``small_chain_groups``).  3x3 layers that hold a (filter row,
     cout) pack (at most 4 couts, 16 .. 64 input channels; ``has_narrow3``: the caller also checks the epilogue) run on
-    risp_conv2d_narrow3 in inference launches, whatever the grid."""
+    risp_conv2d_narrow3 in inference launches, whatever the grid, while the image is within that kernel's buffers
+    (``narrow3_addressable``)."""
     mat = CONV_ARITH == 'f16x2' and w % 4 == 0 and cin * h * w < (1 << 30) and not has_mask
-    if mat and has_narrow3 and infer:                 # 3x3 tails (at most 4 couts) of inference launches: one scale per wave and row - any grid,
+    if mat and has_narrow3 and infer and narrow3_addressable(cin, h, w):   # 3x3 tails (at most 4 couts) of inference launches: one scale per wave and row - any grid,
         return 'risp_conv2d_narrow3'                  # any batch.  (Training keeps the vector kernel: equal at batch 32 - both read 64 planes at
         #                                               2.6 TB/s - and the search step's goldens keep their arithmetic.)
     if mat and has_tapout and h * w < (1 << 24) and (infer or (split == 0 if split is not None else tapout_grid_ok(images, h, w))):
         return 'risp_conv2d_tapout'
-    if mat and has_toep and (infer or (split == 0 if split is not None else toep_grid_ok(images, h, w))):
+    if mat and has_toep and (infer or (split <= 0 if split is not None else toep_grid_ok(images, h, w))):
         return 'risp_conv2d_toep'
     return 'risp_conv2d_small'
 
@@ -510,9 +530,9 @@ def route_small(k, cin, cout, h, w, images, infer=False, has_mask=False, has_toe
 def conv_small(x, sc, n, h, w, epi=0, add=None, add_c=0, mask=None, infer=False, out=None, group=None, split=None, tile_sums=None,
                seg_rows=None):
     """One launch of a layer with at most 12 output channels (``route_small``).  ``infer``: never split the input channels over
-    workgroups - the split depends on the grid, and an inference result must not depend on the batch a tile travels in
-    (test_split.py batches tiles).  ``group``: see ``_group_fields``; ``split``: force the channel split (the per-member form of a
-    grouped launch uses the split the grouped grid would take; 0 = the matrix-pipe kernel) and ``seg_rows`` the segment height of
+    workgroups by the grid - that split depends on the batch, and an inference result must not depend on the batch a tile travels in
+    (test_split.py batches tiles); the fixed split of long chains, ``small_chain_groups``, depends on the layer alone.  ``group``: see ``_group_fields``; ``split``: force the channel split (the per-member form of a
+    grouped launch uses the split the grouped grid would take; 0 / SPLIT_BAND = a matrix-pipe kernel) and ``seg_rows`` the segment height of
     risp_conv2d_tapout (``tapout_seg`` of the grouped launch).  ``tile_sums``: a list that receives the per-tile sums of the input
     planes when a matrix-pipe kernel serves the launch (see ``rect_sums``)."""
     if sc.bias is None:
@@ -524,9 +544,7 @@ def conv_small(x, sc, n, h, w, epi=0, add=None, add_c=0, mask=None, infer=False,
     d = L.ConvDesc(N=n, H=h, W=w, cin=sc.cin, cout=sc.cout, ksize=sc.k, load_mode=LOAD_PLAIN, cin_img=0, epilogue=epi,
                    add_c=add_c, x=_p(x), wpack=_p(sc.wpack), bias=_p(sc.bias), cvals=None, add=_p(add), mask=_p(mask),
                    y=_p(out))
-    has_toep = small_has_toep(sc.k, sc.cout)          # (the packs themselves are built when a launch first asks for them)
-    has_tapout = small_has_tapout(sc.k, sc.cin, sc.cout) and not (epi & EPI_SHUFFLE2)
-    has_narrow3 = small_has_narrow3(sc.k, sc.cin, sc.cout) and not (epi & ~(EPI_RELU | EPI_SHUFFLE2 | EPI_NOBIAS)) and add is None
+    has_toep, has_tapout, has_narrow3 = small_packs(sc.k, sc.cin, sc.cout, epi, add is not None)   # (built when a launch first asks for them)
     entry = route_small(sc.k, sc.cin, sc.cout, h, w, nn_, infer, mask is not None, has_toep, split, has_tapout, has_narrow3)
     if entry == 'risp_conv2d_narrow3':
         pack = sc.narrow3
@@ -567,6 +585,8 @@ def conv_small(x, sc, n, h, w, epi=0, add=None, add_c=0, mask=None, infer=False,
         return out
     _group_fields(d, n, group, sc.wpack, sc.bias)
     groups = 1 if infer else (split if split is not None else L.load().risp_conv_small_groups(C.byref(d)))
+    if groups <= 1:                                 # no split by the grid: long reduction chains are still cut (fixed by the layer alone)
+        groups = small_chain_groups(sc.k, sc.cin, nn_)
     if groups > 1:                                  # small grid: split the input channels over several workgroups per tile
         scratch = torch.empty((groups,) + tuple(out.shape), device=x.device, dtype=torch.float32)
         L.call('risp_conv2d_small_split', C.byref(d), _p(scratch), groups, _stream())
@@ -1247,14 +1267,25 @@ class _SrcnnResGroupFn(torch.autograd.Function):
         return (gx, None, None, None) + gpvs
 
 
+def small_group_split(k, cin, cout, h, w, n_total, epi=0, has_add=False, has_mask=False):
+    """What the per-member form of a grouped training launch of ``n_total`` images passes as ``split`` when the grouped launch runs on a
+    matrix-pipe kernel: 0 = the first such kernel the layer holds a pack for, SPLIT_BAND = risp_conv2d_toep for a layer that also holds
+    a tap-row pack (its grid has too few work items for risp_conv2d_tapout and tiles enough for the band kernel); None = the vector
+    kernel, whose channel split the library chooses.  ``route_small``'s own answer, with ``small_packs`` as ``conv_small`` passes them,
+    so that the two cannot drift (a pure function: tests/test_conv_small_reference_cpu.py holds it next to ``route_small``)."""
+    has_toep, has_tapout, has_narrow3 = small_packs(k, cin, cout, epi, has_add)
+    entry = route_small(k, cin, cout, h, w, n_total, False, has_mask, has_toep, None, has_tapout, has_narrow3)
+    if entry == 'risp_conv2d_small':
+        return None
+    return SPLIT_BAND if entry == 'risp_conv2d_toep' and has_tapout else 0
+
+
 def _small_split(x, sc, n_total, h, w, epi, add_c):
-    """the channel split ``conv_small`` would take for the grouped launch (so that the per-member form uses the same); 0 = the
-    grouped launch runs on ``risp_conv2d_toep``"""
-    if _tapout_ok(sc, h, w, epi):
-        if tapout_grid_ok(n_total, h, w):
-            return 0
-    elif _toep_ok(sc, h, w) and toep_grid_ok(n_total, h, w):
-        return 0
+    """the channel split ``conv_small`` would take for the grouped launch (so that the per-member form uses the same); 0 / SPLIT_BAND =
+    the grouped launch runs on a matrix-pipe kernel (``small_group_split``)"""
+    code = small_group_split(sc.k, sc.cin, sc.cout, h, w, n_total, epi, bool(epi & EPI_ADD))
+    if code is not None:
+        return code
     d = L.ConvDesc(N=n_total, H=h, W=w, cin=sc.cin, cout=sc.cout, ksize=sc.k, load_mode=LOAD_PLAIN, cin_img=0, epilogue=epi,
                    add_c=add_c, x=_p(x), wpack=_p(sc.wpack), bias=None, cvals=None, add=None, mask=None, y=None)
     return L.load().risp_conv_small_groups(C.byref(d))

@@ -518,8 +518,9 @@ __global__ __launch_bounds__(512, 2) void conv_tapout_kernel(const risp_conv_des
 }
 
 // rows of a segment: the whole image when there are work items enough for the chip without cutting it (every cut costs 2 P halo rows of
-// staging and products), else segments of at least 32 rows - or what the caller fixes (a multiple of 4: inference launches, where a
-// result must not depend on the batch it travels in - the per-tile scales follow the segment's row phase)
+// staging and products), else segments of at least 32 rows - or what the caller fixes (inference launches, where a result must not
+// depend on the batch it travels in): a multiple of 4, since the per-tile scales follow the segment's row phase - or any height of at
+// least H, which keeps the image whole (one segment from row 0, what seg_rows = 0 gives a launch with images enough, for any H)
 int tapout_seg_rows(int N, int H, int W, int seg_rows) {
     if (seg_rows > 0) return seg_rows >= H ? H : seg_rows;
     const int strips = (W + TO_TW - 1) / TO_TW, slots = h2_cu_count();
@@ -576,7 +577,8 @@ static int conv2d_tapout_impl(const risp_conv_desc *dp, int seg_rows, float *psu
                    "risp_conv2d_tapout: needs a 5x5 or 9x9 layer with cout <= 3, cin %% 16 == 0, W %% 4 == 0, fewer than 2^30 input elements and 2^24 "
                    "pixels per image (N=%d H=%d W=%d cin=%d cout=%d k=%d)",
                    d.N, d.H, d.W, d.cin, d.cout, d.ksize);
-    RISP_CHECK_ARG(seg_rows >= 0 && seg_rows % 4 == 0, "risp_conv2d_tapout: seg_rows must be 0 (chosen by the launch) or a multiple of 4");
+    RISP_CHECK_ARG(seg_rows >= 0 && (seg_rows % 4 == 0 || seg_rows >= d.H),
+                   "risp_conv2d_tapout: seg_rows must be 0 (chosen by the launch), a multiple of 4, or at least H (the image kept whole)");
     RISP_CHECK_ARG(d.load_mode == RISP_LOAD_PLAIN, "risp_conv2d_tapout: only plain loads");
     RISP_CHECK_ARG(!(d.epilogue & ~(RISP_EPI_RELU | RISP_EPI_ADD | RISP_EPI_NOBIAS)), "risp_conv2d_tapout: epilogue %d not supported", d.epilogue);
     RISP_CHECK_ARG((d.epilogue & RISP_EPI_NOBIAS) || d.bias, "risp_conv2d_tapout: bias missing");

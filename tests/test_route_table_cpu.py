@@ -126,3 +126,17 @@ def test_first_layer_switch_and_addressing(monkeypatch):
     assert CN.route(3, 64, 64, 512, 512, have=CN.pack_kinds(3, 64, 64)) == 'risp_conv2d_f16x2'
     # a residual narrower than the layer (SRCNNRes' 3-channel skip) is not the split-precision kernel's epilogue
     assert CN.route(5, 64, 32, H, W, epi=A, add_c=3, have=CN.pack_kinds(5, 64, 32)) == 'risp_conv2d_wino45'
+
+
+def test_narrow3_route_stays_within_the_kernel_s_buffers(monkeypatch):
+    """risp_conv2d_narrow3 reads an image through a buffer resource of 2^31 - 1 bytes (its entry point refuses cin * H * W * 4 >= 2^31): a
+    64-channel 3x3 tail on an untiled 3000 x 4000 frame stays on the vector kernel, the search's patch keeps the matrix pipe"""
+    monkeypatch.setattr(CN, 'CONV_ARITH', 'f16x2')
+    tail = lambda cin, cout, h, w: CN.route_small(3, cin, cout, h, w, 1, True, False, CN.small_has_toep(3, cout), None,
+                                                  CN.small_has_tapout(3, cin, cout), CN.small_has_narrow3(3, cin, cout))
+    for cout in (3, 4):
+        assert tail(64, cout, 3000, 4000) == 'risp_conv2d_small'
+        assert tail(64, cout, 256, 256) == 'risp_conv2d_narrow3'
+    assert tail(64, 3, 2048, 4096) == 'risp_conv2d_small' and tail(64, 3, 2047, 4096) == 'risp_conv2d_narrow3'      # 2^31 bytes exactly / just below
+    assert tail(32, 3, 4000, 6000) == 'risp_conv2d_small' and tail(16, 3, 4000, 6000) == 'risp_conv2d_narrow3'
+    assert CN.narrow3_addressable(64, 256, 256) and not CN.narrow3_addressable(64, 3000, 4000)
