@@ -130,7 +130,11 @@ enum {
     RISP_OP_GAMMA = 3,
     RISP_OP_GTM_MANUAL = 4,
     RISP_OP_WB_QUADRATIC = 5,
-    RISP_OP_GAIN3 = 6 /* y_c = clamp(x_c * p[n,c]): gray-world apply with precomputed gains */
+    RISP_OP_GAIN3 = 6, /* y_c = clamp(x_c * p[n,c]): gray-world apply with precomputed gains */
+    /* the two classical tone curves that need no whole-image quantity: stages of risp_serve_classical_u8 ONLY (every other
+     * entry point refuses codes above RISP_OP_GAIN3) */
+    RISP_OP_TONE_CRYSIS = 7, /* params (N,1): lum_adapted */
+    RISP_OP_TONE_FILMIC = 8  /* params (N,2): white_point, exposure_bias (already scaled to 1 .. 10) */
 };
 #define RISP_MAX_CHAIN 8
 int risp_chain_fwd(const float *in, int n_ops, const int *ops, const float *const *params,
@@ -790,6 +794,28 @@ int risp_serve_u8(const uint16_t *raw, float divisor, const int32_t *window, con
 int risp_serve_u8_cfa(const uint16_t *raw, float divisor, const int32_t *window, const float *sigma_color,
                       const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params,
                       uint8_t *out, int reverse_channels, int N, int H, int W, int black_level, int cfa, void *stream);
+
+/* A classical pipeline as an ISP, one launch (risp_serve_classical.hip): raw (N,H,W) uint16 mosaic of the sensor -> out
+ * (N,H,W,3) bytes.  Per pixel: (float)max(s - black_level, 0) / divisor (risp_raw_crop_cfa's expression), the demosaic, the
+ * stages ops[k] in registers, the conversion of risp_quantise_u8.  Only the result is stored; its bytes are those of
+ * risp_raw_crop_cfa -> risp_chain_fwd with DEMOSAIC_NEAREST | risp_origin_demosaic(in_scale 255, out_div 255) -> per stage
+ * risp_chain_fwd | risp_origin_tonemap(in_scale 255, out_div 255) -> risp_quantise_u8_flip.
+ * demosaic: RISP_DEMOSAIC_NEAREST (the sample as it is), BILINEAR or LAPLACIAN (Malvar-He-Cutler): risp_origin_demosaic's
+ * expressions on sample x 255, reflect-101 borders over radius 2, the result rounded to its 8-bit code / 255.
+ * ops[k]: SKIP, WB_MANUAL, GAMMA, GTM_MANUAL, WB_QUADRATIC, GAIN3 as in risp_serve_u8, or RISP_OP_TONE_CRYSIS (params (N,1):
+ * lum_adapted) / RISP_OP_TONE_FILMIC (params (N,2): white_point, exposure_bias in 1 .. 10): risp_origin_tonemap's curves and
+ * 8-bit rounding, their per-image constants formed in the kernel (no prepare launch).  No bilateral here.
+ * black_level and cfa as in risp_serve_u8_cfa: the phase is a mirror of addresses, the arithmetic is that of the RGGB image.
+ * No LDS, no barrier: a thread owns a 2 x 4 pixel patch and loads its 6 x 8 mosaic neighbourhood itself.
+ * Rules (anything else is refused before a launch): raw and out not NULL, raw 8-byte and out 4-byte aligned, whole
+ * contiguous frames; divisor > 0; demosaic 0 .. 2; 1 <= N <= 65535, H even and >= 4, W % 4 == 0 and >= 4;
+ * 0 <= n_ops <= RISP_MAX_CHAIN, every stage but a SKIP needs params[k]; cfa 0 .. 3; 0 <= black_level <= 65535. */
+#define RISP_DEMOSAIC_NEAREST 0
+#define RISP_DEMOSAIC_BILINEAR 1
+#define RISP_DEMOSAIC_LAPLACIAN 2
+int risp_serve_classical_u8(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                            const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
+                            int black_level, int cfa, void *stream);
 
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */

@@ -43,7 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
-        self.last_serve_route = None            # 'fused' | 'composed': what the last serve() call ran
+        self.last_serve_route = None            # 'fused' | 'classical' | 'composed': what the last serve() call ran
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -96,8 +96,9 @@ class _FixedPipeline(nn.Module):
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
-        ``pipeline_fusion.serve_plan`` says 'fused' and the learned bilateral window allows it; ``last_serve_route`` records
-        the route taken.  ``intermediate_results`` is left as it was.  ``black_level`` and ``cfa`` ('rggb' | 'grbg' | 'gbrg'
+        ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
+        bilinear / Malvar-He-Cutler demosaic, Crysis / Filmic tone curves), otherwise composed from the existing kernels;
+        ``last_serve_route`` records the route taken.  ``intermediate_results`` is left as it was.  ``black_level`` and ``cfa`` ('rggb' | 'grbg' | 'gbrg'
         | 'bggr') describe the sensor (``pipeline_fusion.serve``): the pedestal is subtracted in integers, the divisor is
         white_level - black_level, and another phase is served by mirrored addresses, without a further pass."""
         with torch.no_grad():

@@ -170,13 +170,60 @@ def serve_plan(modules):
     bilateral and at most MAX_CHAIN WbManual / Gamma / GtmManual / WbQuadratic stages; ``'composed'`` otherwise - the
     uint16 -> fp32 input kernel, the ordinary ``fused_forward`` and ``quantise_u8`` on the last stage.  Gray-world and
     the conditional heads (a whole-image quantity first), CNN stages and the other classical stencils compose.  (A
-    bilateral whose learned window exceeds 3 composes too: known only from the parameters, ``serve`` checks it.)"""
+    bilateral whose learned window exceeds 3 composes too: known only from the parameters, ``serve`` checks it.)
+    ``'composed'`` here reads "not ``risp_serve_u8``": ``serve_route`` tells the classical one launch from the rest."""
     return 'fused' if _serve_split(modules) is not None else 'composed'
+
+
+_CLASSICAL_DEMOSAIC = {T.DemosaicNearest: 'nearest', T.OriginDemosBilinear: 'bilinear', T.OriginDemosLaplacian: 'laplacian'}
+_TONE_OP = {T.OriginToneCrysis: F.OP_TONE_CRYSIS, T.OriginToneFilmic: F.OP_TONE_FILMIC}
+
+
+def _classical_split(modules):
+    """(demosaic kind, indices of the stages) when the pipeline, Skips stripped, is DemosaicNearest / OriginDemosBilinear /
+    OriginDemosLaplacian -> at most MAX_CHAIN stages, each an element-wise one, OriginToneCrysis or OriginToneFilmic; None
+    otherwise."""
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+        return None
+    rest = idx[1:]
+    if len(rest) > MAX_CHAIN or any(type(modules[k]) not in _CHAIN_OP and type(modules[k]) not in _TONE_OP for k in rest):
+        return None
+    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], rest
+
+
+def serve_route(modules):
+    """The route ``serve`` takes for this module list (a pure function of it): ``'fused'`` exactly where ``serve_plan``
+    says so (``risp_serve_u8``); ``'classical'`` - still one launch, ``risp_serve_classical_u8`` - when the pipeline, Skips
+    stripped, is the nearest, the classical bilinear or the classical Malvar-He-Cutler demosaic followed by at most
+    MAX_CHAIN stages, each WbManual / Gamma / GtmManual / WbQuadratic or a classical Crysis / Filmic tone curve;
+    ``'composed'`` otherwise.  A bilateral behind a stencil demosaic, Reinhard, white-world and gray-world (a whole-image
+    quantity first), median / NLM / BM3D and every CNN stage compose."""
+    if _serve_split(modules) is not None:
+        return 'fused'
+    return 'classical' if _classical_split(modules) is not None else 'composed'
+
+
+def _tone_block(mod, par):
+    """the parameter block ``risp_serve_classical_u8`` takes for a tone curve - what ``_origin_call`` hands to
+    ``F.origin_tonemap`` - derived once per parameter version"""
+    key = (par.data_ptr(), par._version, tuple(par.shape))
+    cached = mod.__dict__.get('_risp_tone_block')
+    if cached is None or cached[0] != key:
+        p = par.detach()
+        if type(mod) is T.OriginToneCrysis:
+            block = p[:, :1].float().contiguous()
+        else:
+            block = torch.stack([p[:, 0], p[:, 1] * 9. + 1.], dim=1).float().contiguous()
+        cached = mod.__dict__['_risp_tone_block'] = (key, block, par)      # (par kept: its address stays its own while the key lives)
+    return cached[1]
 
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
-    ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on either route.
+    ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
+    (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
+    and >= 4, W % 4 == 0) or ``'composed'``.
 
     ``black_level`` (integer, 0 <= black_level < white_level) and ``cfa`` ('rggb' | 'grbg' | 'gbrg' | 'bggr') describe the
     sensor: the input becomes max(raw - black_level, 0) / (white_level - black_level) and the mosaic of another phase is
@@ -203,6 +250,13 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
             ops = [_CHAIN_OP[type(modules[k])] for k in chain]
             params = [_chain_param(modules[k], param_tensors[k]) for k in chain]
             return F.serve_u8(raw_u16, divisor, ops, params, args, reverse_channels, out, black_level, cfa), 'fused'
+    if (serve_route(modules) == 'classical' and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535
+            and raw_u16.data_ptr() % 8 == 0):
+        kind, stages = _classical_split(modules)
+        ops = [_TONE_OP.get(type(modules[k])) or _CHAIN_OP[type(modules[k])] for k in stages]
+        params = [_tone_block(modules[k], param_tensors[k]) if type(modules[k]) in _TONE_OP
+                  else _chain_param(modules[k], param_tensors[k]) for k in stages]
+        return F.serve_classical_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa), 'classical'
     from ...data.gpu_input import raw_crops
     sel = torch.zeros((n, 3), device=raw_u16.device, dtype=torch.int32)
     sel[:, 0] = torch.arange(n, device=raw_u16.device, dtype=torch.int32)

@@ -17,6 +17,7 @@ import torch
 from . import lib as L
 
 OP_SKIP, OP_DEMOSAIC_NEAREST, OP_WB_MANUAL, OP_GAMMA, OP_GTM_MANUAL, OP_WB_QUADRATIC, OP_GAIN3 = range(7)
+OP_TONE_CRYSIS, OP_TONE_FILMIC = 7, 8      # stages of serve_classical_u8 only: every other entry point refuses them
 
 
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
@@ -603,6 +604,40 @@ def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=Fal
         L.call('risp_serve_u8_cfa', *args, int(black_level), code, _stream())
     else:
         L.call('risp_serve_u8', *args, _stream())
+    return out
+
+
+DEMOSAIC = {'nearest': 0, 'bilinear': 1, 'laplacian': 2}      # RISP_DEMOSAIC_*
+
+
+def serve_classical_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+    """A classical pipeline as an ISP in ONE launch (``risp_serve_classical_u8``): (N,H,W) ``torch.uint16`` frames on the
+    device -> (N,H,W,3) ``torch.uint8``.  max(sample - black_level, 0) / divisor, the demosaic (a key of ``DEMOSAIC``:
+    nearest, or the classical bilinear / Malvar-He-Cutler ``origin_demosaic`` with its 8-bit rounding), the stages ``ops``
+    with their per-image blocks ``params`` (None for OP_SKIP) - the element-wise OP_* of ``serve_u8`` and the two tone curves
+    OP_TONE_CRYSIS ((N,1): lum_adapted) and OP_TONE_FILMIC ((N,2): white_point, exposure_bias in 1 .. 10), which are
+    ``origin_tonemap`` with scales (255, 255) - then ``quantise_u8``'s conversion.  Only the result is stored; its bytes
+    are those of ``raw_crops`` -> ``origin_demosaic`` / ``chain_forward`` / ``origin_tonemap`` -> ``quantise_u8``.  No
+    bilateral.  H even and >= 4, W % 4 == 0; ``black_level`` and ``cfa`` as in ``serve_u8``.  With ``out`` given nothing
+    is allocated and the host does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
+    if kind is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = raw_u16.shape
+    _check_mirror(code, h, w)
+    out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
+    keep = [_dev(p) if p is not None else None for p in params]
+    L.call('risp_serve_classical_u8', _p(raw_u16), float(divisor), kind, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), _p(out),
+           int(bool(reverse_channels)), n, h, w, int(black_level), code, _stream())
     return out
 
 
