@@ -817,6 +817,61 @@ int risp_serve_classical_u8(const uint16_t *raw, float divisor, int demosaic, in
                             const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
                             int black_level, int cfa, void *stream);
 
+/* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
+ * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
+ * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S
+ * scene stages; the second statistics launch of a two-scene pipeline runs its prefix through the first scene stage).
+ *
+ * risp_serve_scene_stats: risp_serve_classical_u8's pixel pipeline (same arguments, rules, loads, reflection, phase and
+ * black level) with the n_ops PREFIX stages; no image is stored.  The values behind the prefix are reduced per workgroup
+ * (a 64 x 32 pixel tile) according to stat:
+ *   RISP_SCENE_MEAN3   the sums of B, G, R of the [0,1] values                                          (gray-world)
+ *   RISP_SCENE_MAX3    the maxima of B, G, R                                                            (white-world)
+ *   RISP_SCENE_LOGLUM  the sum of log((0.114 b' + 0.587 g' + 0.299 r') / 255 + 1e-4), c' = max(c * 255, 0)  (Reinhard)
+ * in a fixed order (the thread's eight pixels, wavefront shuffles, one LDS step; no atomics), and workgroup `tile` of image
+ * n writes the row partials[(n * G + tile) * 4 .. + 3] = (B, G, R, 0) or (sum, 0, 0, 0), G = risp_serve_scene_groups(H, W),
+ * tile = row-major index of the tiles of the mirrored image (the RGGB image of RISP_CFA_*: with cfa & 1 tile 0 holds the
+ * sensor's right-most columns, with cfa & 2 its bottom rows; the remap of workgroups to XCDs does not enter).  Every row is written in full: partials (N,G,4) needs no initialisation.
+ * Rules beyond risp_serve_classical_u8's: stat one of the three; partials not NULL and 16-byte aligned; ops[k] may also be
+ * RISP_OP_GAIN3_Q8 / RISP_OP_TONE_REINHARD, whose params[k] is the 16-byte aligned consts of an earlier finish.
+ *
+ * risp_serve_scene_finish: consts from partials, one workgroup per image; the G rows are added (or maximised) in index
+ * order in double precision and rounded to float once.  a, b: (N) per-image plugin parameters as risp_origin_tonemap takes
+ * them.  A mean is the total times the reciprocal 1.0f / HW taken in fp32, as risp_grayworld_gains_fwd and risp_origin_tonemap
+ * form it (not a division by HW).  consts holds 4 N floats, 16-byte aligned, every one written:
+ *   MEAN3   gain_c = gray / max(mean_c, 1e-6), gray = the mean of the three means (risp_grayworld_gains_fwd's expression);
+ *           stored as the (N,3) block RISP_OP_GAIN3 takes, packed in the first 3 N floats (the last N are 0).  a, b unused.
+ *   MAX3    (N,4) rows (g_b, g_g, g_r, 0), g_c = 1 + a[n] (big / mx_c - 1), mx_c = max(max_c * 255, 1e-3), big = max mx_c;
+ *           a = ratio (risp_origin_tonemap mode 3).  For RISP_OP_GAIN3_Q8.
+ *   LOGLUM  (N,4) rows (p0, p1, 0, 0), p0 = max(b[n], 0.01) / exp(sum / HW), p1 = 1 / lw^2, lw = max(a[n], 0.01) * 10;
+ *           a = white_point, b = middle_grey (risp_origin_tonemap mode 0).  For RISP_OP_TONE_REINHARD.
+ * Rules: stat one of the three; partials, consts not NULL and 16-byte aligned; a not NULL but for MEAN3, b not NULL for
+ * LOGLUM; 1 <= N <= 65535, G >= 1 (the statistics launch's), HW >= 1 (H * W).
+ *
+ * risp_serve_scene_u8: risp_serve_classical_u8 - signature, rules, bytes for the stages both accept - with two more
+ * stages, which belong to this entry point (and to the prefix of risp_serve_scene_stats) alone:
+ *   RISP_OP_GAIN3_Q8       white-world apply: risp_origin_tonemap mode 3's pixel expression with both scales 255 - the
+ *                          value times its channel's gain, rounded to its 8-bit code / 255; params[k] = MAX3 consts
+ *   RISP_OP_TONE_REINHARD  risp_origin_tonemap mode 0's pixel expression with both scales 255; params[k] = LOGLUM consts
+ * Gray-world applies as RISP_OP_GAIN3 with the MEAN3 consts.  A pipeline whose only scene stages are white-world has the
+ * composed route's bytes (a maximum has no order); sums taken in this order give constants that differ from the composed
+ * route's in their last bits, so gray-world and Reinhard agree with it up to rounding ties only.
+ * Anything outside the rules is refused before a launch and the message names the value. */
+#define RISP_OP_GAIN3_Q8 9
+#define RISP_OP_TONE_REINHARD 10
+#define RISP_SCENE_MEAN3 0
+#define RISP_SCENE_MAX3 1
+#define RISP_SCENE_LOGLUM 2
+int risp_serve_scene_groups(int H, int W); /* workgroups (partial rows) per image; 0 when H, W break the rules */
+int risp_serve_scene_stats(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                           const float *const *params, int stat, float *partials, int N, int H, int W, int black_level,
+                           int cfa, void *stream);
+int risp_serve_scene_finish(int stat, const float *partials, const float *a, const float *b, float *consts, int N, int G,
+                            int HW, void *stream);
+int risp_serve_scene_u8(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                        const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
+                        int black_level, int cfa, void *stream);
+
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic);

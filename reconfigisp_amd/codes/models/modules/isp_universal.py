@@ -43,7 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
-        self.last_serve_route = None            # 'fused' | 'classical' | 'composed': what the last serve() call ran
+        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'composed': what the last serve() call ran
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -93,18 +93,25 @@ class _FixedPipeline(nn.Module):
             self.intermediate_results.append(x)
         return x
 
-    def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+    def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
         bilinear / Malvar-He-Cutler demosaic, Crysis / Filmic tone curves), otherwise composed from the existing kernels;
         ``last_serve_route`` records the route taken.  ``intermediate_results`` is left as it was.  ``black_level`` and ``cfa`` ('rggb' | 'grbg' | 'gbrg'
         | 'bggr') describe the sensor (``pipeline_fusion.serve``): the pedestal is subtracted in integers, the divisor is
-        white_level - black_level, and another phase is served by mirrored addresses, without a further pass."""
+        white_level - black_level, and another phase is served by mirrored addresses, without a further pass.
+
+        ``fast_scene=True`` opts a pipeline with one or two of gray-world, white-world, Reinhard in to the ``'scene'`` route
+        (``pipeline_fusion.scene_plan``; H even and >= 4, W % 4 == 0): 2 S + 1 launches for S scene stages, the mosaic read
+        again per statistic instead of fp32 planes written.  White-world-only pipelines keep the composed route's bytes;
+        gray-world and Reinhard sum in another order and agree with the float64 reference of
+        tests/serve_scene_reference.py under its tie rule, not byte for byte.  Where the route does not apply the call runs
+        as without the flag."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa)
+                                                    black_level, cfa, fast_scene)
         return out
 
     @property

@@ -219,11 +219,84 @@ def _tone_block(mod, par):
     return cached[1]
 
 
-def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+_SCENE_STAT = {T.Grayworld: F.SCENE_MEAN3, T.OriginWbWhiteworld: F.SCENE_MAX3, T.OriginToneReinhard: F.SCENE_LOGLUM}
+_SCENE_OP = {T.Grayworld: F.OP_GAIN3, T.OriginWbWhiteworld: F.OP_GAIN3_Q8, T.OriginToneReinhard: F.OP_TONE_REINHARD}
+
+
+def scene_plan(modules):
+    """(demosaic kind, indices of the stages, which of them are scene stages) when ``serve(fast_scene=True)`` can take the
+    scene route for this module list (a pure function of it): Skips stripped, a nearest, classical bilinear or classical
+    Malvar-He-Cutler demosaic followed by at most MAX_CHAIN stages, each an element-wise one, a classical Crysis / Filmic
+    tone curve or one of the scene stages Grayworld, OriginWbWhiteworld, OriginToneReinhard, with one or two scene stages
+    among them.  None otherwise - without a scene stage ``serve_route`` already names a one-launch route."""
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+        return None
+    rest = idx[1:]
+    kinds = [type(modules[k]) for k in rest]
+    if len(rest) > MAX_CHAIN or any(t not in _CHAIN_OP and t not in _TONE_OP and t not in _SCENE_STAT for t in kinds):
+        return None
+    scene = [t in _SCENE_STAT for t in kinds]
+    if not 1 <= sum(scene) <= 2:
+        return None
+    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], rest, scene
+
+
+def _scene_vectors(mod, par):
+    """the (N,) plugin parameters ``risp_serve_scene_finish`` takes for a scene stage - what ``_origin_call`` hands to
+    ``F.origin_whiteworld`` / ``F.origin_tonemap`` - derived once per parameter version"""
+    if type(mod) is T.Grayworld:
+        return None, None
+    key = (par.data_ptr(), par._version, tuple(par.shape))
+    cached = mod.__dict__.get('_risp_scene_vectors')
+    if cached is None or cached[0] != key:
+        p = par.detach().float()
+        a = p[:, 0].contiguous()
+        b = p[:, 1].contiguous() if type(mod) is T.OriginToneReinhard else None
+        cached = mod.__dict__['_risp_scene_vectors'] = (key, a, b, par)
+    return cached[1], cached[2]
+
+
+def _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa):
+    """2 S + 1 launches for S scene stages: per scene stage the statistics of its input (the mosaic read again, the pipeline
+    evaluated up to the stage, earlier scene stages with their constants) and the finish launch, then the serving launch"""
+    kind, stages, scene = plan
+    n, h, w = raw_u16.shape
+    ops, params, s = [], [], 0
+    for k, is_scene in zip(stages, scene):
+        mod, par = modules[k], param_tensors[k]
+        t = type(mod)
+        if is_scene:
+            parts = F.serve_scene_stats(raw_u16, divisor, kind, ops, params, _SCENE_STAT[t], None, black_level, cfa)
+            a, b = _scene_vectors(mod, par)
+            params.append(F.serve_scene_finish(_SCENE_STAT[t], parts, h * w, a, b, None, tag=s))
+            ops.append(_SCENE_OP[t])
+            s += 1
+        elif t in _TONE_OP:
+            ops.append(_TONE_OP[t])
+            params.append(_tone_block(mod, par))
+        else:
+            ops.append(_CHAIN_OP[t])
+            params.append(_chain_param(mod, par))
+    return F.serve_scene_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa)
+
+
+def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
+          fast_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
     and >= 4, W % 4 == 0) or ``'composed'``.
+
+    ``fast_scene=True`` opts in to the ``'scene'`` route where ``scene_plan`` is not None (a pipeline with one or two of
+    gray-world, white-world, Reinhard), H is even and >= 4, W % 4 == 0, N <= 65535 and the frames are 8-byte aligned;
+    otherwise the call runs exactly as without it.  The scene route reads the mosaic once per scene stage for its
+    whole-image statistic and once to serve: 2 S + 1 launches for S scene stages, no fp32 plane written, ``black_level``,
+    ``cfa`` and ``reverse_channels`` as on the classical route; with ``out`` given and a warm cache it allocates nothing
+    and never waits for the device.  Its contract is weaker than the default's, which is why it is opt-in: a pipeline whose
+    only scene stages are white-world has the composed route's bytes (a maximum has no order); gray-world and Reinhard take
+    their sums in another order, their constants differ from the composed route's in the last bits, and the bytes agree
+    with the float64 reference of tests/serve_scene_reference.py under its tie rule, not with ``torch.equal``.
 
     ``black_level`` (integer, 0 <= black_level < white_level) and ``cfa`` ('rggb' | 'grbg' | 'gbrg' | 'bggr') describe the
     sensor: the input becomes max(raw - black_level, 0) / (white_level - black_level) and the mosaic of another phase is
@@ -241,6 +314,10 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     n, h, w = raw_u16.shape
     F._check_mirror(code, h, w)
     divisor = white_level - black_level
+    if fast_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+        plan = scene_plan(modules)
+        if plan is not None:
+            return _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa), 'scene'
     split = _serve_split(modules)
     if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         bil, chain = split

@@ -641,6 +641,109 @@ def serve_classical_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels
     return out
 
 
+OP_GAIN3_Q8, OP_TONE_REINHARD = 9, 10      # stages of serve_scene_u8 / serve_scene_stats only: they take serve_scene_finish's constants
+SCENE_MEAN3, SCENE_MAX3, SCENE_LOGLUM = 0, 1, 2       # RISP_SCENE_*
+# (device, stream, tag, shape) -> float32 scratch of the scene route (partials, constants), kept until release_scene_scratch()
+_scene_scratch = {}
+
+
+def release_scene_scratch():
+    """Drop the cached partials and constants of the scene route (every device and stream)."""
+    _scene_scratch.clear()
+
+
+def _scene_buffer(device, tag, shape):
+    key = (device, _stream().value, tag, tuple(shape))
+    buf = _scene_scratch.get(key)
+    if buf is None:
+        buf = _scene_scratch[key] = torch.empty(shape, device=device, dtype=torch.float32)
+    return buf
+
+
+def serve_scene_groups(h, w):
+    """partial rows per image of ``serve_scene_stats`` (workgroups of 64 x 32 pixels)"""
+    g = L.load().risp_serve_scene_groups(int(h), int(w))
+    if g <= 0:
+        raise ValueError('a %d x %d frame is outside the scene route: H even and >= 4, W a multiple of 4' % (h, w))
+    return g
+
+
+def _scene_frame_args(raw_u16, demosaic, ops, params, black_level, cfa):
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
+    if kind is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    _check_mirror(code, raw_u16.shape[1], raw_u16.shape[2])
+    keep = [_dev(p) if p is not None else None for p in params]
+    return kind, code, keep, (C.c_int * max(1, len(ops)))(*ops), L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None])
+
+
+def serve_scene_stats(raw_u16, divisor, demosaic, ops, params, stat, partials=None, black_level=0, cfa='rggb', tag=0):
+    """The statistics launch of the scene route (``risp_serve_scene_stats``): ``serve_classical_u8``'s pixel pipeline with the
+    PREFIX stages ``ops`` / ``params`` in front of a scene stage, reduced per 64 x 32 pixel tile according to ``stat`` -
+    SCENE_MEAN3 (sums of B, G, R), SCENE_MAX3 (maxima), SCENE_LOGLUM (sum of log-luminance) - into ``partials``
+    (N, serve_scene_groups(H, W), 4) float32, every row written.  No image is stored.  The prefix may hold OP_GAIN3_Q8 /
+    OP_TONE_REINHARD with the constants of an earlier ``serve_scene_finish``.  ``partials`` None: a buffer cached per
+    device, stream, ``tag`` and shape."""
+    kind, code, keep, oparr, blocks = _scene_frame_args(raw_u16, demosaic, ops, params, black_level, cfa)
+    if stat not in (SCENE_MEAN3, SCENE_MAX3, SCENE_LOGLUM):
+        raise ValueError('stat %r: SCENE_MEAN3, SCENE_MAX3 or SCENE_LOGLUM' % (stat,))
+    n, h, w = raw_u16.shape
+    shape = (n, serve_scene_groups(h, w), 4)
+    if partials is None:
+        partials = _scene_buffer(raw_u16.device, ('partials', tag), shape)
+    elif (partials.dtype != torch.float32 or tuple(partials.shape) != shape or not partials.is_contiguous()
+          or partials.device != raw_u16.device):
+        raise ValueError('partials must be a contiguous float32 %s tensor on %s' % (shape, raw_u16.device))
+    L.call('risp_serve_scene_stats', _p(raw_u16), float(divisor), kind, len(ops), oparr, blocks, int(stat), _p(partials), n, h, w,
+           int(black_level), code, _stream())
+    return partials
+
+
+def serve_scene_finish(stat, partials, hw, a=None, b=None, consts=None, tag=0):
+    """``partials`` (N,G,4) of ``serve_scene_stats`` -> the per-image constants of the scene stage (``risp_serve_scene_finish``;
+    the rows are added in index order in double precision).  ``hw`` = H * W; ``a`` / ``b`` (N,) the plugin parameters:
+    nothing for SCENE_MEAN3, the ratio for SCENE_MAX3, (white_point, middle_grey) for SCENE_LOGLUM.  Returns the block the
+    stage takes: (N,3) gains for OP_GAIN3 (a view of the 4 N floats), (N,4) for OP_GAIN3_Q8 and OP_TONE_REINHARD.
+    ``consts`` None: a buffer cached per device, stream, ``tag`` and shape."""
+    _need_gpu(partials, 'partials')
+    if partials.dtype != torch.float32 or partials.dim() != 3 or partials.shape[2] != 4 or not partials.is_contiguous():
+        raise ValueError('expected contiguous float32 (N,G,4) partials, got %s %s' % (partials.dtype, tuple(partials.shape)))
+    if stat not in (SCENE_MEAN3, SCENE_MAX3, SCENE_LOGLUM):
+        raise ValueError('stat %r: SCENE_MEAN3, SCENE_MAX3 or SCENE_LOGLUM' % (stat,))
+    n, g = partials.shape[:2]
+    if consts is None:
+        consts = _scene_buffer(partials.device, ('consts', tag), (n, 4))
+    elif consts.dtype != torch.float32 or consts.numel() != 4 * n or not consts.is_contiguous() or consts.device != partials.device:
+        raise ValueError('consts must be a contiguous float32 tensor of %d elements on %s' % (4 * n, partials.device))
+    if (stat != SCENE_MEAN3 and a is None) or (stat == SCENE_LOGLUM and b is None):
+        raise ValueError('stat %d needs its plugin parameters' % stat)
+    a = None if a is None else _vec(a, n, partials.device)
+    b = None if b is None else _vec(b, n, partials.device)
+    L.call('risp_serve_scene_finish', int(stat), _p(partials), _p(a), _p(b), _p(consts), n, g, int(hw), _stream())
+    return consts.view(-1)[:3 * n].view(n, 3) if stat == SCENE_MEAN3 else consts.view(n, 4)
+
+
+def serve_scene_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+    """``serve_classical_u8`` with two more stages (``risp_serve_scene_u8``): OP_GAIN3_Q8 (white-world apply) and
+    OP_TONE_REINHARD, whose blocks are the (N,4) constants of ``serve_scene_finish``; gray-world applies as OP_GAIN3 with
+    that function's (N,3) gains.  Same frames, rules and bytes otherwise.  With ``out`` given nothing is allocated and the
+    host does not wait."""
+    kind, code, keep, oparr, blocks = _scene_frame_args(raw_u16, demosaic, ops, params, black_level, cfa)
+    n, h, w = raw_u16.shape
+    out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
+    L.call('risp_serve_scene_u8', _p(raw_u16), float(divisor), kind, len(ops), oparr, blocks, _p(out), int(bool(reverse_channels)),
+           n, h, w, int(black_level), code, _stream())
+    return out
+
+
 class _FanOut(torch.autograd.Function):
     """k aliases of one tensor whose gradients are added by ONE launch (operand order, the order autograd's own pairwise
     additions take: the same bits) - the slot input of a super-net feeds the proxy group, Path-Restore and the fused mixture, and

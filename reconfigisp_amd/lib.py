@@ -187,6 +187,10 @@ SIGNATURES = {
     'risp_quantise_u8_flip': (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_u8_cfa': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_classical_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_scene_groups': (_i, [_i, _i]),
+    'risp_serve_scene_stats': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _f, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_scene_finish': (_i, [_i, _f, _f, _f, _f, _i, _i, _i, _s]),
+    'risp_serve_scene_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_sse_uint8_doubles': (_z, []),
     'risp_sse_uint8': (_i, [_f, _f, _f, _z, _z, _s]),
     'risp_ssim_scratch_floats': (_z, [_i, _i, _i, _i]),
