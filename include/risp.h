@@ -872,6 +872,32 @@ int risp_serve_scene_u8(const uint16_t *raw, float divisor, int demosaic, int n_
                         const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
                         int black_level, int cfa, void *stream);
 
+/* A classical pipeline with ONE classical denoiser as an ISP, one launch (risp_serve_denoise.hip): raw (N,H,W) uint16 mosaic
+ * of the sensor -> out (N,H,W,3) bytes.  Per pixel: risp_serve_classical_u8's input expression and demosaic, the n_pre stages
+ * pre_ops, the denoiser, the n_post stages post_ops, the conversion of risp_quantise_u8.  Only the result is stored; its bytes
+ * are those of risp_raw_crop_cfa -> demosaic -> stages -> risp_origin_bilateral | risp_origin_median | risp_origin_fastnlm
+ * (in_scale 255, out_div 255) -> stages -> risp_quantise_u8_flip, every stage as risp_serve_classical_u8 states it.
+ * pre_ops[k], post_ops[k]: the stages risp_serve_classical_u8 accepts (SKIP, WB_MANUAL, GAMMA, GTM_MANUAL, WB_QUADRATIC, GAIN3,
+ * TONE_CRYSIS, TONE_FILMIC), n_pre + n_post <= RISP_MAX_CHAIN, every stage but a SKIP needs its parameter block.
+ * denoise: RISP_DENOISE_BILATERAL  window = 3, den_a = sigma_color (N), den_b = sigma_space (N); search ignored
+ *          RISP_DENOISE_MEDIAN     window = 3 (the size); search, den_a, den_b ignored
+ *          RISP_DENOISE_FASTNLM    window = 3 (the block), search = 3, den_a = decay (N); den_b ignored
+ * with the per-image arrays as the risp_origin_* entry points take them.  Any other window, size, block or search is refused:
+ * those pipelines compose.  The image border is reflect-101 in the image the denoiser sees (the pipeline evaluated at the
+ * reflected coordinate), as in risp_origin_*.
+ * A workgroup owns a 64 x 32 pixel tile: it evaluates demosaic and pre-stages for the tile and a ring into LDS (three fp32
+ * planes of 36 x 72, 31104 bytes), one barrier (two on the image border), then the denoiser and post-stages per thread.
+ * black_level and cfa as in risp_serve_u8_cfa.  Rules (anything else is refused before a launch and the message names it): raw
+ * and out not NULL, raw 8-byte and out 4-byte aligned, whole contiguous frames; divisor > 0; demosaic 0 .. 2; denoise 0 .. 2;
+ * 1 <= N <= 65535, H even and >= 4, W % 4 == 0 and >= 4; cfa 0 .. 3; 0 <= black_level <= 65535. */
+#define RISP_DENOISE_BILATERAL 0
+#define RISP_DENOISE_MEDIAN 1
+#define RISP_DENOISE_FASTNLM 2
+int risp_serve_denoise_u8(const uint16_t *raw, float divisor, int demosaic, int n_pre, const int *pre_ops,
+                          const float *const *pre_params, int denoise, int window, int search, const float *den_a,
+                          const float *den_b, int n_post, const int *post_ops, const float *const *post_params, uint8_t *out,
+                          int reverse_channels, int N, int H, int W, int black_level, int cfa, void *stream);
+
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic);

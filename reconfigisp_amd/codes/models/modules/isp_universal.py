@@ -43,7 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
-        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'composed': what the last serve() call ran
+        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'composed': what the last serve() call ran
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -93,7 +93,8 @@ class _FixedPipeline(nn.Module):
             self.intermediate_results.append(x)
         return x
 
-    def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False):
+    def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
+              fast_denoise=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -107,11 +108,16 @@ class _FixedPipeline(nn.Module):
         again per statistic instead of fp32 planes written.  White-world-only pipelines keep the composed route's bytes;
         gray-world and Reinhard sum in another order and agree with the float64 reference of
         tests/serve_scene_reference.py under its tie rule, not byte for byte.  Where the route does not apply the call runs
-        as without the flag."""
+        as without the flag.
+
+        ``fast_denoise=True`` opts a pipeline with one classical bilateral, median or non-local means behind a classical
+        demosaic in to the ``'denoise'`` route (``pipeline_fusion.denoise_plan``; H even and >= 4, W % 4 == 0, learned sizes
+        3 / 3 / (3, 3)): one launch with the composed route's bytes.  Where the route does not apply the call runs as
+        without the flag."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa, fast_scene)
+                                                    black_level, cfa, fast_scene, fast_denoise)
         return out
 
     @property

@@ -198,7 +198,8 @@ def serve_route(modules):
     stripped, is the nearest, the classical bilinear or the classical Malvar-He-Cutler demosaic followed by at most
     MAX_CHAIN stages, each WbManual / Gamma / GtmManual / WbQuadratic or a classical Crysis / Filmic tone curve;
     ``'composed'`` otherwise.  A bilateral behind a stencil demosaic, Reinhard, white-world and gray-world (a whole-image
-    quantity first), median / NLM / BM3D and every CNN stage compose."""
+    quantity first), median / NLM / BM3D and every CNN stage compose on the default call; ``scene_plan`` and ``denoise_plan``
+    name the lists among them that ``serve(fast_scene=True)`` / ``serve(fast_denoise=True)`` take without fp32 planes."""
     if _serve_split(modules) is not None:
         return 'fused'
     return 'classical' if _classical_split(modules) is not None else 'composed'
@@ -281,8 +282,62 @@ def _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channel
     return F.serve_scene_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa)
 
 
+_DENOISER = {T.OriginNoiseBilateral: 'bilateral', T.OriginNoiseMedian: 'median', T.OriginNoiseFastnlm: 'fastnlm'}
+
+
+def denoise_plan(modules):
+    """(demosaic kind, indices of the stages in front of the denoiser, index of the denoiser, indices of the stages behind it)
+    when ``serve(fast_denoise=True)`` can take the denoise route for this module list (a pure function of it): Skips stripped,
+    a nearest, classical bilinear or classical Malvar-He-Cutler demosaic, stages, exactly one of OriginNoiseBilateral /
+    OriginNoiseMedian / OriginNoiseFastnlm, more stages - each stage an element-wise one or a classical Crysis / Filmic tone
+    curve, at most MAX_CHAIN of them in all.  None otherwise: where ``serve_plan`` already says ``'fused'`` (the bilateral
+    directly behind the nearest demosaic), for two denoisers, scene stages, BM3D, CNN stages and the proxy pipelines.  Whether
+    the learned parameters give the sizes the route serves (3 / 3 / (3, 3)) is known only from them: ``serve`` checks it."""
+    if _serve_split(modules) is not None:
+        return None
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+        return None
+    rest = idx[1:]
+    den = [k for k in rest if type(modules[k]) in _DENOISER]
+    if len(den) != 1:
+        return None
+    stages = [k for k in rest if k != den[0]]
+    if len(stages) > MAX_CHAIN or any(type(modules[k]) not in _CHAIN_OP and type(modules[k]) not in _TONE_OP for k in stages):
+        return None
+    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], [k for k in stages if k < den[0]], den[0], [k for k in stages if k > den[0]]
+
+
+def _denoise_args(mod, par):
+    """(name, arguments) as ``F.serve_denoise_u8`` takes them, or None when the parameters give a size the denoise route does
+    not serve - derived once per parameter version (the median's size and the non-local means' sizes need a host read)"""
+    if type(mod) is T.OriginNoiseBilateral:
+        _, sc, ss, wmax = _bilateral_args(mod, par)
+        return ('bilateral', (3, sc, ss)) if wmax == 3 else None
+    key = (par.data_ptr(), par._version, tuple(par.shape))
+    cached = mod.__dict__.get('_risp_denoise_args')
+    if cached is None or cached[0] != key:
+        d = mod._params(par.detach(), {})
+        if type(mod) is T.OriginNoiseMedian:
+            args = ('median', (3,)) if d['size'] == 3 else None
+        else:
+            sizes = torch.stack([d['block_size'], d['search_block']]).cpu()
+            ok = bool((sizes == 3).all())
+            args = ('fastnlm', (3, 3, d['decay_factor'].float().contiguous())) if ok else None
+        cached = mod.__dict__['_risp_denoise_args'] = (key, args, par)     # (par kept: its address stays its own while the key lives)
+    return cached[1]
+
+
+def _stage_lists(modules, param_tensors, stages):
+    """(op codes, parameter blocks) of element-wise / Crysis / Filmic stages as the classical and the denoise launch take them"""
+    ops =[_TONE_OP.get(type(modules[k])) or _CHAIN_OP[type(modules[k])] for k in stages]
+    params = [_tone_block(modules[k], param_tensors[k]) if type(modules[k]) in _TONE_OP
+              else _chain_param(modules[k], param_tensors[k]) for k in stages]
+    return ops, params
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
-          fast_scene=False):
+          fast_scene=False, fast_denoise=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -297,6 +352,14 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     only scene stages are white-world has the composed route's bytes (a maximum has no order); gray-world and Reinhard take
     their sums in another order, their constants differ from the composed route's in the last bits, and the bytes agree
     with the float64 reference of tests/serve_scene_reference.py under its tie rule, not with ``torch.equal``.
+
+    ``fast_denoise=True`` opts in to the ``'denoise'`` route (``risp_serve_denoise_u8``, one launch) where ``denoise_plan`` is
+    not None - one classical bilateral, median or non-local means anywhere behind a classical demosaic -, the geometry is the
+    classical route's and the learned parameters give the sizes every reference configuration below a saturated parameter
+    produces (bilateral window 3, median 3, non-local means block 3 and search 3); otherwise the call runs exactly as without
+    it.  The bytes are the composed route's (``torch.equal``); the keyword exists because the default call's route is pinned by
+    tests.  The denoiser's arguments are derived once per parameter version: with ``out`` given a warm call launches once,
+    allocates nothing and never waits for the device.
 
     ``black_level`` (integer, 0 <= black_level < white_level) and ``cfa`` ('rggb' | 'grbg' | 'gbrg' | 'bggr') describe the
     sensor: the input becomes max(raw - black_level, 0) / (white_level - black_level) and the mosaic of another phase is
@@ -318,6 +381,14 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         plan = scene_plan(modules)
         if plan is not None:
             return _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa), 'scene'
+    if fast_denoise and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+        plan = denoise_plan(modules)
+        args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
+        if args is not None:
+            pre_ops, pre_params = _stage_lists(modules, param_tensors, plan[1])
+            post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
+            return F.serve_denoise_u8(raw_u16, divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
+                                      reverse_channels, out, black_level, cfa), 'denoise'
     split = _serve_split(modules)
     if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         bil, chain = split
@@ -330,9 +401,7 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     if (serve_route(modules) == 'classical' and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535
             and raw_u16.data_ptr() % 8 == 0):
         kind, stages = _classical_split(modules)
-        ops = [_TONE_OP.get(type(modules[k])) or _CHAIN_OP[type(modules[k])] for k in stages]
-        params = [_tone_block(modules[k], param_tensors[k]) if type(modules[k]) in _TONE_OP
-                  else _chain_param(modules[k], param_tensors[k]) for k in stages]
+        ops, params = _stage_lists(modules, param_tensors, stages)
         return F.serve_classical_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa), 'classical'
     from ...data.gpu_input import raw_crops
     sel = torch.zeros((n, 3), device=raw_u16.device, dtype=torch.int32)

@@ -641,6 +641,62 @@ def serve_classical_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels
     return out
 
 
+DENOISE = {'bilateral': 0, 'median': 1, 'fastnlm': 2}          # RISP_DENOISE_*
+
+
+def serve_denoise_u8(raw_u16, divisor, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+                     reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+    """A classical pipeline with ONE classical denoiser as an ISP in ONE launch (``risp_serve_denoise_u8``): (N,H,W)
+    ``torch.uint16`` frames on the device -> (N,H,W,3) ``torch.uint8``.  ``serve_classical_u8``'s input expression and
+    demosaic ``kind``, the stages ``pre_ops`` / ``pre_params``, the denoiser, the stages ``post_ops`` / ``post_params`` (both
+    lists hold what ``serve_classical_u8`` accepts, at most 8 stages together), then ``quantise_u8``'s conversion.
+    ``denoise`` is a key of ``DENOISE`` and ``denoise_args`` what ``origin_denoise`` takes for it, at the sizes the reference's
+    parameter rules give below a saturated parameter:
+
+        'bilateral'  (3, sigma_color, sigma_space)    'median'  (3,)    'fastnlm'  (3, 3, decay)
+
+    with (N,) float32 device tensors for the per-image values; any other window, size, block or search is refused (those
+    pipelines compose).  Only the result is stored; its bytes are those of ``raw_crops`` -> ``origin_demosaic`` /
+    ``chain_forward`` / ``origin_tonemap`` -> ``origin_denoise`` -> stages -> ``quantise_u8`` with scales (255, 255).  H even
+    and >= 4, W % 4 == 0; ``black_level`` and ``cfa`` as in ``serve_u8``.  With ``out`` given nothing is allocated and the host
+    does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(pre_ops) != len(pre_params) or len(post_ops) != len(post_params):
+        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(pre_ops), len(post_ops), len(pre_params), len(post_params)))
+    code_d = DEMOSAIC.get(kind) if isinstance(kind, str) else None
+    if code_d is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (kind, ', '.join(DEMOSAIC)))
+    code_n = DENOISE.get(denoise) if isinstance(denoise, str) else None
+    if code_n is None:
+        raise ValueError('unknown denoiser %r: one of %s' % (denoise, ', '.join(DENOISE)))
+    if len(denoise_args) != (3, 1, 3)[code_n]:
+        raise ValueError('%s takes %d arguments, got %d' % (denoise, (3, 1, 3)[code_n], len(denoise_args)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = raw_u16.shape
+    _check_mirror(code, h, w)
+    window, search, vecs = int(denoise_args[0]), 0, []
+    if code_n == 0:
+        vecs = list(denoise_args[1:])
+    elif code_n == 2:
+        search, vecs = int(denoise_args[1]), [denoise_args[2]]
+    for v in vecs:
+        if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != (n,) or not v.is_contiguous():
+            raise ValueError('%s takes contiguous float32 (%d,) device tensors for its per-image values' % (denoise, n))
+    out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
+    pre = [_dev(p) if p is not None else None for p in pre_params]
+    post = [_dev(p) if p is not None else None for p in post_params]
+    L.call('risp_serve_denoise_u8', _p(raw_u16), float(divisor), code_d, len(pre_ops), (C.c_int * max(1, len(pre_ops)))(*pre_ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in pre] or [None]), code_n, window, search,
+           _p(vecs[0]) if vecs else None, _p(vecs[1]) if len(vecs) > 1 else None, len(post_ops),
+           (C.c_int * max(1, len(post_ops)))(*post_ops), L.ptr_array([p.data_ptr() if p is not None else None for p in post] or [None]),
+           _p(out), int(bool(reverse_channels)), n, h, w, int(black_level), code, _stream())
+    return out
+
+
 OP_GAIN3_Q8, OP_TONE_REINHARD = 9, 10      # stages of serve_scene_u8 / serve_scene_stats only: they take serve_scene_finish's constants
 SCENE_MEAN3, SCENE_MAX3, SCENE_LOGLUM = 0, 1, 2       # RISP_SCENE_*
 # (device, stream, tag, shape) -> float32 scratch of the scene route (partials, constants), kept until release_scene_scratch()
