@@ -2,8 +2,10 @@
 
     risp_serve_u8[_cfa]        max(s - b, 0) / (white - b) -> nearest demosaic [-> bilateral] -> element-wise stages -> bytes
     risp_serve_classical_u8    ... -> nearest | bilinear | Malvar-He-Cutler demosaic -> element-wise / Crysis / Filmic -> bytes
+    risp_serve_denoise_u8      ... -> one of the three demosaics -> stages -> bilateral | median | non-local means -> stages -> bytes
 
-Truth of tests/test_serve_reference_cpu.py and of the case table tests/serve_space_cases.py.  Plain numpy / torch on the CPU, no HIP and
+Truth of tests/test_serve_reference_cpu.py, tests/test_serve_denoise_reference_cpu.py and of the case tables
+tests/serve_space_cases.py and tests/serve_denoise_cases.py.  Plain numpy / torch on the CPU, no HIP and
 no import of the package.  It is the SECOND statement of a Bayer phase beside "phase by mirror": a phase is a table of
 colour sites (``SITES``), every demosaic below is written for an arbitrary table, and no mirror appears in this file.
 
@@ -14,6 +16,11 @@ OPSPEC restated (constants as oracle/isp_oracle.py lists them, written out here)
     site type.  Both on samples x 255 with reflect-101 borders (-1 -> 1, H -> H - 2) and the 8-bit code
     floor(clamp(v, 0, 255) + 0.5), returned as code / 255;
   * bilateral (serve_u8 only): fused_segment_reference.bilateral_raw and its code;
+  * denoisers (serve_denoise_u8; oracle/isp_oracle.py: origin_denoise), on the finished pixels x 255 with reflect-101
+    borders in image coordinates: bilateral, window 3, weights exp(-(dy^2 + dx^2) / (2 ss^2) - d^2 / (2 sc^2)) with d the L1
+    colour distance, one weighted mean per channel and its code; median 3 x 3 of the 8-bit codes of its input, per channel,
+    an integer carried as a code; non-local means, block 3 and search 3: per shift d2 = the sum over the block and the
+    channels of squared differences, weight exp(-(d2 / 27) / decay^2), the centre shift 1, the weighted mean and its code;
   * stages: fused_segment_reference.elementwise for the six element-wise operators; Crysis 1 - exp(-max(x,0) * 0.5 /
     (lum_adapted + 0.05)); Filmic hable(max(x,0) * exposure_bias) / hable(11.2 * max(white_point, 0.01)); both tone curves
     end in the 8-bit code;
@@ -27,12 +34,17 @@ sample at or below the black level, a sample at the white level, the bound of an
 Gain3 keep a pinned 0.
 
 The small functions green_row, far_ring (with its ``inside`` argument), malvar_terms, crysis_scale, filmic_block,
-image_params, store_order, final_byte and code are each one sentence of the OPSPEC on its own, so that
-tests/test_serve_reference_cpu.py can put a wrong variant of that one sentence in its place.
+image_params, store_order, final_byte and code - and for the denoisers denoise_border, median_input, median_window,
+colour_distance, spatial_term, nlm_normaliser, nlm_block_pair, nlm_weight, nlm_centre_weight and split_stages - are each
+one sentence of the OPSPEC on its own, so that tests/test_serve_reference_cpu.py and
+tests/test_serve_denoise_reference_cpu.py can put a wrong variant of that one sentence in its place.
 
 Tie bookkeeping: at every quantisation point the distance, in codes, of the unquantised float64 value from the nearest
 decision boundary.  ``inner`` (N,H,W): the smallest over a pixel's three channels and all inner points (demosaic code,
-bilateral code, tone-curve code) - WbQuadratic mixes channels, so a tie in one channel taints the pixel.  ``final``
+bilateral code, tone-curve code, the codes 'den-bilateral' and 'fastnlm' of the denoise route, and the median's input code
+'median-in/<last op>' where a float stands in front of it: a carried code makes the median exact) - WbQuadratic mixes channels, so a tie in one channel taints the pixel.  A denoiser mixes
+pixels: a code in front of it that may fall either way reaches every pixel of its footprint, which neighbour_taint excuses
+where that code can change the denoiser's result (a second evaluation with every such code on its other side).  ``final``
 (N,H,W,3), per byte in stored order: the distance of v * 255 from the nearest integer in 1 .. 255 for a float, infinite
 for a carried code, and for a pinned 1 the distance of the operator's unclamped value from its bound.
 
@@ -271,6 +283,113 @@ def store_order(reverse):
     return [2, 1, 0] if reverse else [0, 1, 2]
 
 
+# ---------------------------------------------------------------------------------------------------- the classical denoisers
+DENOISERS = ('bilateral', 'median', 'fastnlm')             # RISP_DENOISE_* in this order
+
+
+def denoise_border(i, n):
+    """the denoisers take a neighbour outside the image from the FINISHED pixels through reflect-101 in image coordinates"""
+    return reflect101(i, n)
+
+
+def _taps(v):
+    """v (N,3,H,W) -> tap(dy, dx): the image shifted by (dy, dx) under the denoisers' border rule"""
+    h, w = v.shape[2:]
+    rows, cols = np.arange(h), np.arange(w)
+    return lambda dy, dx: v[:, :, denoise_border(rows + dy, h)][:, :, :, denoise_border(cols + dx, w)]
+
+
+def colour_distance(q, c):
+    """the bilateral's colour distance between a neighbour and the centre: L1 over the three channels"""
+    return np.abs(q - c).sum(axis=1, keepdims=True)
+
+
+def spatial_term(dy, dx, ss, dtype):
+    """the bilateral's spatial exponent (dy^2 + dx^2) / (2 ss^2)"""
+    return dtype(dy * dy + dx * dx) / (dtype(2) * ss * ss)
+
+
+def denoise_bilateral(v, sigma_color, sigma_space, dtype=np.float64):
+    """window 3.  v (N,3,H,W) in the 0..255 domain, (N,) sigmas -> the weighted mean in front of the clip-and-round.  The
+    oracle's expression term by term (one reciprocal per pixel); in float64 it is fused_segment_reference.bilateral_raw at
+    window 3 (tests/test_serve_denoise_reference_cpu.py), written out here so that one sentence of it can be replaced"""
+    d, n = dtype, v.shape[0]
+    v = v.astype(d)
+    sc, ss = (np.asarray(a, np.float64).astype(d).reshape(n, 1, 1, 1) for a in (sigma_color, sigma_space))
+    tap = _taps(v)
+    num, den = np.zeros(v.shape, d), np.zeros((n, 1) + v.shape[2:], d)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            q = tap(dy, dx)
+            dist = colour_distance(q, v)
+            wgt = _exp(-spatial_term(dy, dx, ss, d) - dist * dist / (d(2) * sc * sc))
+            num, den = num + wgt * q, den + wgt
+    return num * (d(1) / den)
+
+
+def median_input(v, codes, dtype):
+    """what the median sorts: the 8-bit codes of its input, floor(clamp(v, 0, 255) + 0.5)"""
+    return codes.astype(dtype)
+
+
+def median_window(win):
+    """win (N,3,H,W,9), the 3 x 3 neighbourhood of every channel -> the middle of the 9 values, per channel"""
+    return np.sort(win, axis=-1)[..., 4]
+
+
+def denoise_median(c):
+    """3 x 3.  c (N,3,H,W) -> the median of every channel's neighbourhood"""
+    tap = _taps(c)
+    return median_window(np.stack([tap(dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1)], axis=-1))
+
+
+def nlm_normaliser():
+    """d2 is divided by channels x block x block"""
+    return 3 * 3 * 3
+
+
+def nlm_block_pair(tap, sy, sx, oy, ox):
+    """the two pixels compared at block offset (oy, ox) for the shift (sy, sx): the offset moves both sides"""
+    return tap(sy + oy, sx + ox), tap(oy, ox)
+
+
+def nlm_weight(d2, decay, dtype):
+    """exp(-(d2 / normaliser) / decay^2)"""
+    return _exp(-(d2 / dtype(nlm_normaliser())) / (decay * decay))
+
+
+def nlm_centre_weight():
+    """the unshifted pixel takes part, with weight 1 (its d2 is 0)"""
+    return 1
+
+
+def denoise_fastnlm(v, decay, dtype=np.float64):
+    """block 3, search 3.  v (N,3,H,W) in the 0..255 domain, (N,) decay -> the weighted mean in front of the clip-and-round"""
+    d, n = dtype, v.shape[0]
+    v = v.astype(d)
+    decay = np.asarray(decay, np.float64).astype(d).reshape(n, 1, 1, 1)
+    tap = _taps(v)
+    num, den = np.zeros(v.shape, d), np.zeros((n, 1) + v.shape[2:], d)
+    for sy in (-1, 0, 1):
+        for sx in (-1, 0, 1):
+            if (sy, sx) == (0, 0):
+                wgt = np.full(den.shape, nlm_centre_weight(), d)
+            else:
+                d2 = np.zeros(den.shape, d)
+                for oy in (-1, 0, 1):
+                    for ox in (-1, 0, 1):
+                        a, b = nlm_block_pair(tap, sy, sx, oy, ox)
+                        d2 = d2 + ((a - b) * (a - b)).sum(axis=1, keepdims=True)
+                wgt = nlm_weight(d2, decay, d)
+            num, den = num + wgt * tap(sy, sx), den + wgt
+    return num * (d(1) / den)
+
+
+def split_stages(stages, n_pre):
+    """the stage list as (stages in front of the denoiser, stages behind it): the first n_pre, the rest"""
+    return stages[:n_pre], stages[n_pre:]
+
+
 # ---------------------------------------------------------------------------------------------------- the pipeline
 class Trace:
     """what one evaluation leaves: bytes, the tie bookkeeping, and per quantisation point (kind, unquantised value, codes)"""
@@ -278,14 +397,22 @@ class Trace:
     def __init__(self):
         self.points, self.bytes, self.inner, self.final, self.final_kind, self.final_t = [], None, None, None, None, None
         self.bilateral_windows, self.final_pin = None, None        # per-image windows where a bilateral ran; pins at the truncation
+        # the denoise route: how many points stand in front of the denoiser's neighbourhood, (name, its output in front of
+        # the code - the median's codes), the evaluation again with flipped ties (neighbour_taint), its cached result
+        self.denoise_at, self.denoise_out, self.rerun, self.taint, self.taint_distance = None, None, None, None, None
 
 
-def serve(raw, white, black, phase, demosaic, bilateral, ops, params, reverse=False, dtype=np.float64, sync=None):
+def serve(raw, white, black, phase, demosaic, bilateral, ops, params, reverse=False, dtype=np.float64, sync=None, denoise=None,
+          _flip=None):
     """raw (N,H,W) uint16 (or any integer) frames -> Trace.
 
     ``phase`` a key of SITES, ``demosaic`` a key of DEMOSAIC, ``bilateral`` None or (window (N,), sigma_color (N,),
     sigma_space (N,)) - behind the nearest demosaic only -, ``ops`` / ``params`` the stage list as the C ABI takes it
-    (per-image (N,P) blocks, None for SKIP).  ``sync``: the float64 Trace whose codes a float32 run takes over."""
+    (per-image (N,P) blocks, None for SKIP).  ``sync``: the float64 Trace whose codes a float32 run takes over.
+    ``denoise`` None or (name, n_pre, args) - risp_serve_denoise_u8 -: ``name`` of DENOISERS at the sizes that entry point
+    serves (window 3, 3 x 3, block 3 and search 3), behind the first ``n_pre`` entries of ``ops``, ``args`` its per-image (N,)
+    blocks as the C ABI takes them: (sigma_color, sigma_space), () or (decay,).  ``_flip``: a TAU; every code in front of the
+    denoiser that stands within it of a boundary takes the other side (neighbour_taint's second evaluation)."""
     raw = np.asarray(raw.cpu().numpy() if isinstance(raw, torch.Tensor) else raw)
     n, h, w = raw.shape
     assert phase in SITES and demosaic in DEMOSAIC and len(ops) == len(params)
@@ -304,6 +431,8 @@ def serve(raw, white, black, phase, demosaic, bilateral, ops, params, reverse=Fa
         if sync is not None:
             assert sync.points[k][0] == kind
             codes = sync.points[k][2]
+        if _flip is not None and tr.denoise_at is None:
+            codes = np.where(tie_distance(unq) <= _flip[kind], other_code(unq, codes), codes)
         return codes.astype(dtype) / dtype(255), codes, np.where(codes == 0, 1, np.where(codes == 255, 2, 0)).astype(np.int8)
 
     if demosaic == 'nearest':
@@ -327,8 +456,40 @@ def serve(raw, white, black, phase, demosaic, bilateral, ops, params, reverse=Fa
         val, codes, pin = quantise('bilateral', unq)
         tr.bilateral_windows = win
         pin_dist, last = np.full(val.shape, INF), None
-    for op, par in zip(ops, params):
+    stages = list(zip(ops, params))
+    if denoise is not None:
+        name, n_pre, args = denoise
+        assert bilateral is None and name in DENOISERS and 0 <= n_pre <= len(ops) and len(args) == {'bilateral': 2, 'median': 0, 'fastnlm': 1}[name]
+        pre, post = split_stages(stages, n_pre)
+        stages = list(pre) + [(name, args)] + list(post)
+    for op, par in stages:
         if op == OP_SKIP:
+            continue
+        if op in DENOISERS:
+            arg = [np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64).reshape(n) for a in par]
+            arg = [np.stack([image_params(a, i) for i in range(n)]) for a in arg]
+            # the pixels x 255; a carried code is its integer, whatever float stands for it
+            v = codes.astype(dtype) if codes is not None else val.astype(dtype) * dtype(255)
+            if op == 'median':
+                cin = codes
+                if cin is None:                             # a float in front: the median's input code is a quantisation point
+                    _, cin, _ = quantise('median-in/' + last, v)
+                tr.denoise_at = len(tr.points)
+                m = denoise_median(median_input(v, cin, dtype))
+                tr.denoise_out = (op, m)
+                # the middle of nine codes is a code, carried on (were it taken on floats it would be a float)
+                codes, last = (m.astype(np.int64), None) if np.array_equal(m, np.floor(m)) else (None, 'median')
+                val = m / dtype(255)
+                pin = np.where(m == 0, 1, np.where(m == 255, 2, 0)).astype(np.int8)
+            elif op == 'bilateral':
+                tr.denoise_at = len(tr.points)
+                val, codes, pin = quantise('den-bilateral', denoise_bilateral(v, arg[0], arg[1], dtype))
+                tr.denoise_out, last = (op, tr.points[-1][1]), None
+            else:
+                tr.denoise_at = len(tr.points)
+                val, codes, pin = quantise('fastnlm', denoise_fastnlm(v, arg[0], dtype))
+                tr.denoise_out, last = (op, tr.points[-1][1]), None
+            pin_dist = np.full(val.shape, INF)
             continue
         if par is not None:
             par = np.asarray(par.detach().cpu().numpy() if isinstance(par, torch.Tensor) else par, dtype=np.float64)
@@ -364,7 +525,45 @@ def serve(raw, white, black, phase, demosaic, bilateral, ops, params, reverse=Fa
     t = val.astype(np.float64) * 255.0 if dtype == np.float64 else (val * np.float32(255)).astype(np.float64)
     tr.final_t = np.where(pin != 0, np.nan, t) if codes is None else np.full(val.shape, np.nan)
     tr.final_pin = pin
+    if denoise is not None and _flip is None:
+        tr.rerun = lambda TAU: serve(raw, white, black, phase, demosaic, None, ops, params, reverse, denoise=denoise, _flip=TAU)
     return tr
+
+
+def other_code(unq, codes):
+    """the code on the other side of the boundary nearest to the unquantised value"""
+    return np.clip(np.where(unq >= codes, codes + 1, codes - 1), 0, 255)
+
+
+def neighbour_taint(tr, TAU):
+    """(N,H,W): pixels whose own points are decided but whose denoiser reads a neighbour that is not.  A denoiser mixes
+    pixels, so a code in front of it that may fall either way (within TAU of its boundary; the median's input code among
+    them) reaches every pixel of the footprint - 3 x 3 for the bilateral and the median, 5 x 5 for non-local means.  The
+    pipeline is evaluated a second time with every such code on its other side.  A pixel with ONE such code in its
+    footprint has exactly the two outcomes that the two evaluations hold: it stays decided when they give the denoiser the
+    same code, the second one also further than TAU from a boundary (the median: the same middle code).  A pixel with two or
+    more in its footprint (a reflected neighbour counts twice) is excused without looking"""
+    key = tuple(sorted(TAU.items()))
+    if tr.taint is None or tr.taint[0] != key:
+        name, out = tr.denoise_out
+        near = [(tie_distance(unq) <= TAU[kind]).sum(axis=1) for kind, unq, _ in tr.points[:tr.denoise_at]]
+        mask = np.zeros(out.shape[:1] + out.shape[2:], bool)
+        tr.taint_distance = np.full(mask.shape, INF)        # of the nearest boundary among the codes the denoiser reads (the report's)
+        if near and sum(near).any():
+            other = tr.rerun(TAU).denoise_out[1]
+            r = 2 if name == 'fastnlm' else 1
+            window = [(dy, dx) for dy in range(-r, r + 1) for dx in range(-r, r + 1)]
+            tap = _taps(sum(near)[:, None])
+            foot = sum(tap(dy, dx) for dy, dx in window)[:, 0]
+            tap = _taps(np.minimum.reduce([tie_distance(unq).min(axis=1) for _, unq, _ in tr.points[:tr.denoise_at]])[:, None])
+            tr.taint_distance = np.minimum.reduce([tap(dy, dx) for dy, dx in window])[:, 0]
+            if name == 'median':
+                moved = (out != other).any(axis=1)
+            else:
+                moved = (code(out) != code(other)).any(axis=1) | (tie_distance(other).min(axis=1) <= TAU[tr.points[tr.denoise_at][0]])
+            mask = (foot >= 2) | ((foot >= 1) & moved)
+        tr.taint = (key, mask)
+    return tr.taint[1]
 
 
 def taus(tr, TAU):
@@ -377,6 +576,8 @@ def taus(tr, TAU):
         else:
             tau = TAU[kind]
         decided &= tie_distance(unq).min(axis=1) > tau
+    if tr.denoise_at is not None:
+        decided &= ~neighbour_taint(tr, TAU)
     return decided, (TAU['final/' + tr.final_kind] if tr.final_kind else 0.0)
 
 
@@ -414,7 +615,8 @@ def check(got, tr, TAU):
     if loose_share > FINAL_CAP:
         bad.append('%.3e of the bytes under the +-1 rule (cap %.0e)' % (loose_share, FINAL_CAP))
     diff = d != 0
-    dist = np.where(dec, tr.final, np.broadcast_to(tr.inner[..., None], d.shape))
+    inner = tr.inner if tr.denoise_at is None else np.where(neighbour_taint(tr, TAU), np.minimum(tr.inner, tr.taint_distance), tr.inner)
+    dist = np.where(dec, tr.final, np.broadcast_to(inner[..., None], d.shape))
     report = dict(decided_differ=int((d[strict] != 0).sum()), decided_share=float((d[strict] != 0).sum() / d.size),
                   differ=int(diff.sum()), share=float(diff.mean()), worst=float(dist[diff].max()) if diff.any() else 0.0,
                   inner_share=float(inner_share), loose_share=float(loose_share))
@@ -426,23 +628,41 @@ STAGE_OPS = {'wbmanual': OP_WB_MANUAL, 'gamma': OP_GAMMA, 'gtmmanual': OP_GTM_MA
              'crysisengine': OP_TONE_CRYSIS, 'filmic': OP_TONE_FILMIC, 'skip': OP_SKIP}
 
 
-def plugin_stages(step_names, blocks):
+def plugin_stages(step_names, blocks, denoise=False):
     """a fixed pipeline's stage names and its per-image (N,P) parameters after the sigmoid -> (demosaic, bilateral, ops,
     params) as the C ABI takes them, by the mapping the modules apply (in float32, the type of the blocks): WbManual
     gain = 5 p; Filmic (white_point, exposure_bias) = (p0, 1 + 9 p1); Crysis lum_adapted = p0; bilateral window =
-    (int(p0) * 7) * 2 + 3, sigma_color = 1 + 99 p1, sigma_space = 1 + 99 p2; every other block is the parameter itself"""
+    (int(p0) * 7) * 2 + 3, sigma_color = 1 + 99 p1, sigma_space = 1 + 99 p2; every other block is the parameter itself.
+
+    ``denoise=True``: -> (demosaic, bilateral, ops, params, denoise) with ``denoise`` as ``serve`` takes it, for one classical
+    denoiser that is not the bilateral directly behind the nearest demosaic (pipeline_fusion._denoise_args): a bilateral as
+    above; median size = 2 int(7 p) + 3 of image 0; non-local means block = (int(p0) * 7) * 2 + 3, search the same of p1,
+    decay = 1 + 99 p2.  The sizes must be the ones the route serves: 3, 3 x 3, (3, 3)"""
     f = np.float32
-    demosaic, bilateral, ops, params = None, None, [], []
+    demosaic, bilateral, ops, params, den = None, None, [], [], None
     for name, p in zip(step_names, blocks):
         p = None if p is None else np.asarray(p, dtype=f)
         if name in DEMOSAIC:
             assert demosaic is None and not ops
             demosaic = name
-        elif name == 'bilateral':
-            assert demosaic == 'nearest' and not ops and bilateral is None
+        elif name == 'bilateral' and not (denoise and (demosaic != 'nearest' or ops)):
+            assert demosaic == 'nearest' and not ops and bilateral is None and den is None
             bilateral = ((p[:, 0].astype(np.int32) * 7) * 2 + 3, p[:, 1] * f(99) + f(1), p[:, 2] * f(99) + f(1))
+        elif name in DENOISERS:
+            assert denoise and demosaic is not None and bilateral is None and den is None
+            if name == 'bilateral':
+                assert ((p[:, 0].astype(np.int32) * 7) * 2 + 3 == 3).all()
+                den = (name, len(ops), (p[:, 1] * f(99) + f(1), p[:, 2] * f(99) + f(1)))
+            elif name == 'median':
+                assert 2 * int(p[0, 0] * 7) + 3 == 3
+                den = (name, len(ops), ())
+            else:
+                assert ((p[:, :2].astype(np.int32) * 7) * 2 + 3 == 3).all()
+                den = (name, len(ops), (p[:, 2] * f(99) + f(1),))
         else:
             op = STAGE_OPS[name]
+            if op == OP_SKIP and demosaic is None:          # a Skip on the mosaic, in front of the demosaic
+                continue
             ops.append(op)
             if op == OP_WB_MANUAL:
                 p = p * f(5)
@@ -451,4 +671,4 @@ def plugin_stages(step_names, blocks):
             elif op == OP_TONE_CRYSIS:
                 p = p[:, :1]
             params.append(p)
-    return demosaic, bilateral, ops, params
+    return (demosaic, bilateral, ops, params, den) if denoise else (demosaic, bilateral, ops, params)
