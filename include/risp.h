@@ -872,6 +872,41 @@ int risp_serve_scene_u8(const uint16_t *raw, float divisor, int demosaic, int n_
                         const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
                         int black_level, int cfa, void *stream);
 
+/* Conditional heads on the serving path (risp_serve_cond.hip): ConditionalGamma / ConditionalWbManual / ConditionalWbQuadratic
+ * predict their parameters per image with an MLP on the per-channel histogram of their input.  The mosaic is read once more
+ * per head instead of fp32 planes being written: a histogram launch, a finish launch, and risp_serve_classical_u8 serves with
+ * the head as RISP_OP_GAMMA / WB_MANUAL / WB_QUADRATIC and the finished block (2 S + 1 launches for S heads; the histogram
+ * launch of a later head runs its prefix through the earlier ones).
+ *
+ * risp_serve_cond_hist: risp_serve_classical_u8's pixel pipeline (same arguments, rules, loads, reflection, phase and black
+ * level) with the n_ops PREFIX stages; no image is stored.  Every value v behind the prefix - B, G, R of every pixel - is
+ * binned by risp_histc's rule: it counts only if v >= 0 && v <= 1 (NaN and values outside count nowhere), in bin
+ * min((int)(v * (float)bins), bins - 1).  counts is (N, RISP_COND_SHARDS, 3 * bins) unsigned 32-bit integers, channel order
+ * B, G, R: a workgroup (a 64 x 32 pixel tile) counts in private LDS histograms and adds its totals to shard
+ * tile % RISP_COND_SHARDS of its image with integer atomics, so no result depends on an order; the histogram of image n is the
+ * sum of its shards.  The entry point zeroes counts itself on the same stream (capturable): counts is fully defined after the
+ * call whatever it held before.  Rules (anything else is refused before a launch and the message names the value): raw and
+ * counts not NULL, raw 8-byte aligned, whole contiguous frames; divisor > 0; demosaic 0 .. 2; cfa 0 .. 3 and no mirrored axis
+ * of odd length; 0 <= black_level <= 65535; bins >= 1 and 3 * bins <= 1024 (the widest layer of risp_cond_fc_fwd);
+ * 1 <= N <= 65535, H even and >= 4, W % 4 == 0 and >= 4, H * W <= 2^24 (above it the float counts of risp_histc stop being
+ * exact and "the composed route's bytes" cannot be promised); 0 <= n_ops <= RISP_MAX_CHAIN, ops[k] one of SKIP, WB_MANUAL ..
+ * TONE_FILMIC as risp_serve_classical_u8 takes them, every stage but a SKIP needs params[k].
+ *
+ * risp_serve_cond_finish: one workgroup per image.  Word i of the image's `shards` rows of counts, added in integers and
+ * converted to float once, is the histogram risp_histc gives; then risp_cond_fc_fwd's arithmetic on flat / widths / n_layers
+ * (same expressions in the same order: z = sum_i a[i] W[i][j] in i order, + b[j], ReLU between layers, on the last layer
+ * + the global scalar and 1 / (1 + exp(-z))), and block[n][j] = that value * scale in fp32 (scale 1: the value itself; 5 for
+ * ConditionalWbManual).  block is (N, widths[n_layers]); no activation row is written.  Rules: counts, flat, block not NULL;
+ * 1 <= shards <= 65535; 1 <= N <= 65535; scale > 0 and finite; 1 <= n_layers <= 8, every width in 1 .. 1024; counts rows are
+ * widths[0] words long.  With both, the block - and every byte risp_serve_classical_u8 serves with it - is the composed
+ * route's (risp_raw_crop_cfa -> ... -> risp_histc -> risp_cond_fc_fwd -> * scale). */
+#define RISP_COND_SHARDS 32
+int risp_serve_cond_hist(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                         const float *const *params, int bins, unsigned int *counts, int N, int H, int W, int black_level,
+                         int cfa, void *stream);
+int risp_serve_cond_finish(const unsigned int *counts, int shards, const float *flat, const int *widths, int n_layers,
+                           float scale, float *block, int N, void *stream);
+
 /* A classical pipeline with ONE classical denoiser as an ISP, one launch (risp_serve_denoise.hip): raw (N,H,W) uint16 mosaic
  * of the sensor -> out (N,H,W,3) bytes.  Per pixel: risp_serve_classical_u8's input expression and demosaic, the n_pre stages
  * pre_ops, the denoiser, the n_post stages post_ops, the conversion of risp_quantise_u8.  Only the result is stored; its bytes

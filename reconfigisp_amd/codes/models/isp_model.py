@@ -124,11 +124,13 @@ class IspModel(BaseModel):
         return self.output, self.netG.intermediate_results
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False):
+              fast_denoise=False, fast_cond=False):
         """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
         describe the sensor; ``fast_scene=True`` opts gray-world / white-world / Reinhard pipelines in to the scene route,
         whose bytes agree with the float64 reference under its tie rule - white-world-only pipelines byte for byte;
         ``fast_denoise=True`` opts pipelines with one classical bilateral / median / non-local means in to the one-launch
-        denoise route, whose bytes are the default call's)."""
+        denoise route, whose bytes are the default call's; ``fast_cond=True`` opts pipelines with one to three conditional
+        heads in to the conditional route - one more read of the mosaic per head instead of fp32 planes -, whose bytes are
+        the default call's too)."""
         with torch.no_grad():
-            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise)
+            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond)

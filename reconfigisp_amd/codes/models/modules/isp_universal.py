@@ -43,7 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
-        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'composed': what the last serve() call ran
+        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'cond' | 'composed': what the last serve() call ran
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -94,7 +94,7 @@ class _FixedPipeline(nn.Module):
         return x
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False):
+              fast_denoise=False, fast_cond=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -113,11 +113,17 @@ class _FixedPipeline(nn.Module):
         ``fast_denoise=True`` opts a pipeline with one classical bilateral, median or non-local means behind a classical
         demosaic in to the ``'denoise'`` route (``pipeline_fusion.denoise_plan``; H even and >= 4, W % 4 == 0, learned sizes
         3 / 3 / (3, 3)): one launch with the composed route's bytes.  Where the route does not apply the call runs as
-        without the flag."""
+        without the flag.
+
+        ``fast_cond=True`` opts a pipeline with one to three conditional heads (ConditionalGamma / ConditionalWbManual /
+        ConditionalWbQuadratic) among element-wise stages and Crysis / Filmic curves behind a classical demosaic in to the
+        ``'cond'`` route (``pipeline_fusion.cond_plan``; H even and >= 4, W % 4 == 0, H * W <= 2^24): 2 S + 1 launches for S
+        heads, the mosaic read again per histogram instead of fp32 planes written, with the composed route's bytes.  Where
+        the route does not apply the call runs as without the flag."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa, fast_scene, fast_denoise)
+                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond)
         return out
 
     @property

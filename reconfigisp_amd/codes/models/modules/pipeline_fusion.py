@@ -282,6 +282,66 @@ def _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channel
     return F.serve_scene_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa)
 
 
+MAX_COND_HEADS = 3         # one head of each kind; every head costs one more read of the mosaic
+
+
+def cond_plan(modules):
+    """(demosaic kind, indices of the stages, which of them are conditional heads) when ``serve(fast_cond=True)`` can take the
+    conditional route for this module list (a pure function of it): Skips stripped, a nearest, classical bilinear or classical
+    Malvar-He-Cutler demosaic followed by at most MAX_CHAIN stages, each an element-wise one, a classical Crysis / Filmic tone
+    curve or one of the heads ConditionalGamma, ConditionalWbManual, ConditionalWbQuadratic, with one to MAX_COND_HEADS heads
+    among them.  None otherwise: without a head ``serve_route`` already names a one-launch route; a scene stage, a classical
+    denoiser or BM3D, a CNN stage or a proxy demosaic beside a head keeps the list where it is today."""
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+        return None
+    rest = idx[1:]
+    kinds = [type(modules[k]) for k in rest]
+    if len(rest) > MAX_CHAIN or any(t not in _CHAIN_OP and t not in _TONE_OP and t not in _COND_OP for t in kinds):
+        return None
+    heads = [t in _COND_OP for t in kinds]
+    if not 1 <= sum(heads) <= MAX_COND_HEADS:
+        return None
+    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], rest, heads
+
+
+def _cond_heads_ok(plan, modules, param_tensors):
+    """whether every head of the plan is one the kernels take: 3 * bins and the layer widths within risp_cond_fc_fwd's limits,
+    and the flat vector what ``_fc_forward`` expects (anything else is the composed route's to refuse)"""
+    for k, is_head in zip(plan[1], plan[2]):
+        if is_head:
+            mod, par = modules[k], param_tensors[k]
+            if not F.cond_widths_ok(mod.in_out_channels):
+                return False
+            if (not torch.is_tensor(par) or not par.is_cuda or par.dtype != torch.float32 or par.dim() != 1
+                    or not par.is_contiguous() or par.numel() != mod.total_params):
+                return False
+    return True
+
+
+def _serve_cond(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa):
+    """2 S + 1 launches for S heads: per head the histogram of its input (the mosaic read again, the pipeline evaluated up to
+    the head, earlier heads with their blocks) and the finish launch on the head's raw flat vector, then the classical serving
+    launch with every head as its element-wise op"""
+    kind, stages, heads = plan
+    ops, params, s = [], [], 0
+    for k, is_head in zip(stages, heads):
+        mod, par = modules[k], param_tensors[k]
+        t = type(mod)
+        if is_head:
+            counts = F.serve_cond_hist(raw_u16, divisor, kind, ops, params, mod.hist_bin, None, black_level, cfa, tag=s)
+            params.append(F.serve_cond_finish(counts, par.detach(), mod.in_out_channels, _COND_OP[t][1], None, tag=s))
+            ops.append(_COND_OP[t][0])
+            s += 1
+        elif t in _TONE_OP:
+            ops.append(_TONE_OP[t])
+            params.append(_tone_block(mod, par))
+        else:
+            ops.append(_CHAIN_OP[t])
+            params.append(_chain_param(mod, par))
+    return F.serve_classical_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa)
+
+
 _DENOISER = {T.OriginNoiseBilateral: 'bilateral', T.OriginNoiseMedian: 'median', T.OriginNoiseFastnlm: 'fastnlm'}
 
 
@@ -337,7 +397,7 @@ def _stage_lists(modules, param_tensors, stages):
 
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
-          fast_scene=False, fast_denoise=False):
+          fast_scene=False, fast_denoise=False, fast_cond=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -360,6 +420,16 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     it.  The bytes are the composed route's (``torch.equal``); the keyword exists because the default call's route is pinned by
     tests.  The denoiser's arguments are derived once per parameter version: with ``out`` given a warm call launches once,
     allocates nothing and never waits for the device.
+
+    ``fast_cond=True`` opts in to the ``'cond'`` route where ``cond_plan`` is not None - one to three conditional heads among
+    element-wise stages and Crysis / Filmic curves behind a classical demosaic -, the geometry is the classical route's,
+    H * W <= 2^24 and every head has 3 * bins <= 1024 and layer widths within ``risp_cond_fc_fwd``'s limits; otherwise the call
+    runs exactly as without it.  Per head the mosaic is read once more: ``risp_serve_cond_hist`` bins the head's input into
+    integer counts, ``risp_serve_cond_finish`` runs the head's MLP on them, and ``risp_serve_classical_u8`` serves with every
+    head as its element-wise op - 2 S + 1 launches (and S capturable memsets) for S heads, no fp32 plane written.  Counts are
+    integers and have no summation order, so the bytes are the composed route's (``torch.equal``); the keyword exists because
+    the default call's route is pinned by tests.  The head's flat vector is read by the finish launch on every call: with
+    ``out`` given a warm call allocates nothing and never waits for the device.
 
     ``black_level`` (integer, 0 <= black_level < white_level) and ``cfa`` ('rggb' | 'grbg' | 'gbrg' | 'bggr') describe the
     sensor: the input becomes max(raw - black_level, 0) / (white_level - black_level) and the mosaic of another phase is
@@ -389,6 +459,11 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
             post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
             return F.serve_denoise_u8(raw_u16, divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
                                       reverse_channels, out, black_level, cfa), 'denoise'
+    if (fast_cond and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0
+            and h * w <= 1 << 24):
+        plan = cond_plan(modules)
+        if plan is not None and _cond_heads_ok(plan, modules, param_tensors):
+            return _serve_cond(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa), 'cond'
     split = _serve_split(modules)
     if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         bil, chain = split

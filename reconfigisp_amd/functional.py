@@ -704,15 +704,16 @@ _scene_scratch = {}
 
 
 def release_scene_scratch():
-    """Drop the cached partials and constants of the scene route (every device and stream)."""
+    """Drop the cached partials and constants of the scene route and the cached counts and blocks of the conditional route
+    (every device and stream)."""
     _scene_scratch.clear()
 
 
-def _scene_buffer(device, tag, shape):
+def _scene_buffer(device, tag, shape, dtype=torch.float32):
     key = (device, _stream().value, tag, tuple(shape))
     buf = _scene_scratch.get(key)
     if buf is None:
-        buf = _scene_scratch[key] = torch.empty(shape, device=device, dtype=torch.float32)
+        buf = _scene_scratch[key] = torch.empty(shape, device=device, dtype=dtype)
     return buf
 
 
@@ -798,6 +799,85 @@ def serve_scene_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels=Fal
     L.call('risp_serve_scene_u8', _p(raw_u16), float(divisor), kind, len(ops), oparr, blocks, _p(out), int(bool(reverse_channels)),
            n, h, w, int(black_level), code, _stream())
     return out
+
+
+COND_SHARDS = 32           # RISP_COND_SHARDS: rows of counts per image, which serve_cond_finish adds
+COND_MAX_WIDTH, COND_MAX_LAYERS = 1024, 8      # the limits of risp_cond_fc_fwd and risp_serve_cond_finish
+
+
+def serve_cond_hist(raw_u16, divisor, demosaic, ops, params, bins, counts=None, black_level=0, cfa='rggb', tag=0):
+    """The histogram launch of the conditional route (``risp_serve_cond_hist``): ``serve_classical_u8``'s pixel pipeline with
+    the PREFIX stages ``ops`` / ``params`` in front of a conditional head, binned with ``histc01``'s rule (a value counts only
+    inside [0,1], 1 lands in the last bin) into ``counts`` (N, COND_SHARDS, 3 * bins) int32, channel order B, G, R.  No image
+    is stored.  The histogram of image n is ``counts[n].sum(0)``: integers throughout, so ``histc01`` of the composed
+    intermediate exactly.  The call zeroes ``counts`` itself.  An earlier head joins the prefix as its element-wise op with
+    the block of its ``serve_cond_finish``.  H even and >= 4, W % 4 == 0, H * W <= 2^24, 3 * bins <= 1024.  ``counts`` None: a
+    buffer cached per device, stream, ``tag`` and shape."""
+    kind, code, keep, oparr, blocks = _scene_frame_args(raw_u16, demosaic, ops, params, black_level, cfa)
+    if bins != int(bins) or not 1 <= bins or 3 * bins > COND_MAX_WIDTH:
+        raise ValueError('bins %r: an integer with 1 <= bins and 3 * bins <= %d' % (bins, COND_MAX_WIDTH))
+    n, h, w = raw_u16.shape
+    serve_scene_groups(h, w)
+    if n > 65535:
+        raise ValueError('%d frames: at most 65535 in one call' % n)
+    if h * w > 1 << 24:
+        raise ValueError('a %d x %d frame has more than 2^24 pixels: float counts stop being exact' % (h, w))
+    shape = (n, COND_SHARDS, 3 * int(bins))
+    if counts is None:
+        counts = _scene_buffer(raw_u16.device, ('cond_counts', tag), shape, torch.int32)
+    elif (counts.dtype != torch.int32 or tuple(counts.shape) != shape or not counts.is_contiguous()
+          or counts.device != raw_u16.device):
+        raise ValueError('counts must be a contiguous int32 %s tensor on %s' % (shape, raw_u16.device))
+    L.call('risp_serve_cond_hist', _p(raw_u16), float(divisor), kind, len(ops), oparr, blocks, int(bins), _p(counts), n, h, w,
+           int(black_level), code, _stream())
+    return counts
+
+
+def cond_widths_ok(widths):
+    """whether ``serve_cond_finish`` (and ``conditional_fc``) takes these layer widths: 1 .. 8 layers, every width in
+    1 .. 1024, the first a multiple of 3"""
+    widths = list(widths)
+    return (2 <= len(widths) <= COND_MAX_LAYERS + 1 and all(int(v) == v and 1 <= v <= COND_MAX_WIDTH for v in widths)
+            and widths[0] % 3 == 0)
+
+
+def cond_param_count(widths):
+    """entries of the flat vector the layers and the global scalar need"""
+    return sum(widths[i] * widths[i + 1] + widths[i + 1] for i in range(len(widths) - 1)) + 1
+
+
+def serve_cond_finish(counts, flat, widths, scale, block=None, tag=0):
+    """``counts`` (N, shards, widths[0]) of ``serve_cond_hist`` -> the head's per-image block (``risp_serve_cond_finish``): the
+    shards added in integers, ``conditional_fc``'s MLP on ``flat`` / ``widths`` (same arithmetic, no activations kept), then
+    ``* scale`` in fp32 (1: nothing; 5 for ConditionalWbManual).  Returns (N, widths[-1]) float32, bit for bit
+    ``conditional_fc(x, flat, widths) * scale`` of the image ``counts`` was taken from.  ``block`` None: a buffer cached per
+    device, stream, ``tag`` and shape."""
+    _need_gpu(counts, 'counts')
+    if counts.dtype != torch.int32 or counts.dim() != 3 or not counts.is_contiguous():
+        raise ValueError('expected contiguous int32 (N,shards,3*bins) counts, got %s %s' % (counts.dtype, tuple(counts.shape)))
+    widths = [int(v) for v in widths]
+    if not cond_widths_ok(widths):
+        raise ValueError('widths %r: 2 .. %d entries in 1 .. %d, the first a multiple of 3'
+                         % (widths, COND_MAX_LAYERS + 1, COND_MAX_WIDTH))
+    n, shards, w0 = counts.shape
+    if w0 != widths[0]:
+        raise ValueError('counts rows hold %d words but the first layer takes %d' % (w0, widths[0]))
+    _need_gpu(flat, 'params')
+    if flat.dtype != torch.float32 or flat.dim() != 1 or not flat.is_contiguous() or flat.device != counts.device:
+        raise ValueError('params must be a contiguous float32 vector on %s, got %s %s' % (counts.device, flat.dtype, tuple(flat.shape)))
+    if flat.numel() < cond_param_count(widths):
+        raise ValueError('%d parameters, the layers %r need %d' % (flat.numel(), widths, cond_param_count(widths)))
+    scale = float(scale)
+    if not 0.0 < scale < float('inf'):
+        raise ValueError('scale %r: a positive finite number' % (scale,))
+    shape = (n, widths[-1])
+    if block is None:
+        block = _scene_buffer(counts.device, ('cond_block', tag), shape)
+    elif block.dtype != torch.float32 or tuple(block.shape) != shape or not block.is_contiguous() or block.device != counts.device:
+        raise ValueError('block must be a contiguous float32 %s tensor on %s' % (shape, counts.device))
+    L.call('risp_serve_cond_finish', _p(counts), shards, _p(flat), (C.c_int * len(widths))(*widths), len(widths) - 1, scale,
+           _p(block), n, _stream())
+    return block
 
 
 class _FanOut(torch.autograd.Function):
