@@ -933,6 +933,51 @@ int risp_serve_denoise_u8(const uint16_t *raw, float divisor, int demosaic, int 
                           const float *den_b, int n_post, const int *post_ops, const float *const *post_params, uint8_t *out,
                           int reverse_channels, int N, int H, int W, int black_level, int cfa, void *stream);
 
+/* A classical denoiser beside gray-world / white-world on the serving path (risp_serve_denoise_scene.hip): the statistic of an
+ * image that lies BEHIND a denoiser, and a serving launch that takes a denoiser and the scene constants together.  With
+ * risp_serve_scene_stats (a scene stage whose prefix holds no denoiser) and risp_serve_scene_finish a pipeline with S scene stages
+ * and one denoiser runs in 2 S + 1 launches and writes no fp32 plane.
+ *
+ * risp_serve_denoise_stats: risp_serve_denoise_u8's tile pipeline (same arguments, rules, loads, mosaic reflection, image-border
+ * reflection, phase, black level, two-phase LDS tile of 31104 bytes) with the n_post stages behind the denoiser evaluated in
+ * registers; no image is stored.  The values behind the last post stage are reduced per workgroup (a 64 x 32 pixel tile)
+ * according to stat:
+ *   RISP_SCENE_MEAN3   the sums of B, G, R of the [0,1] values        (gray-world)
+ *   RISP_SCENE_MAX3    the maxima of B, G, R                          (white-world)
+ * in risp_serve_scene_stats' order (the thread's eight pixels in row order, wavefront shuffles, one LDS step in wave order; no
+ * atomics; a thread of a ragged tile that owns no pixel holds 0 for a sum and -inf for a maximum), and workgroup `tile` of image n
+ * writes the row partials[(n * G + tile) * 4 .. + 3] = (B, G, R, 0), G = risp_serve_scene_groups(H, W), tile = row-major index of
+ * the tiles of the mirrored (RGGB) image: exactly the layout of risp_serve_scene_stats, every row written in full, and
+ * risp_serve_scene_finish turns the rows into constants unchanged.  RISP_SCENE_LOGLUM is refused.
+ *
+ * risp_serve_denoise_scene_u8: risp_serve_denoise_u8 - signature, rules, bytes for every stage both accept - with one more stage
+ * accepted in front of and behind the denoiser:
+ *   RISP_OP_GAIN3_Q8   white-world apply, the expression risp_serve_scene_u8 has: the value times its channel's gain, rounded to
+ *                      its 8-bit code / 255; its parameter block is the 16-byte aligned MAX3 consts of risp_serve_scene_finish
+ * Gray-world applies as the existing RISP_OP_GAIN3 with the MEAN3 consts.  RISP_OP_TONE_REINHARD is refused by both entry points
+ * (its log-average has no order-free form and its apply step no stand-alone entry point to be held to).  The prefix of
+ * risp_serve_denoise_stats accepts RISP_OP_GAIN3_Q8 too: an earlier scene stage enters it with its constants.
+ *
+ * Contract.  Given the constants, the bytes are those of the composed route evaluated with the same constants
+ * (risp_raw_crop_cfa -> demosaic -> stages -> risp_origin_* -> stages -> risp_quantise_u8_flip, gray-world as risp_gain3_fwd and
+ * white-world as risp_origin_tonemap mode 3 at their places).  A maximum has no order: MAX3 rows, white-world's constants and the
+ * bytes of a pipeline whose only scene stages are white-world are the composed route's.  A sum taken in this order differs from
+ * risp_channel_stats' in its last bits: a MEAN3 row lies within (64 * 32 - 1) * 2^-24 * sum|x| of the exact sum of its tile.
+ *
+ * Rules for both (anything else is refused before a launch and the message names the value): those of risp_serve_denoise_u8 -
+ * bilateral window 3, median size 3, non-local means block 3 and search 3, the denoiser's parameter blocks; H even and >= 4,
+ * W % 4 == 0 and >= 4, 1 <= N <= 65535; n_pre + n_post <= RISP_MAX_CHAIN; every stage but a SKIP needs its parameter block; raw
+ * 8-byte aligned; divisor > 0; demosaic 0 .. 2; denoise 0 .. 2; cfa 0 .. 3; 0 <= black_level <= 65535 - plus stat MEAN3 or MAX3 and
+ * partials not NULL and 16-byte aligned (the statistics), out not NULL and 4-byte aligned (the serving launch). */
+int risp_serve_denoise_stats(const uint16_t *raw, float divisor, int demosaic, int n_pre, const int *pre_ops,
+                             const float *const *pre_params, int denoise, int window, int search, const float *den_a,
+                             const float *den_b, int n_post, const int *post_ops, const float *const *post_params, int stat,
+                             float *partials, int N, int H, int W, int black_level, int cfa, void *stream);
+int risp_serve_denoise_scene_u8(const uint16_t *raw, float divisor, int demosaic, int n_pre, const int *pre_ops,
+                                const float *const *pre_params, int denoise, int window, int search, const float *den_a,
+                                const float *den_b, int n_post, const int *post_ops, const float *const *post_params, uint8_t *out,
+                                int reverse_channels, int N, int H, int W, int black_level, int cfa, void *stream);
+
 /* Diagnostics: the kernel instance risp_bilateral_chain_fwd launches for these arguments (16-byte aligned input), named as rocprofv3 prints it
  * (bench.py binds the committed counter readings of profiles/traffic.json to the kernel it actually launches). */
 const char *risp_bilateral_chain_kernel(int from_bayer, int max_window, int with_wb_quadratic);

@@ -124,13 +124,16 @@ class IspModel(BaseModel):
         return self.output, self.netG.intermediate_results
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False):
+              fast_denoise=False, fast_cond=False, fast_denoise_scene=False):
         """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
         describe the sensor; ``fast_scene=True`` opts gray-world / white-world / Reinhard pipelines in to the scene route,
         whose bytes agree with the float64 reference under its tie rule - white-world-only pipelines byte for byte;
         ``fast_denoise=True`` opts pipelines with one classical bilateral / median / non-local means in to the one-launch
         denoise route, whose bytes are the default call's; ``fast_cond=True`` opts pipelines with one to three conditional
         heads in to the conditional route - one more read of the mosaic per head instead of fp32 planes -, whose bytes are
-        the default call's too)."""
+        the default call's too; ``fast_denoise_scene=True`` opts pipelines with one such denoiser AND one or two of gray-world /
+        white-world in to the denoise + scene route - white-world-only lists byte for byte, gray-world with the composed route's
+        bytes for its own gains, which differ from the composed route's within the summation bound)."""
         with torch.no_grad():
-            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond)
+            return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond,
+                                        fast_denoise_scene)

@@ -94,7 +94,7 @@ class _FixedPipeline(nn.Module):
         return x
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False):
+              fast_denoise=False, fast_cond=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -119,11 +119,18 @@ class _FixedPipeline(nn.Module):
         ConditionalWbQuadratic) among element-wise stages and Crysis / Filmic curves behind a classical demosaic in to the
         ``'cond'`` route (``pipeline_fusion.cond_plan``; H even and >= 4, W % 4 == 0, H * W <= 2^24): 2 S + 1 launches for S
         heads, the mosaic read again per histogram instead of fp32 planes written, with the composed route's bytes.  Where
-        the route does not apply the call runs as without the flag."""
+        the route does not apply the call runs as without the flag.
+
+        ``fast_denoise_scene=True`` opts a pipeline with one classical bilateral, median or non-local means AND one or two of
+        gray-world / white-world behind a classical demosaic in to the ``'denoise_scene'`` route
+        (``pipeline_fusion.denoise_scene_plan``; H even and >= 4, W % 4 == 0, learned sizes 3 / 3 / (3, 3)): 2 S + 1 launches
+        for S scene stages, no fp32 plane written.  White-world-only lists keep the default call's bytes; with gray-world the
+        bytes are the composed route's for the same gains, and the gains are within the summation bound of the composed
+        route's.  Where the route does not apply the call runs as without the flag."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond)
+                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond, fast_denoise_scene)
         return out
 
     @property

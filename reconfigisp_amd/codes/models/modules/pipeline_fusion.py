@@ -396,8 +396,81 @@ def _stage_lists(modules, param_tensors, stages):
     return ops, params
 
 
+_DENOISE_SCENE_STAT = {T.Grayworld: F.SCENE_MEAN3, T.OriginWbWhiteworld: F.SCENE_MAX3}
+# (denoiser, where the scene stages lie: 'front' | 'behind' | 'both') combinations that tools/bench_serve_denoise_scene.py found no
+# faster than the default call at one of its two sizes (profiles/serve_denoise_scene.txt): the plan leaves them where they are.
+# A scene stage behind non-local means costs a second run of the denoiser, which is compute bound: at 64 x 256 x 256 the route
+# took 193.1 us against 161.6 us composed (gray-world behind) and 213.1 against 192.1 (one scene stage each side); at
+# 1 x 3000 x 4000 it won (522.7 against 753.9 us, 582.2 against 811.9), but the rule asks for both sizes
+_DENOISE_SCENE_SLOWER = frozenset({('fastnlm', 'behind'), ('fastnlm', 'both')})
+
+
+def denoise_scene_plan(modules):
+    """(demosaic kind, indices of the stages around the denoiser in pipeline order, index of the denoiser, which of the stages
+    are scene stages) when ``serve(fast_denoise_scene=True)`` can take the denoise + scene route for this module list (a pure
+    function of it): Skips stripped, a nearest, classical bilinear or classical Malvar-He-Cutler demosaic followed by at most
+    MAX_CHAIN stages and exactly one of OriginNoiseBilateral / OriginNoiseMedian / OriginNoiseFastnlm; one or two of the stages
+    are Grayworld / OriginWbWhiteworld, at any position relative to the denoiser, every other stage an element-wise one or a
+    classical Crysis / Filmic tone curve.  None otherwise: a Reinhard stage anywhere (its log-average has no order-free form
+    and its apply step no entry point to be held to), two denoisers, three scene stages, BM3D, CNN stages, proxies,
+    conditional heads - and lists without a scene stage (``denoise_plan``'s) or without a denoiser (``scene_plan``'s), so the
+    plan is disjoint from every other.  None as well for non-local means with a scene stage behind it, which was measured
+    slower than the default call at 64 x 256 x 256 (``_DENOISE_SCENE_SLOWER``); the kernels serve it all the same."""
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+        return None
+    rest = idx[1:]
+    den = [k for k in rest if type(modules[k]) in _DENOISER]
+    if len(den) != 1:
+        return None
+    stages = [k for k in rest if k != den[0]]
+    kinds = [type(modules[k]) for k in stages]
+    if len(stages) > MAX_CHAIN or any(t not in _CHAIN_OP and t not in _TONE_OP and t not in _DENOISE_SCENE_STAT for t in kinds):
+        return None
+    scene = [t in _DENOISE_SCENE_STAT for t in kinds]
+    if not 1 <= sum(scene) <= 2:
+        return None
+    sides = {k < den[0] for k, s in zip(stages, scene) if s}
+    where = 'both' if len(sides) == 2 else ('front' if True in sides else 'behind')
+    if (_DENOISER[type(modules[den[0]])], where) in _DENOISE_SCENE_SLOWER:
+        return None
+    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], stages, den[0], scene
+
+
+def _serve_denoise_scene(plan, den_args, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa):
+    """2 S + 1 launches for S scene stages: per scene stage the statistics of its input - ``risp_serve_scene_stats`` while the
+    denoiser lies behind the stage, ``risp_serve_denoise_stats`` once it lies in the stage's prefix; earlier scene stages enter
+    the prefix with their constants - and the finish launch, then ``risp_serve_denoise_scene_u8`` serves"""
+    kind, stages, den, scene = plan
+    h, w = raw_u16.shape[1:]
+    pre, post, s = ([], []), ([], []), 0
+    for k, is_scene in zip(stages, scene):
+        mod, par = modules[k], param_tensors[k]
+        t = type(mod)
+        ops, params = pre if k < den else post
+        if is_scene:
+            stat = _DENOISE_SCENE_STAT[t]
+            if k < den:
+                parts = F.serve_scene_stats(raw_u16, divisor, kind, ops, params, stat, None, black_level, cfa)
+            else:
+                parts = F.serve_denoise_stats(raw_u16, divisor, kind, pre[0], pre[1], den_args[0], den_args[1], ops, params, stat,
+                                              None, black_level, cfa)
+            a, b = _scene_vectors(mod, par)
+            params.append(F.serve_scene_finish(stat, parts, h * w, a, b, None, tag=s))
+            ops.append(_SCENE_OP[t])
+            s += 1
+        elif t in _TONE_OP:
+            ops.append(_TONE_OP[t])
+            params.append(_tone_block(mod, par))
+        else:
+            ops.append(_CHAIN_OP[t])
+            params.append(_chain_param(mod, par))
+    return F.serve_denoise_scene_u8(raw_u16, divisor, kind, pre[0], pre[1], den_args[0], den_args[1], post[0], post[1],
+                                    reverse_channels, out, black_level, cfa)
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
-          fast_scene=False, fast_denoise=False, fast_cond=False):
+          fast_scene=False, fast_denoise=False, fast_cond=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -431,6 +504,21 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     the default call's route is pinned by tests.  The head's flat vector is read by the finish launch on every call: with
     ``out`` given a warm call allocates nothing and never waits for the device.
 
+    ``fast_denoise_scene=True`` opts in to the ``'denoise_scene'`` route where ``denoise_scene_plan`` is not None - one
+    classical bilateral, median or non-local means together with one or two of gray-world / white-world, anywhere behind a
+    classical demosaic -, the geometry is the classical route's and the learned parameters give the sizes the denoise route
+    serves; otherwise the call runs exactly as without it.  Per scene stage the mosaic is read once more for the statistic of
+    the stage's input (``risp_serve_scene_stats`` in front of the denoiser, ``risp_serve_denoise_stats`` - the denoise route's
+    tile pipeline, reduced instead of stored - behind it) and ``risp_serve_scene_finish`` forms its constants; then
+    ``risp_serve_denoise_scene_u8`` serves: 2 S + 1 launches for S scene stages, no fp32 plane written; with ``out`` given and
+    a warm cache the call allocates nothing and never waits for the device.  The contract, every part checkable exactly: a
+    maximum has no order, so a list whose only scene stages are white-world has the default call's bytes (``torch.equal``);
+    gray-world sums in another order than ``risp_channel_stats``, so (a) given the constants, the bytes are those of the
+    composed route evaluated with the same constants, and (b) the constants are within the summation bound of the composed
+    route's.  Which is why the route is opt-in, as ``fast_scene`` is.  The plan leaves non-local means with a scene stage behind
+    it on the default route: there the route runs the denoiser twice and was measured slower at 64 x 256 x 256
+    (profiles/serve_denoise_scene.txt).
+
     ``black_level`` (integer, 0 <= black_level < white_level) and ``cfa`` ('rggb' | 'grbg' | 'gbrg' | 'bggr') describe the
     sensor: the input becomes max(raw - black_level, 0) / (white_level - black_level) and the mosaic of another phase is
     read mirrored - which makes it RGGB for every stage, learned ones included - and the image stored un-mirrored.  No
@@ -459,6 +547,12 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
             post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
             return F.serve_denoise_u8(raw_u16, divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
                                       reverse_channels, out, black_level, cfa), 'denoise'
+    if fast_denoise_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+        plan = denoise_scene_plan(modules)
+        args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
+        if args is not None:
+            return _serve_denoise_scene(plan, args, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level,
+                                        cfa), 'denoise_scene'
     if (fast_cond and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0
             and h * w <= 1 << 24):
         plan = cond_plan(modules)

@@ -801,6 +801,88 @@ def serve_scene_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels=Fal
     return out
 
 
+def _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params, black_level, cfa):
+    """what ``serve_denoise_u8`` checks and forms, for the two launches that take a denoiser and scene constants together:
+    (leading C arguments through post_params, CFA code, the tensors to keep alive across the call)"""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(pre_ops) != len(pre_params) or len(post_ops) != len(post_params):
+        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(pre_ops), len(post_ops), len(pre_params), len(post_params)))
+    code_d = DEMOSAIC.get(kind) if isinstance(kind, str) else None
+    if code_d is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (kind, ', '.join(DEMOSAIC)))
+    code_n = DENOISE.get(denoise) if isinstance(denoise, str) else None
+    if code_n is None:
+        raise ValueError('unknown denoiser %r: one of %s' % (denoise, ', '.join(DENOISE)))
+    if len(denoise_args) != (3, 1, 3)[code_n]:
+        raise ValueError('%s takes %d arguments, got %d' % (denoise, (3, 1, 3)[code_n], len(denoise_args)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = raw_u16.shape
+    _check_mirror(code, h, w)
+    window, search, vecs = int(denoise_args[0]), 0, []
+    if code_n == 0:
+        vecs = list(denoise_args[1:])
+    elif code_n == 2:
+        search, vecs = int(denoise_args[1]), [denoise_args[2]]
+    for v in vecs:
+        if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != (n,) or not v.is_contiguous():
+            raise ValueError('%s takes contiguous float32 (%d,) device tensors for its per-image values' % (denoise, n))
+    pre = [_dev(p) if p is not None else None for p in pre_params]
+    post = [_dev(p) if p is not None else None for p in post_params]
+    args = (code_d, len(pre_ops), (C.c_int * max(1, len(pre_ops)))(*pre_ops),
+            L.ptr_array([p.data_ptr() if p is not None else None for p in pre] or [None]), code_n, window, search,
+            _p(vecs[0]) if vecs else None, _p(vecs[1]) if len(vecs) > 1 else None, len(post_ops),
+            (C.c_int * max(1, len(post_ops)))(*post_ops), L.ptr_array([p.data_ptr() if p is not None else None for p in post] or [None]))
+    return args, code, (pre, post, vecs)
+
+
+def serve_denoise_stats(raw_u16, divisor, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params, stat,
+                        partials=None, black_level=0, cfa='rggb', tag=0):
+    """The statistics launch of a scene stage that lies BEHIND a denoiser (``risp_serve_denoise_stats``):
+    ``serve_denoise_u8``'s tile pipeline - same frames, demosaic ``kind``, ``pre_ops`` / ``pre_params``, ``denoise`` /
+    ``denoise_args`` (sizes 3 / 3 / (3, 3) only), ``post_ops`` / ``post_params`` - with the values behind the last post stage
+    reduced per 64 x 32 pixel tile according to ``stat`` - SCENE_MEAN3 (sums of B, G, R) or SCENE_MAX3 (maxima); SCENE_LOGLUM
+    is refused - into ``partials`` (N, serve_scene_groups(H, W), 4) float32 in ``serve_scene_stats``' layout, every row
+    written, which ``serve_scene_finish`` takes unchanged.  No image is stored.  Either stage list may hold OP_GAIN3 /
+    OP_GAIN3_Q8 with the constants of an earlier ``serve_scene_finish``; OP_TONE_REINHARD is refused.  MAX3 rows are the
+    maxima of the composed route's plane exactly; a MEAN3 row lies within (64 * 32 - 1) * 2^-24 * sum|x| of its tile's exact
+    sum.  ``partials`` None: a buffer cached per device, stream, ``tag`` and shape."""
+    args, code, keep = _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+                                           black_level, cfa)
+    if stat not in (SCENE_MEAN3, SCENE_MAX3):
+        raise ValueError('stat %r: SCENE_MEAN3 or SCENE_MAX3 (a log-average is not served behind a denoiser)' % (stat,))
+    n, h, w = raw_u16.shape
+    shape = (n, serve_scene_groups(h, w), 4)
+    if partials is None:
+        partials = _scene_buffer(raw_u16.device, ('partials', tag), shape)
+    elif (partials.dtype != torch.float32 or tuple(partials.shape) != shape or not partials.is_contiguous()
+          or partials.device != raw_u16.device):
+        raise ValueError('partials must be a contiguous float32 %s tensor on %s' % (shape, raw_u16.device))
+    L.call('risp_serve_denoise_stats', _p(raw_u16), float(divisor), *args, int(stat), _p(partials), n, h, w, int(black_level),
+           code, _stream())
+    return partials
+
+
+def serve_denoise_scene_u8(raw_u16, divisor, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+                           reverse_channels=False, out=None, black_level=0, cfa='rggb'):
+    """``serve_denoise_u8`` with one more stage accepted in front of and behind the denoiser
+    (``risp_serve_denoise_scene_u8``): OP_GAIN3_Q8, white-world's apply step, whose block is the (N,4) constants
+    ``serve_scene_finish`` gives for SCENE_MAX3; gray-world applies as OP_GAIN3 with that function's (N,3) gains.
+    OP_TONE_REINHARD is refused.  Same frames, rules and - for every stage both accept - bytes as ``serve_denoise_u8``;
+    given the constants, the bytes are those of the composed route evaluated with the same constants (``chain_forward`` with
+    OP_GAIN3, ``origin_whiteworld`` at their places).  With ``out`` given nothing is allocated and the host does not wait."""
+    args, code, keep = _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+                                           black_level, cfa)
+    n, h, w = raw_u16.shape
+    out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
+    L.call('risp_serve_denoise_scene_u8', _p(raw_u16), float(divisor), *args, _p(out), int(bool(reverse_channels)), n, h, w,
+           int(black_level), code, _stream())
+    return out
+
+
 COND_SHARDS = 32           # RISP_COND_SHARDS: rows of counts per image, which serve_cond_finish adds
 COND_MAX_WIDTH, COND_MAX_LAYERS = 1024, 8      # the limits of risp_cond_fc_fwd and risp_serve_cond_finish
 

@@ -195,6 +195,10 @@ SIGNATURES = {
     'risp_serve_cond_finish': (_i, [_f, _i, _f, C.POINTER(_i), _i, _fl, _f, _i, _s]),
     'risp_serve_denoise_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, _i, _f, _f, _i, C.POINTER(_i), _pp, _f,
                                    _i, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_denoise_stats': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, _i, _f, _f, _i, C.POINTER(_i), _pp, _i, _f,
+                                      _i, _i, _i, _i, _i, _s]),
+    'risp_serve_denoise_scene_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, _i, _f, _f, _i, C.POINTER(_i), _pp, _f,
+                                         _i, _i, _i, _i, _i, _i, _s]),
     'risp_sse_uint8_doubles': (_z, []),
     'risp_sse_uint8': (_i, [_f, _f, _f, _z, _z, _s]),
     'risp_ssim_scratch_floats': (_z, [_i, _i, _i, _i]),
