@@ -580,6 +580,21 @@ int risp_tile_gather(const float *img, float *patches, const int32_t *pos_dev, i
                      int H, int W, int h, int w, void *stream);
 int risp_tile_blend(const float *patches, float *img, const int32_t *pos_dev, int T, int C,
                     int H, int W, int h, int w, int eh, int ew, void *stream);
+/* risp_tile_blend followed by risp_quantise_u8_flip in ONE launch, the fp32 frame never written: patches (T,C,h,w) fp32 and
+ * pos_dev (T,2) int32 (y,x) as for risp_tile_blend, out (H,W,C) packed bytes, C 1 or 3.  Per pixel and channel the arithmetic
+ * is risp_tile_blend's, expression for expression and in tile order - m = min(ramp_y, ramp_x), cnt += m, acc += p * m,
+ * acc / cnt - and then risp_quantise_u8's: the product with 255 in fp32, clipped to [0,255], truncated.  reverse_channels as
+ * in risp_quantise_u8.  flip (bit 0 x, bit 1 y: the RISP_CFA_* bits) stores the image un-mirrored, as risp_quantise_u8_flip
+ * does: output pixel (Y,X) is blended pixel (fy ? H-1-Y : Y, fx ? W-1-X : X).  Contract, byte for byte:
+ *     out == risp_quantise_u8_flip(risp_tile_blend(patches, ...), ..., reverse_channels, flip).
+ * A thread owns four adjacent pixels of a row: 16-byte tile loads and three dword stores where W % 4 == 0, w % 4 == 0, patches
+ * is 16-byte and out 4-byte aligned (a tile whose x origin is no multiple of 4 is read float by float inside the same launch);
+ * every other geometry and alignment takes a scalar form with the same bytes.
+ * Rules (anything else is refused before a launch and the message names the value): no NULL pointer; 1 <= T <= 65535; C 1 or
+ * 3; 1 <= h <= H <= 65535, 1 <= w <= W; 0 <= eh <= h / 2, 0 <= ew <= w / 2; flip 0 .. 3.  Every tile lies inside the frame and
+ * every pixel under a tile (the caller's part, as for risp_tile_blend). */
+int risp_tile_blend_u8(const float *patches, uint8_t *out, const int32_t *pos_dev, int T, int C,
+                       int H, int W, int h, int w, int eh, int ew, int reverse_channels, int flip, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Classical, non-differentiable "Origin" kernels of OriginUniversal (tools_origin.py:445-804).

@@ -137,3 +137,12 @@ class IspModel(BaseModel):
         with torch.no_grad():
             return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                         fast_denoise_scene)
+
+    def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
+                    black_level=0, cfa='rggb'):
+        """(H,W) or (N,H,W) uint16 sensor frames on the device -> (H,W,3) or (N,H,W,3) uint8 through overlapped tiles (the
+        pipeline's ``serve_frame``): the bytes ``test_split.py`` writes, without an fp32 frame at either end; ``black_level``
+        and ``cfa`` describe the sensor."""
+        with torch.no_grad():
+            return self.netG_attr.serve_frame(raw_u16, white_level, patch_size, patch_stride, tile_batch, reverse_channels, out,
+                                              black_level, cfa)

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import fused_forward, serve, wants_grad
+from .pipeline_fusion import fused_forward, serve, serve_frame, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -43,7 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
-        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'cond' | 'composed': what the last serve() call ran
+        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -131,6 +131,21 @@ class _FixedPipeline(nn.Module):
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond, fast_denoise_scene)
+        return out
+
+    def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
+                    black_level=0, cfa='rggb'):
+        """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
+        uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
+        ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
+        ``raw_crops`` launch cuts the tiles out of the mosaic, this module's inference forward runs on slices of
+        ``tile_batch`` tiles, ``risp_tile_blend_u8`` blends their last stage into the packed image: no fp32 frame at either
+        end, nothing leaves the device.  ``black_level`` and ``cfa`` describe the sensor as in ``serve``.
+        ``last_serve_route`` becomes 'tiled'; ``intermediate_results`` is left as it was."""
+        with torch.no_grad():
+            out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
+                              reverse_channels, out, black_level, cfa)
+            self.last_serve_route = 'tiled'
         return out
 
     @property

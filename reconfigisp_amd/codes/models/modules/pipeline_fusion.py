@@ -584,5 +584,76 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     return F.quantise_u8(x, reverse_channels, out, code), 'composed'
 
 
+_FRAME_GEOMETRY = {}
+
+
+def _pair(v):
+    return tuple(int(k) for k in v) if hasattr(v, '__len__') else (int(v), int(v))
+
+
+def frame_geometry(H, W, size, stride, cfa, device):
+    """(tile origins (T,2), ``sel`` rows (T,3)) of ``util_path_restore.frame_tile_sel`` as int32 tensors on ``device``, kept
+    per (H, W, size, stride, cfa, device): a warm ``serve_frame`` call uploads nothing."""
+    from ...utils.util_path_restore import frame_tile_sel
+    device = torch.device(device)
+    key = (int(H), int(W), _pair(size), _pair(stride), F.cfa_code(cfa), device.type, device.index)
+    hit = _FRAME_GEOMETRY.get(key)
+    if hit is None:
+        origins, sel = frame_tile_sel(key[0], key[1], key[2], key[3], cfa)
+        hit = _FRAME_GEOMETRY[key] = (torch.from_numpy(origins).to(device), torch.from_numpy(sel).to(device))
+    return hit
+
+
+def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
+                out=None, black_level=0, cfa='rggb'):
+    """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
+    (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
+    (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
+    white_level - black_level, the windows of another phase read mirrored, which makes every tile RGGB), ``fused_forward``
+    runs on slices of ``tile_batch`` tiles, each writing its last stage into its rows of one (T,3,h,w) stack
+    (``final_out``), and ``risp_tile_blend_u8`` blends the stack straight into the packed image, stored un-mirrored.  No
+    fp32 frame exists at either end.  The bytes are those ``test_split.py`` writes for ``raw / white_level`` (``run_frame``,
+    then clip, x 255, truncate), and for a sensor byte for byte
+    ``unflip(serve_frame(flip(clamp(raw - black_level)), white_level - black_level, ...))``.
+
+    ``param_tensors``: the per-stage blocks of ``min(tile_batch, T)`` images, or a callable that returns them for a number
+    of images (a shorter last slice takes the first rows of its blocks).
+    ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
+    on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
+    of ``serve``."""
+    from ...data.gpu_input import raw_crops
+    F._need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() not in (2, 3):
+        raise ValueError('expected (H,W) or (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    code = F.cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level < white_level:
+        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
+    if int(tile_batch) < 1:
+        raise ValueError('tile_batch %r: at least one tile per forward' % (tile_batch,))
+    single = raw_u16.dim() == 2
+    frames = (raw_u16[None] if single else raw_u16).contiguous()
+    n, H, W = frames.shape
+    F._check_mirror(code, H, W)
+    size, stride = _pair(patch_size), _pair(patch_stride)
+    origins, sel = frame_geometry(H, W, size, stride, cfa, frames.device)
+    count, tile_batch = origins.shape[0], int(tile_batch)
+    out = F._u8_out(out, (H, W, 3) if single else (n, H, W, 3), frames.device, 1)
+    stack = torch.empty((count, 3) + size, device=frames.device, dtype=torch.float32)
+    if callable(param_tensors):
+        param_tensors = param_tensors(min(tile_batch, count))
+    with torch.no_grad():
+        for k in range(n):
+            tiles = raw_crops(frames[k:k + 1], sel, size, white_level, black_level, cfa)
+            for at in range(0, count, tile_batch):
+                chunk, dest = tiles[at:at + tile_batch], stack[at:at + tile_batch]
+                m = chunk.shape[0]
+                pars = [p[:m] if p is not None and p.dim() == 2 and p.shape[0] > m else p for p in param_tensors]
+                y, _ = fused_forward(modules, pars, chunk, dest)
+                if y.data_ptr() != dest.data_ptr():
+                    dest.copy_(y)
+            F.tile_blend_u8(stack, origins, (H, W), stride, reverse_channels, out if single else out[k], code)
+    return out
+
+
 def wants_grad(x, raw_params):
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in raw_params))

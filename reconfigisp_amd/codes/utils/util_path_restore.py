@@ -3,7 +3,8 @@
 ``whole2patch`` / ``patch2whole`` / ``create_patch_mask`` keep the reference's numpy signatures
 (HWC arrays, positions, count map) but the gather / blend run on the GPU
 (risp_tile_gather / risp_tile_blend); ``tile_positions``, ``gather_tiles`` and ``blend_tiles``
-are the device-resident forms used by test_split.py so a frame never leaves HBM between stages.
+are the device-resident forms used by test_split.py so a frame never leaves HBM between stages;
+``frame_tile_sel`` lists the same tiles as windows of a uint16 sensor frame (the serving route).
 """
 import ctypes as C
 
@@ -50,6 +51,29 @@ def tile_grid(H, W, size, stride):
     """int32 (T,2) array of (y,x) tile origins, row-major like the reference's nested loops."""
     return np.asarray([[y, x] for y in tile_positions(H, size[0], stride[0])
                        for x in tile_positions(W, size[1], stride[1])], dtype=np.int32)
+
+
+def frame_tile_sel(H, W, size, stride, cfa):
+    """The tiles of a sensor frame of Bayer phase ``cfa`` for ``raw_crops``: (origins, sel), both int32 numpy arrays.
+    ``origins`` (T,2) are the tile origins (y,x) of the RGGB-oriented frame (``tile_grid``); ``sel`` (T,3) holds the rows
+    {0, row, col} that make ``raw_crops(frame, sel, size, ..., cfa=cfa)`` return exactly those tiles.  ``risp_raw_crop_cfa``
+    mirrors INSIDE its window, so on a mirrored axis the window of the tile at ``origin`` starts at full - origin - size.
+    H, W, size and stride must be even - then every tile starts on an even row and column on both sides of the mirror and
+    is RGGB for every stage, learned ones included - and a tile must fit the frame: ``ValueError`` otherwise.  Pure host
+    arithmetic, no GPU needed."""
+    (h, w), (sh, sw) = (int(v) for v in size), (int(v) for v in stride)
+    for name, v in (('H', H), ('W', W), ('patch height', h), ('patch width', w), ('stride (rows)', sh), ('stride (columns)', sw)):
+        if v < 2 or v % 2:
+            raise ValueError('frame_tile_sel: %s %d must be even and >= 2 (every tile has to start on an even row and column)'
+                             % (name, v))
+    if h > H or w > W:
+        raise ValueError('frame_tile_sel: a %d x %d tile does not fit the %d x %d frame' % (h, w, H, W))
+    code = F.cfa_code(cfa)
+    origins = tile_grid(H, W, (h, w), (sh, sw))
+    sel = np.zeros((len(origins), 3), dtype=np.int32)
+    sel[:, 1] = H - origins[:, 0] - h if code & 2 else origins[:, 0]
+    sel[:, 2] = W - origins[:, 1] - w if code & 1 else origins[:, 1]
+    return origins, sel
 
 
 def _edges(size, stride):

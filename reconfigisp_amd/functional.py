@@ -565,6 +565,31 @@ def quantise_u8(x, reverse_channels=False, out=None, flip=0):
     return out
 
 
+def tile_blend_u8(patches, positions, full, stride, reverse_channels=False, out=None, flip=0):
+    """``blend_tiles`` and ``quantise_u8`` in ONE launch (``risp_tile_blend_u8``): the tile stack ``patches`` (T,C,h,w), C 1 or
+    3, with the (T,2) tile origins ``positions`` (y,x) -> the packed (H,W,C) ``torch.uint8`` image of the ``full`` = (H,W)
+    frame.  The edges of the ramp mask are (size - stride) // 2, as ``blend_tiles`` derives them; ``reverse_channels`` and
+    ``flip`` as in ``quantise_u8``.  Byte for byte ``quantise_u8(blend_tiles(patches, ...)[None], reverse_channels,
+    flip=flip)[0]``; the fp32 frame is never written.  With ``out`` given nothing is allocated - apart from ``positions``
+    when it is not yet an int32 device tensor - and the host does not wait."""
+    patches = _dev(patches, 'patches')
+    if patches.dim() != 4 or patches.shape[1] not in (1, 3):
+        raise ValueError('expected a (T,1|3,h,w) tile stack, got %s' % (tuple(patches.shape),))
+    if flip not in (0, 1, 2, 3):
+        raise ValueError('flip %r: 0 .. 3 (bit 0 mirrors x, bit 1 mirrors y)' % (flip,))
+    t, c, h, w = patches.shape
+    if not (isinstance(positions, torch.Tensor) and positions.is_cuda and positions.dtype == torch.int32
+            and positions.is_contiguous()):
+        positions = torch.as_tensor(positions).to(device=patches.device, dtype=torch.int32).contiguous()
+    if tuple(positions.shape) != (t, 2):
+        raise ValueError('positions must be (T=%d,2), got %s' % (t, tuple(positions.shape)))
+    eh, ew = (h - int(stride[0])) // 2, (w - int(stride[1])) // 2
+    out = _u8_out(out, (int(full[0]), int(full[1]), c), patches.device, 1)
+    L.call('risp_tile_blend_u8', _p(patches), _p(out), _p(positions), t, c, int(full[0]), int(full[1]), h, w, eh, ew,
+           int(bool(reverse_channels)), flip, _stream())
+    return out
+
+
 def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
     """A fixed pipeline as an ISP in ONE launch (``risp_serve_u8``): (N,H,W) ``torch.uint16`` RGGB frames on the device ->
     (N,H,W,3) ``torch.uint8``.  sample / divisor, nearest demosaic, the bilateral when ``bilateral = (window_i32,

@@ -164,6 +164,7 @@ SIGNATURES = {
     'risp_cond_fc_bwd': (_i, [_f, C.POINTER(C.c_int), _i, _f, _f, _f, _f, _f, _i, _i, _s]),
     'risp_tile_gather': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_tile_blend': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_tile_blend_u8': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_origin_demosaic': (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _s]),
     'risp_origin_bilateral': (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _fl, _fl, _s]),
     'risp_origin_median': (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _s]),
