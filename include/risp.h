@@ -832,6 +832,44 @@ int risp_serve_classical_u8(const uint16_t *raw, float divisor, int demosaic, in
                             const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
                             int black_level, int cfa, void *stream);
 
+/* YUV 4:2:0 (NV12) out of the serving path (risp_nv12.hip, risp_nv12.h).  For an image of H x W pixels, H and W even, the
+ * NV12 image is (3H/2, W) bytes, images contiguous: rows 0 .. H-1 are the Y plane, row H + j holds U(j,0) V(j,0) U(j,1)
+ * V(j,1) ... for the W/2 chroma sites of quad row j.  With B, G, R the 8-bit codes of a pixel and coef = cy[4], cu[4], cv[4],
+ * each row kR, kG, kB, offset:
+ *     Y(y,x) = (cy0*R + cy1*G + cy2*B + cy3) >> 8                     per pixel
+ *     Rm     = (R00 + R01 + R10 + R11 + 2) >> 2  (Gm, Bm likewise)    per 2 x 2 quad: the rounded mean of the CODES
+ *     U(j,i) = (cu0*Rm + cu1*Gm + cu2*Bm + cu3) >> 8,  V(j,i) = (cv0*Rm + cv1*Gm + cv2*Bm + cv3) >> 8
+ * chroma sited at the quad centre (JPEG, MPEG-1).  The offsets carry the rounding constant (128) and the plane offset
+ * (16 << 8, 128 << 8): every intermediate is a non-negative 32-bit integer, there is no clamp and no signed shift.  A matrix
+ * is accepted only if that holds for all codes: per row |k| <= 256, offset + 255 * (sum of positive k) <= 65535 and
+ * offset + 255 * (sum of negative k) >= 0; a refusal names the row (cy, cu, cv).  BT.601 full range, the default of the
+ * Python side: {77, 150, 29, 128,  -43, -84, 127, 32896,  127, -106, -21, 32896}.
+ *
+ * risp_bgr8_to_nv12: img (N,H,W,3) packed bytes, B,G,R per pixel or R,G,B with rgb_in != 0 -> nv12 (N,3H/2,W), one launch,
+ * 3 bytes read and 1.5 written per pixel.  The end of every serving route that has no fused NV12 store.  With W % 4 == 0 and
+ * both buffers 4-byte aligned a thread owns a 2 x 4 patch (three dword loads per row, one Y dword per row and one UV dword
+ * stored); otherwise a thread owns one quad and moves bytes.  Rules (anything else is refused before a launch and nothing is
+ * written): img, nv12 and coef not NULL, N >= 1, H and W even and >= 2, a valid matrix.  img and nv12 must not overlap. */
+int risp_bgr8_to_nv12(const uint8_t *img, uint8_t *nv12, const int32_t coef[12], int rgb_in, int N, int H, int W, void *stream);
+
+/* risp_serve_u8_cfa with the NV12 store: signature, rules, black level and cfa are that entry point's, with the matrix coef
+ * in place of reverse_channels and out (N,3H/2,W).  One launch, 2 bytes read and 1.5 written per pixel.  The pixel pipeline
+ * is risp_serve_u8_cfa's; from the eight codes of its 2 x 4 patch a thread forms eight Y, two quad means and two UV pairs and
+ * stores three dwords instead of six, at the un-mirrored place (with cfa & 1 the Y bytes of a row go to column W-4-px in
+ * reverse order and the two quads swap places in the UV dword; with cfa & 2 rows py, py+1 go to H-1-py, H-2-py and the
+ * chroma row is (H-2-py)/2).  out == risp_bgr8_to_nv12(risp_serve_u8_cfa(..., reverse_channels 0, ...), coef) byte for
+ * byte.  The matrix travels by value with the launch; it is validated before the launch as in risp_bgr8_to_nv12. */
+int risp_serve_nv12(const uint16_t *raw, float divisor, const int32_t *window, const float *sigma_color,
+                    const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params,
+                    uint8_t *out, const int32_t coef[12], int N, int H, int W, int black_level, int cfa, void *stream);
+
+/* risp_serve_classical_u8 with the NV12 store, as risp_serve_nv12 is to risp_serve_u8_cfa: coef in place of
+ * reverse_channels, out (N,3H/2,W), every other argument and rule that entry point's, one launch;
+ * out == risp_bgr8_to_nv12(risp_serve_classical_u8(..., reverse_channels 0, ...), coef) byte for byte. */
+int risp_serve_classical_nv12(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                              const float *const *params, uint8_t *out, const int32_t coef[12], int N, int H, int W,
+                              int black_level, int cfa, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

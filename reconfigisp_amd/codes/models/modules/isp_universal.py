@@ -44,6 +44,7 @@ class _FixedPipeline(nn.Module):
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
         self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
+        self.last_serve_store = None            # with out_format='nv12': 'fused' (the serving launch stored NV12) | 'pass' (the conversion launch did); None for 'bgr8'
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -94,7 +95,7 @@ class _FixedPipeline(nn.Module):
         return x
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False, fast_denoise_scene=False):
+              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -126,26 +127,40 @@ class _FixedPipeline(nn.Module):
         (``pipeline_fusion.denoise_scene_plan``; H even and >= 4, W % 4 == 0, learned sizes 3 / 3 / (3, 3)): 2 S + 1 launches
         for S scene stages, no fp32 plane written.  White-world-only lists keep the default call's bytes; with gray-world the
         bytes are the composed route's for the same gains, and the gains are within the summation bound of the composed
-        route's.  Where the route does not apply the call runs as without the flag."""
+        route's.  Where the route does not apply the call runs as without the flag.
+
+        ``out_format='nv12'`` returns (N,3H/2,W) YUV 4:2:0 - H rows of Y, H/2 rows of interleaved U V, ``yuv_matrix`` a key of
+        ``functional.NV12_MATRIX`` or twelve integers -, byte for byte ``functional.bgr8_to_nv12`` of the same call's BGR
+        bytes, on the route the call takes without the keyword.  ``last_serve_store`` records who stored it: 'fused' (the one
+        launch of the 'fused' / 'classical' route) or 'pass' (``risp_bgr8_to_nv12`` behind any other route); None for 'bgr8'.
+        H and W even; ``reverse_channels`` is refused.  ``out_format``, ``yuv_matrix`` and ``fast_denoise_scene`` are
+        keyword-only (``pipeline_fusion.serve``)."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond, fast_denoise_scene)
+                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond,
+                                                    out_format=out_format, yuv_matrix=yuv_matrix,
+                                                    fast_denoise_scene=fast_denoise_scene)
+            self.last_serve_store = None if out_format == 'bgr8' else (
+                'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
-                    black_level=0, cfa='rggb'):
+                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full'):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
         ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
         ``raw_crops`` launch cuts the tiles out of the mosaic, this module's inference forward runs on slices of
         ``tile_batch`` tiles, ``risp_tile_blend_u8`` blends their last stage into the packed image: no fp32 frame at either
         end, nothing leaves the device.  ``black_level`` and ``cfa`` describe the sensor as in ``serve``.
-        ``last_serve_route`` becomes 'tiled'; ``intermediate_results`` is left as it was."""
+        ``last_serve_route`` becomes 'tiled'; ``intermediate_results`` is left as it was.  ``out_format='nv12'`` and
+        ``yuv_matrix`` as in ``serve``: (3H/2,W) or (N,3H/2,W), converted per frame behind the blend (``last_serve_store``
+        'pass')."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
-                              reverse_channels, out, black_level, cfa)
+                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix)
             self.last_serve_route = 'tiled'
+            self.last_serve_store = None if out_format == 'bgr8' else 'pass'
         return out
 
     @property

@@ -469,8 +469,27 @@ def _serve_denoise_scene(plan, den_args, modules, param_tensors, raw_u16, diviso
                                     reverse_channels, out, black_level, cfa)
 
 
+def _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w):
+    """the twelve integers of ``yuv_matrix`` for ``out_format='nv12'``, None for 'bgr8'; everything else is refused"""
+    if out_format == 'bgr8':
+        return None
+    if out_format != 'nv12':
+        raise ValueError("unknown out_format %r: 'bgr8' or 'nv12'" % (out_format,))
+    if reverse_channels:
+        raise ValueError("reverse_channels has no meaning with out_format='nv12': the conversion knows the channel order")
+    if h % 2 or w % 2:
+        raise ValueError('a %d x %d frame has no 4:2:0 form: H and W must be even' % (h, w))
+    return F.nv12_matrix(yuv_matrix)
+
+
+def _nv12_bgr(shape, device):
+    """the packed BGR image a route without a fused NV12 store serves into, kept per (shape, device, stream)"""
+    return F._scene_buffer(device, 'nv12_bgr', shape, torch.uint8)
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
-          fast_scene=False, fast_denoise=False, fast_cond=False, fast_denoise_scene=False):
+          fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
+          fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -524,7 +543,17 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     read mirrored - which makes it RGGB for every stage, learned ones included - and the image stored un-mirrored.  No
     extra pass on either route: the kernels mirror their addresses (``risp_serve_u8_cfa``; ``risp_raw_crop_cfa`` and
     ``risp_quantise_u8_flip`` around the unchanged ``fused_forward``).  Byte for byte
-    ``unflip(serve(flip(clamp(raw - black_level)), white_level - black_level))``."""
+    ``unflip(serve(flip(clamp(raw - black_level)), white_level - black_level))``.
+
+    ``out_format='nv12'`` returns YUV 4:2:0 instead: (N,3H/2,W) uint8, H rows of Y and H/2 rows of interleaved U V, converted
+    with ``yuv_matrix`` (a key of ``F.NV12_MATRIX`` or twelve integers) - byte for byte ``F.bgr8_to_nv12`` of what the same
+    call returns without the keyword.  The route is chosen exactly as without it.  ``'fused'`` and ``'classical'`` store NV12
+    from their one launch (``risp_serve_nv12``, ``risp_serve_classical_nv12``); every other route serves into a packed image
+    kept per shape, device and stream and ``risp_bgr8_to_nv12`` follows, one launch more.  H and W even;
+    ``reverse_channels`` is refused.  With ``out`` given a warm call allocates nothing.
+
+    ``out_format`` and ``yuv_matrix`` are keyword-only, and so is ``fast_denoise_scene``: it stays the last parameter
+    (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in front of it is unchanged."""
     F._need_gpu(raw_u16, 'raw')
     if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3:
         raise ValueError('expected (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
@@ -535,10 +564,29 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     n, h, w = raw_u16.shape
     F._check_mirror(code, h, w)
     divisor = white_level - black_level
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
+    if coef is not None:
+        if out is not None:
+            F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
+        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out)
+        return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
+    return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
+                      fast_denoise, fast_cond, fast_denoise_scene)
+
+
+def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
+               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None):
+    """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
+    NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch"""
+    n, h, w = raw_u16.shape
+    code = F.cfa_code(cfa)
+    # where a route without the NV12 store writes its packed image
+    dst = (lambda: out) if coef is None else (lambda: _nv12_bgr((n, h, w, 3), raw_u16.device))
     if fast_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         plan = scene_plan(modules)
         if plan is not None:
-            return _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa), 'scene'
+            return _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, dst(), black_level, cfa), 'scene'
     if fast_denoise and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         plan = denoise_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
@@ -546,18 +594,18 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
             pre_ops, pre_params = _stage_lists(modules, param_tensors, plan[1])
             post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
             return F.serve_denoise_u8(raw_u16, divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
-                                      reverse_channels, out, black_level, cfa), 'denoise'
+                                      reverse_channels, dst(), black_level, cfa), 'denoise'
     if fast_denoise_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         plan = denoise_scene_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
         if args is not None:
-            return _serve_denoise_scene(plan, args, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level,
+            return _serve_denoise_scene(plan, args, modules, param_tensors, raw_u16, divisor, reverse_channels, dst(), black_level,
                                         cfa), 'denoise_scene'
     if (fast_cond and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0
             and h * w <= 1 << 24):
         plan = cond_plan(modules)
         if plan is not None and _cond_heads_ok(plan, modules, param_tensors):
-            return _serve_cond(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa), 'cond'
+            return _serve_cond(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, dst(), black_level, cfa), 'cond'
     split = _serve_split(modules)
     if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
         bil, chain = split
@@ -566,11 +614,15 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         if args is None or (args[3] <= 3 and min(h, w) > 8):
             ops = [_CHAIN_OP[type(modules[k])] for k in chain]
             params = [_chain_param(modules[k], param_tensors[k]) for k in chain]
+            if coef is not None:
+                return F.serve_nv12(raw_u16, divisor, ops, params, args, coef, nv12_out, black_level, cfa), 'fused'
             return F.serve_u8(raw_u16, divisor, ops, params, args, reverse_channels, out, black_level, cfa), 'fused'
     if (serve_route(modules) == 'classical' and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535
             and raw_u16.data_ptr() % 8 == 0):
         kind, stages = _classical_split(modules)
         ops, params = _stage_lists(modules, param_tensors, stages)
+        if coef is not None:
+            return F.serve_classical_nv12(raw_u16, divisor, kind, ops, params, coef, nv12_out, black_level, cfa), 'classical'
         return F.serve_classical_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa), 'classical'
     from ...data.gpu_input import raw_crops
     sel = torch.zeros((n, 3), device=raw_u16.device, dtype=torch.int32)
@@ -581,7 +633,7 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     else:
         for mod, par in zip(modules, param_tensors):
             x = mod(x, par)
-    return F.quantise_u8(x, reverse_channels, out, code), 'composed'
+    return F.quantise_u8(x, reverse_channels, dst(), code), 'composed'
 
 
 _FRAME_GEOMETRY = {}
@@ -605,7 +657,7 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
-                out=None, black_level=0, cfa='rggb'):
+                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full'):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -618,6 +670,8 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
 
     ``param_tensors``: the per-stage blocks of ``min(tile_batch, T)`` images, or a callable that returns them for a number
     of images (a shorter last slice takes the first rows of its blocks).
+    ``out_format='nv12'`` returns (3H/2,W) or (N,3H/2,W) YUV 4:2:0 as ``serve`` does: ``risp_tile_blend_u8`` blends each frame
+    into a packed image kept per shape, device and stream and ``risp_bgr8_to_nv12`` converts it with ``yuv_matrix``.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
@@ -637,7 +691,12 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     size, stride = _pair(patch_size), _pair(patch_stride)
     origins, sel = frame_geometry(H, W, size, stride, cfa, frames.device)
     count, tile_batch = origins.shape[0], int(tile_batch)
-    out = F._u8_out(out, (H, W, 3) if single else (n, H, W, 3), frames.device, 1)
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W)
+    if coef is None:
+        out = F._u8_out(out, (H, W, 3) if single else (n, H, W, 3), frames.device, 1)
+    else:
+        out = F._u8_out(out, (H + H // 2, W) if single else (n, H + H // 2, W), frames.device, 1)
+        bgr = _nv12_bgr((H, W, 3), frames.device)
     stack = torch.empty((count, 3) + size, device=frames.device, dtype=torch.float32)
     if callable(param_tensors):
         param_tensors = param_tensors(min(tile_batch, count))
@@ -651,7 +710,11 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
                 y, _ = fused_forward(modules, pars, chunk, dest)
                 if y.data_ptr() != dest.data_ptr():
                     dest.copy_(y)
-            F.tile_blend_u8(stack, origins, (H, W), stride, reverse_channels, out if single else out[k], code)
+            if coef is None:
+                F.tile_blend_u8(stack, origins, (H, W), stride, reverse_channels, out if single else out[k], code)
+            else:
+                F.tile_blend_u8(stack, origins, (H, W), stride, False, bgr, code)
+                F.bgr8_to_nv12(bgr, coef, 'bgr', out if single else out[k])
     return out
 
 

@@ -20,6 +20,7 @@
 // The black level is subtracted in integers, clamped at 0, before the conversion to float.  Both are a further template parameter:
 // the instantiations risp_serve_u8 launches do not see them.
 #include "risp_common.h"
+#include "risp_nv12.h"
 #include "risp_ops.h"
 
 namespace {
@@ -120,8 +121,13 @@ struct ServeCfaArgs : ServeArgs {
     int black;                  // subtracted from every sample in integers, clamped at 0
     int flip;                   // RISP_CFA_*: bit 0 mirrors x, bit 1 mirrors y
 };
-template <bool CFA> struct serve_args { using type = ServeArgs; };
-template <> struct serve_args<true> { using type = ServeCfaArgs; };
+// risp_serve_nv12: the block of risp_serve_u8_cfa, then the matrix by value (`reverse` is not read)
+struct ServeNv12Args : ServeCfaArgs {
+    risp_nv12::Coef yuv;
+};
+template <bool CFA, bool NV12 = false> struct serve_args { using type = ServeArgs; };
+template <> struct serve_args<true, false> { using type = ServeCfaArgs; };
+template <bool CFA> struct serve_args<CFA, true> { using type = ServeNv12Args; };
 
 __device__ __forceinline__ float q8f(float v) {
     return floorf(__builtin_amdgcn_fmed3f(v, 0.f, 255.f) + 0.5f);   // clamp in one instruction (v is never NaN here)
@@ -144,9 +150,10 @@ __device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz) {
 constexpr int STX = 16, STY = 256 / STX, PXT = 4;      // threads across and down a workgroup: a 64 x 32 pixel tile
 
 // CFA: black level and mirror (wave-uniform at run time).  px, py and every coordinate derived from them are those of the mirrored
-// image, which is RGGB; only ld2 / ld4 / smp and the store know where the samples really are
-template <bool BIL, bool WBQ, bool CFA = false>
-__global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CFA>::type a) {
+// image, which is RGGB; only ld2 / ld4 / smp and the store know where the samples really are.  NV12: the store epilogue alone
+// differs - the patch's eight codes leave as two Y dwords and one UV dword of a (3H/2, W) image (risp_nv12.h)
+template <bool BIL, bool WBQ, bool CFA = false, bool NV12 = false>
+__global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CFA, NV12>::type a) {
     const int H = a.H, W = a.W;
     int bxi, byi, bzi;
     xcd_tile(bxi, byi, bzi);
@@ -273,6 +280,16 @@ __global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CF
     // ---- element-wise stages
     for (int k = 0; k < a.n_ops; ++k) apply_op<2 * PXT, WBQ>(a.ops[k], a.params[k], n, &pix[0][0]);
 
+    if constexpr (NV12) {
+        // ---- the codes the BGR store would write, as 4:2:0: three dwords instead of six
+        unsigned cr[2][PXT], cg[2][PXT], cb[2][PXT];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int c = 0; c < PXT; ++c) cb[p][c] = u8(pix[p][c].b), cg[p][c] = u8(pix[p][c].g), cr[p][c] = u8(pix[p][c].r);
+        risp_nv12::nv12_store_patch(a.out + (size_t)n * (H + H / 2) * W, a.yuv, cr, cg, cb, H, W, py, px, flip);
+        return;
+    }
     // ---- the result alone: 4 pixels x 3 bytes of a row are three dwords (the row offset is a multiple of 12 bytes).  Mirrored
     // along x the four pixels land at W-4-px in reverse order (the bytes of a pixel keep theirs)
 #pragma unroll
@@ -436,6 +453,42 @@ int risp_serve_u8_cfa(const uint16_t *raw, float divisor, const int32_t *window,
         else hipLaunchKernelGGL((serve_kernel<false, false, true>), grid, dim3(256), 0, s, a);
     }
     RISP_LAUNCH_CHECK("risp_serve_u8_cfa");
+    return 0;
+}
+
+int risp_serve_nv12(const uint16_t *raw, float divisor, const int32_t *window, const float *sigma_color, const float *sigma_space,
+                    int max_window, int n_ops, const int *ops, const float *const *params, uint8_t *out, const int32_t coef[12], int N,
+                    int H, int W, int black_level, int cfa, void *stream) {
+    RISP_CHECK_ARG(cfa >= 0 && cfa <= 3, "risp_serve_nv12: cfa %d (RISP_CFA_RGGB 0, GRBG 1, GBRG 2, BGGR 3)", cfa);
+    RISP_CHECK_ARG(black_level >= 0 && black_level <= 65535, "risp_serve_nv12: black_level %d outside 0 .. 65535", black_level);
+    ServeNv12Args a;
+    bool wbq = false;
+    if (int err = serve_args_fill("risp_serve_nv12", a, wbq, raw, divisor, window, sigma_color, sigma_space, max_window, n_ops, ops,
+                                  params, out, 0, N, H, W))
+        return err;
+    if (int err = risp_nv12::nv12_check("risp_serve_nv12", coef, a.yuv)) return err;
+    a.black = black_level;
+    a.flip = cfa;
+    const dim3 grid = serve_grid(N, H, W);
+    hipStream_t s = (hipStream_t)stream;
+    // an RGGB sensor without a black level takes the instantiations without the mirror, as risp_serve_u8 is to risp_serve_u8_cfa
+    // (max(s - 0, 0) == s and no address is mirrored: the same bytes, profiles/serve_cfa.txt has what the mirror costs)
+    if (black_level == 0 && cfa == 0) {
+        if (max_window) {
+            if (wbq) hipLaunchKernelGGL((serve_kernel<true, true, false, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((serve_kernel<true, false, false, true>), grid, dim3(256), 0, s, a);
+        } else {
+            if (wbq) hipLaunchKernelGGL((serve_kernel<false, true, false, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((serve_kernel<false, false, false, true>), grid, dim3(256), 0, s, a);
+        }
+    } else if (max_window) {
+        if (wbq) hipLaunchKernelGGL((serve_kernel<true, true, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((serve_kernel<true, false, true, true>), grid, dim3(256), 0, s, a);
+    } else {
+        if (wbq) hipLaunchKernelGGL((serve_kernel<false, true, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((serve_kernel<false, false, true, true>), grid, dim3(256), 0, s, a);
+    }
+    RISP_LAUNCH_CHECK("risp_serve_nv12");
     return 0;
 }
 

@@ -15,6 +15,7 @@
 // bytes are the composed route's (tests/test_gpu_serve_classical.py, torch.equal).  Black level and Bayer phase as in
 // risp_serve_u8_cfa: the phase is a mirror of addresses, coordinates, reflection and parity live in the mirrored (RGGB) image.
 #include "risp_common.h"
+#include "risp_nv12.h"
 #include "risp_ops.h"
 
 namespace {
@@ -48,6 +49,13 @@ struct ClassicalArgs {
     const float *params[RISP_MAX_CHAIN];
 };
 
+// risp_serve_classical_nv12: the same block first, then the matrix by value (`reverse` is not read)
+struct ClassicalNv12Args : ClassicalArgs {
+    risp_nv12::Coef yuv;
+};
+template <bool NV12> struct classical_args { using type = ClassicalArgs; };
+template <> struct classical_args<true> { using type = ClassicalNv12Args; };
+
 // XCD-aware tile order, as in risp_serve.hip: XCD k works through the k-th contiguous eighth of the tile list
 __device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz) {
     bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
@@ -78,9 +86,10 @@ __device__ __forceinline__ void tone_all(float p0, float p1, f3 *px) {
 }
 
 // KIND: RISP_DEMOSAIC_*.  px, py and every coordinate derived from them are those of the mirrored image, which is RGGB; only
-// row_at / ld2 / ld4 and the store know where the samples really are
-template <int KIND, bool WBQ>
-__global__ __launch_bounds__(256) void serve_classical_kernel(const ClassicalArgs a) {
+// row_at / ld2 / ld4 and the store know where the samples really are.  NV12: the store epilogue alone differs - the patch's
+// eight codes leave as two Y dwords and one UV dword of a (3H/2, W) image (risp_nv12.h)
+template <int KIND, bool WBQ, bool NV12 = false>
+__global__ __launch_bounds__(256) void serve_classical_kernel(const typename classical_args<NV12>::type a) {
     const int H = a.H, W = a.W;
     int bxi, byi, bzi;
     xcd_tile(bxi, byi, bzi);
@@ -183,6 +192,17 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const ClassicalArg
         }
     }
 
+    if constexpr (NV12) {
+        // ---- the codes the BGR store would write, as 4:2:0: three dwords instead of six
+        unsigned cr[2][PXT], cg[2][PXT], cb[2][PXT];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int c = 0; c < PXT; ++c) cb[p][c] = u8(pix[p][c].b), cg[p][c] = u8(pix[p][c].g), cr[p][c] = u8(pix[p][c].r);
+        risp_nv12::nv12_store_patch(a.out + (size_t)n * (H + H / 2) * W, a.yuv, cr, cg, cb, H, W, py, px, flip);
+        return;
+    }
+
     // ---- the result alone: 4 pixels x 3 bytes of a row are three dwords (the row offset is a multiple of 12 bytes).  Mirrored
     // along x the four pixels land at W-4-px in reverse order (the bytes of a pixel keep theirs)
 #pragma unroll
@@ -205,18 +225,16 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const ClassicalArg
     }
 }
 
-template <int KIND>
-void launch_kind(bool wbq, dim3 grid, hipStream_t s, const ClassicalArgs &a) {
-    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false>), grid, dim3(256), 0, s, a);
+template <int KIND, bool NV12, class Args>
+void launch_kind(bool wbq, dim3 grid, hipStream_t s, const Args &a) {
+    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true, NV12>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false, NV12>), grid, dim3(256), 0, s, a);
 }
 
-}  // namespace
-
-extern "C" int risp_serve_classical_u8(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
-                                       const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
-                                       int black_level, int cfa, void *stream) {
-    const char *name = "risp_serve_classical_u8";
+// the rules both entry points share (include/risp.h), and the argument block; `name` is the entry point's, for the message
+int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const uint16_t *raw, float divisor, int demosaic, int n_ops,
+                        const int *ops, const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
+                        int black_level, int cfa) {
     RISP_CHECK_ARG(raw && out, "%s: null argument", name);
     RISP_CHECK_ARG(divisor > 0.f, "%s: divisor %g", name, (double)divisor);
     RISP_CHECK_ARG(demosaic >= RISP_DEMOSAIC_NEAREST && demosaic <= RISP_DEMOSAIC_LAPLACIAN,
@@ -228,7 +246,6 @@ extern "C" int risp_serve_classical_u8(const uint16_t *raw, float divisor, int d
                    "%s: bad shape N=%d H=%d W=%d (H even and >= 4, W a multiple of 4)", name, N, H, W);
     RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(raw) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
                    "%s: raw must be 8-byte and out 4-byte aligned", name);
-    ClassicalArgs a;
     a.raw = raw;
     a.out = out;
     a.divisor = divisor;
@@ -239,7 +256,7 @@ extern "C" int risp_serve_classical_u8(const uint16_t *raw, float divisor, int d
     a.reverse = reverse_channels ? 1 : 0;
     a.black = black_level;
     a.flip = cfa;
-    bool wbq = false;
+    wbq = false;
     for (int k = 0; k < RISP_MAX_CHAIN; ++k) {
         a.ops[k] = RISP_OP_SKIP;
         a.params[k] = nullptr;
@@ -252,11 +269,42 @@ extern "C" int risp_serve_classical_u8(const uint16_t *raw, float divisor, int d
         a.params[k] = ops[k] == RISP_OP_SKIP ? nullptr : params[k];
         wbq |= ops[k] == RISP_OP_WB_QUADRATIC;
     }
-    const dim3 grid((W / 4 + STX - 1) / STX, (H / 2 + STY - 1) / STY, N);
-    hipStream_t s = (hipStream_t)stream;
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN>(wbq, grid, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR>(wbq, grid, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST>(wbq, grid, s, a);
+    return 0;
+}
+
+template <bool NV12, class Args>
+void launch_classical(int demosaic, bool wbq, hipStream_t s, const Args &a) {
+    const dim3 grid((a.W / 4 + STX - 1) / STX, (a.H / 2 + STY - 1) / STY, a.N);
+    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, NV12>(wbq, grid, s, a);
+    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, NV12>(wbq, grid, s, a);
+    else launch_kind<RISP_DEMOSAIC_NEAREST, NV12>(wbq, grid, s, a);
+}
+
+}  // namespace
+
+extern "C" int risp_serve_classical_u8(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                                       const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
+                                       int black_level, int cfa, void *stream) {
+    ClassicalArgs a;
+    bool wbq = false;
+    if (int err = classical_args_fill("risp_serve_classical_u8", a, wbq, raw, divisor, demosaic, n_ops, ops, params, out,
+                                      reverse_channels, N, H, W, black_level, cfa))
+        return err;
+    launch_classical<false>(demosaic, wbq, (hipStream_t)stream, a);
     RISP_LAUNCH_CHECK("risp_serve_classical_u8");
+    return 0;
+}
+
+extern "C" int risp_serve_classical_nv12(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                                         const float *const *params, uint8_t *out, const int32_t coef[12], int N, int H, int W,
+                                         int black_level, int cfa, void *stream) {
+    ClassicalNv12Args a;
+    bool wbq = false;
+    if (int err = classical_args_fill("risp_serve_classical_nv12", a, wbq, raw, divisor, demosaic, n_ops, ops, params, out, 0, N, H,
+                                      W, black_level, cfa))
+        return err;
+    if (int err = risp_nv12::nv12_check("risp_serve_classical_nv12", coef, a.yuv)) return err;
+    launch_classical<true>(demosaic, wbq, (hipStream_t)stream, a);
+    RISP_LAUNCH_CHECK("risp_serve_classical_nv12");
     return 0;
 }

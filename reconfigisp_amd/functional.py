@@ -666,6 +666,124 @@ def serve_classical_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels
     return out
 
 
+# YUV 4:2:0 (NV12) out: cy[4], cu[4], cv[4], each row kR, kG, kB, offset (include/risp.h states the format).  The offsets
+# carry the rounding constant 128 and the plane offset (16 << 8, 128 << 8); the full-range chroma rows use 127, not 128, so
+# that no sum leaves 0 .. 65535 and the kernels need no clamp
+NV12_MATRIX = {
+    'bt601_full': (77, 150, 29, 128, -43, -84, 127, 32896, 127, -106, -21, 32896),
+    'bt601_video': (66, 129, 25, 4224, -38, -74, 112, 32896, 112, -94, -18, 32896),
+    'bt709_full': (54, 183, 19, 128, -29, -98, 127, 32896, 127, -115, -12, 32896),
+    'bt709_video': (47, 157, 16, 4224, -26, -86, 112, 32896, 112, -102, -10, 32896),
+}
+
+
+def nv12_matrix(matrix):
+    """A key of ``NV12_MATRIX`` or twelve integers -> the twelve integers the NV12 entry points take.  A matrix is accepted
+    when every sum stays in 0 .. 65535 for all codes: per row |k| <= 256, offset + 255 * (sum of positive k) <= 65535 and
+    offset + 255 * (sum of negative k) >= 0."""
+    if isinstance(matrix, str):
+        coef = NV12_MATRIX.get(matrix)
+        if coef is None:
+            raise ValueError('unknown yuv matrix %r: one of %s, or twelve integers' % (matrix, ', '.join(NV12_MATRIX)))
+        return coef
+    try:
+        coef = tuple(int(k) for k in matrix)
+        exact = all(k == v for k, v in zip(coef, matrix))
+    except (TypeError, ValueError):
+        coef, exact = (), False
+    if len(coef) != 12 or not exact:
+        raise ValueError('a yuv matrix is a key of NV12_MATRIX or twelve integers, got %r' % (matrix,))
+    for r, name in enumerate(('cy', 'cu', 'cv')):
+        k = coef[4 * r:4 * r + 4]
+        if (max(abs(v) for v in k[:3]) > 256 or k[3] + 255 * sum(v for v in k[:3] if v > 0) > 65535
+                or k[3] + 255 * sum(v for v in k[:3] if v < 0) < 0):
+            raise ValueError('yuv matrix row %s %s leaves 0 .. 65535 for some codes (or a coefficient is outside -256 .. 256)'
+                             % (name, k))
+    return coef
+
+
+def bgr8_to_nv12(img_u8, matrix='bt601_full', channels='bgr', out=None):
+    """Packed 8-bit images to YUV 4:2:0 in ONE launch (``risp_bgr8_to_nv12``): (N,H,W,3) or (H,W,3) ``torch.uint8`` on the
+    device, ``channels`` 'bgr' or 'rgb', H and W even -> (N,3H/2,W) or (3H/2,W) ``torch.uint8``: H rows of Y, then H/2 rows
+    of U V U V ..., chroma the matrix of the rounded mean of a 2 x 2 quad's codes (``nv12_matrix``; the integer definition
+    is in include/risp.h).  With ``out`` given nothing is allocated and the host does not wait."""
+    _need_gpu(img_u8, 'img')
+    if img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
+        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s' % (img_u8.dtype, tuple(img_u8.shape)))
+    if channels not in ('bgr', 'rgb'):
+        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    coef = nv12_matrix(matrix)
+    h, w = img_u8.shape[-3], img_u8.shape[-2]
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
+    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
+    img_u8 = img_u8.contiguous()
+    out = _u8_out(out, tuple(img_u8.shape[:-3]) + (h + h // 2, w), img_u8.device, 1)
+    L.call('risp_bgr8_to_nv12', _p(img_u8), _p(out), (C.c_int * 12)(*coef), int(channels == 'rgb'), n, h, w, _stream())
+    return out
+
+
+def serve_nv12(raw_u16, divisor, ops, params, bilateral=None, matrix='bt601_full', out=None, black_level=0, cfa='rggb'):
+    """``serve_u8`` with the NV12 store (``risp_serve_nv12``, ONE launch): the same arguments with ``matrix``
+    (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte
+    ``bgr8_to_nv12(serve_u8(...), matrix)`` without the packed image ever being written.  H even, W % 4 == 0.  With ``out``
+    given nothing is allocated and the host does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    coef = nv12_matrix(matrix)
+    n, h, w = raw_u16.shape
+    if h % 2 or w % 2:
+        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
+    out = _u8_out(out, (n, h + h // 2, w), raw_u16.device, 4)
+    keep = [_dev(p) if p is not None else None for p in params]
+    if bilateral is not None:
+        win, sc, ss, wmax = bilateral
+        if win.dtype != torch.int32 or not win.is_cuda:
+            raise ValueError('window must be an int32 device tensor')
+        keep += [win.contiguous(), _dev(sc), _dev(ss)]
+        bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
+    else:
+        bil = (None, None, None, 0)
+    L.call('risp_serve_nv12', _p(raw_u16), float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
+           _p(out), (C.c_int * 12)(*coef), n, h, w, int(black_level), code, _stream())
+    return out
+
+
+def serve_classical_nv12(raw_u16, divisor, demosaic, ops, params, matrix='bt601_full', out=None, black_level=0, cfa='rggb'):
+    """``serve_classical_u8`` with the NV12 store (``risp_serve_classical_nv12``, ONE launch): the same arguments with
+    ``matrix`` (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte
+    ``bgr8_to_nv12(serve_classical_u8(...), matrix)``.  H even and >= 4, W % 4 == 0.  With ``out`` given nothing is allocated
+    and the host does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
+    if kind is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    coef = nv12_matrix(matrix)
+    n, h, w = raw_u16.shape
+    if h % 2 or w % 2:
+        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
+    out = _u8_out(out, (n, h + h // 2, w), raw_u16.device, 4)
+    keep = [_dev(p) if p is not None else None for p in params]
+    L.call('risp_serve_classical_nv12', _p(raw_u16), float(divisor), kind, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), _p(out), (C.c_int * 12)(*coef),
+           n, h, w, int(black_level), code, _stream())
+    return out
+
+
 DENOISE = {'bilateral': 0, 'median': 1, 'fastnlm': 2}          # RISP_DENOISE_*
 
 

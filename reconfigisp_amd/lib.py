@@ -188,6 +188,9 @@ SIGNATURES = {
     'risp_quantise_u8_flip': (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_u8_cfa': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_classical_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_bgr8_to_nv12': (_i, [_f, _f, C.POINTER(_i), _i, _i, _i, _i, _s]),
+    'risp_serve_nv12': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _s]),
+    'risp_serve_classical_nv12': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _s]),
     'risp_serve_scene_groups': (_i, [_i, _i]),
     'risp_serve_scene_stats': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _f, _i, _i, _i, _i, _i, _s]),
     'risp_serve_scene_finish': (_i, [_i, _f, _f, _f, _f, _i, _i, _i, _s]),
