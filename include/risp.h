@@ -870,6 +870,45 @@ int risp_serve_classical_nv12(const uint16_t *raw, float divisor, int demosaic, 
                               const float *const *params, uint8_t *out, const int32_t coef[12], int N, int H, int W,
                               int black_level, int cfa, void *stream);
 
+/* MIPI-packed RAW10 / RAW12 into the serving path (risp_rawpack.hip, risp_rawpack.h): the layout of CSI-2 receivers, V4L2
+ * pRAA / pRCC buffers and DNG.  bits is 10 or 12.  An image is H rows of `stride` bytes, stride >= W * bits / 8, W % 4 == 0;
+ * image n starts at byte n * H * stride.  The bytes of a row behind the first W * bits / 8 are padding: any content, never read.
+ *     RAW10: pixels 4g .. 4g+3 of a row live in bytes 5g .. 5g+4:   P[4g+k] = (byte[5g+k] << 2) | ((byte[5g+4] >> 2k) & 3), k = 0 .. 3
+ *            (pixels 0x3FF, 0x000, 0x155, 0x2AA are the bytes FF 00 55 AA 93)
+ *     RAW12: pixels 2g, 2g+1 live in bytes 3g .. 3g+2:              P[2g]   = (byte[3g]   << 4) | (byte[3g+2] & 15)
+ *                                                                   P[2g+1] = (byte[3g+1] << 4) | (byte[3g+2] >> 4)
+ *            (pixels 0xABC, 0x123 are the bytes AB 12 3C)
+ * `packed` may start at any byte and `stride` may have any parity.  No byte outside [packed, packed + N * H * stride) is read,
+ * and within a row none behind W * bits / 8.  white_level is not implied by the format.  RAW8, RAW14 and 16-bit containers
+ * are not covered.
+ *
+ * risp_raw_unpack: packed -> out (N,H,W) uint16 contiguous, one sample per word, one launch, bits / 8 bytes read and 2 written
+ * per pixel.  The front of every serving route that has no fused packed load.  With packed and stride 4-byte aligned a thread
+ * loads the 20 / 24 bytes of 16 pixels as dwords; otherwise (and for a row's last, shorter chunk) it copies 4, 2 and 1 bytes
+ * per four pixels.  Rules (anything else is refused before a launch, the message names the value): packed and out not NULL,
+ * bits 10 or 12, N and H >= 1, W >= 4 and W % 4 == 0, stride >= W * bits / 8, out 8-byte aligned. */
+int risp_raw_unpack(const uint8_t *packed, uint16_t *out, int bits, int N, int H, int W, int stride, void *stream);
+
+/* risp_serve_u8_cfa / risp_serve_nv12 on packed frames, still one launch: raw, bits, stride in place of the uint16 pointer, and
+ * coef: NULL stores BGR (N,H,W,3) with reverse_channels, non-NULL stores NV12 (N,3H/2,W) with that matrix (validated as in
+ * risp_bgr8_to_nv12; reverse_channels is then not read).  bits / 8 bytes read per pixel.  The same kernel: a thread's four
+ * centre pixels are one 5-byte group or two 3-byte groups, the pairs left and right of them half a group or one group, and
+ * mirrored along x the group at W-4-x is read and reversed; everything behind the sample is unchanged, so
+ *     out == risp_serve_u8_cfa | risp_serve_nv12 (risp_raw_unpack(raw), ...)   byte for byte.
+ * Rules: those of risp_serve_u8_cfa (H even, W % 4 == 0, ...) without its alignment rule on raw, plus bits 10 or 12 and
+ * stride >= W * bits / 8. */
+int risp_serve_packed(const uint8_t *raw, int bits, int stride, float divisor, const int32_t *window, const float *sigma_color,
+                      const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params,
+                      uint8_t *out, int reverse_channels, const int32_t *coef, int N, int H, int W, int black_level, int cfa,
+                      void *stream);
+
+/* risp_serve_classical_u8 / risp_serve_classical_nv12 on packed frames, as risp_serve_packed is to risp_serve_u8_cfa /
+ * risp_serve_nv12: raw, bits, stride and coef as there, every other argument and rule risp_serve_classical_u8's (H even and
+ * >= 4), one launch; out == risp_serve_classical_u8 | risp_serve_classical_nv12 (risp_raw_unpack(raw), ...) byte for byte. */
+int risp_serve_classical_packed(const uint8_t *raw, int bits, int stride, float divisor, int demosaic, int n_ops, const int *ops,
+                                const float *const *params, uint8_t *out, int reverse_channels, const int32_t *coef, int N,
+                                int H, int W, int black_level, int cfa, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

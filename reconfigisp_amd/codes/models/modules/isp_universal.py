@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import fused_forward, serve, serve_frame, wants_grad
+from .pipeline_fusion import fused_forward, serve, serve_frame, serve_load, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -45,6 +45,7 @@ class _FixedPipeline(nn.Module):
         self.intermediate_results = []
         self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
         self.last_serve_store = None            # with out_format='nv12': 'fused' (the serving launch stored NV12) | 'pass' (the conversion launch did); None for 'bgr8'
+        self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
 
     def _apply(self, fn, *args, **kwargs):
         # sub-modules and zero-size placeholders live in plain lists (as in the reference, so the
@@ -95,7 +96,8 @@ class _FixedPipeline(nn.Module):
         return x
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', fast_denoise_scene=False):
+              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', raw_format='u16', raw_width=None,
+              fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -133,20 +135,27 @@ class _FixedPipeline(nn.Module):
         ``functional.NV12_MATRIX`` or twelve integers -, byte for byte ``functional.bgr8_to_nv12`` of the same call's BGR
         bytes, on the route the call takes without the keyword.  ``last_serve_store`` records who stored it: 'fused' (the one
         launch of the 'fused' / 'classical' route) or 'pass' (``risp_bgr8_to_nv12`` behind any other route); None for 'bgr8'.
-        H and W even; ``reverse_channels`` is refused.  ``out_format``, ``yuv_matrix`` and ``fast_denoise_scene`` are
-        keyword-only (``pipeline_fusion.serve``)."""
+        H and W even; ``reverse_channels`` is refused.
+
+        ``raw_format='raw10'`` / ``'raw12'`` takes the frames MIPI-packed, (N,H,stride) uint8 with ``raw_width`` pixels per row
+        (None: all the rows hold) - the bytes of the same call on ``functional.raw_unpack`` of them, on the same route.
+        ``last_serve_load`` records who decoded them, as ``pipeline_fusion.serve_load`` tells: 'fused' (the one launch of the
+        'fused' / 'classical' route) or 'pass' (``risp_raw_unpack`` in front of any other route); None for 'u16'.
+        ``white_level`` is not implied by the format.  ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width`` and
+        ``fast_denoise_scene`` are keyword-only (``pipeline_fusion.serve``)."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
-                                                    out_format=out_format, yuv_matrix=yuv_matrix,
-                                                    fast_denoise_scene=fast_denoise_scene)
+                                                    out_format=out_format, yuv_matrix=yuv_matrix, raw_format=raw_format,
+                                                    raw_width=raw_width, fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
+            self.last_serve_load = serve_load(self.last_serve_route, raw_format)
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
-                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full'):
+                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16', raw_width=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
         ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
@@ -155,11 +164,14 @@ class _FixedPipeline(nn.Module):
         end, nothing leaves the device.  ``black_level`` and ``cfa`` describe the sensor as in ``serve``.
         ``last_serve_route`` becomes 'tiled'; ``intermediate_results`` is left as it was.  ``out_format='nv12'`` and
         ``yuv_matrix`` as in ``serve``: (3H/2,W) or (N,3H/2,W), converted per frame behind the blend (``last_serve_store``
-        'pass')."""
+        'pass').  ``raw_format`` and ``raw_width`` as in ``serve``, (H,stride) included: unpacked once in front of the tiles
+        (``last_serve_load`` 'pass')."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
-                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix)
+                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix, raw_format=raw_format,
+                              raw_width=raw_width)
             self.last_serve_route = 'tiled'
+            self.last_serve_load = serve_load('tiled', raw_format)
             self.last_serve_store = None if out_format == 'bgr8' else 'pass'
         return out
 

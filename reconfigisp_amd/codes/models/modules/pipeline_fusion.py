@@ -487,9 +487,49 @@ def _nv12_bgr(shape, device):
     return F._scene_buffer(device, 'nv12_bgr', shape, torch.uint8)
 
 
+SERVE_ROUTES = ('fused', 'classical', 'scene', 'denoise', 'denoise_scene', 'cond', 'composed', 'tiled')
+# (route, raw_format) whose one launch decodes the packed bytes itself.  A route is listed only where the fused load beat the
+# unpack launch followed by the uint16 call by more than the spread on the 3000 x 4000 frame (profiles/serve_packed.txt,
+# DESIGN.md 4.6).  The classical kernel does, by 10 us; the headline kernel with its bilateral does not - its 36 narrow loads and
+# their shifts cost the issue-bound launch 10-14 %, what the unpack launch costs or more - and unpacks first.  risp_serve_packed exists
+# either way (functional.serve_packed): it is correct and saves the intermediate frames
+_FUSED_LOAD = frozenset({('classical', 'raw10'), ('classical', 'raw12')})
+
+
+def serve_load(route, raw_format):
+    """Who decodes MIPI-packed frames on ``route`` (a name of ``SERVE_ROUTES``): 'fused' - the route's one launch loads the
+    packed bytes (``risp_serve_packed``, ``risp_serve_classical_packed``) - or 'pass' - ``risp_raw_unpack`` writes uint16
+    frames first and the route runs as for them; None for ``raw_format='u16'``.  A pure function of its arguments: what
+    ``serve`` does and what ``last_serve_load`` reports."""
+    if route not in SERVE_ROUTES:
+        raise ValueError('unknown route %r: one of %s' % (route, ', '.join(SERVE_ROUTES)))
+    if not F.raw_format_bits(raw_format):
+        return None
+    return 'fused' if (route, raw_format) in _FUSED_LOAD else 'pass'
+
+
+def _packed_plan(raw, raw_format, raw_width, dims):
+    """``serve`` / ``serve_frame`` on MIPI-packed frames, checked on the host before anything else: (bits, W) for uint8 frames
+    of ``dims`` dimensions whose last is the row pitch in bytes; everything else is refused"""
+    bits = F.raw_format_bits(raw_format)
+    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or raw.dim() not in dims:
+        raise ValueError("raw_format=%r takes %s uint8 frames (rows of stride bytes), got %s %s"
+                         % (raw_format, ' or '.join('(N,H,stride)' if d == 3 else '(H,stride)' for d in dims),
+                            getattr(raw, 'dtype', type(raw)), tuple(getattr(raw, 'shape', ()))))
+    w = F.packed_width(bits, raw.shape[-1], raw_width)
+    if raw.shape[-2] % 2:
+        raise ValueError('packed frames of %d rows: H must be even' % raw.shape[-2])
+    return bits, w
+
+
+def _packed_u16(shape, device):
+    """the uint16 frames a route without a fused packed load unpacks into, kept per (shape, device, stream)"""
+    return F._scene_buffer(device, 'raw_u16', shape, torch.uint16)
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          fast_denoise_scene=False):
+          raw_format='u16', raw_width=None, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -552,16 +592,36 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     kept per shape, device and stream and ``risp_bgr8_to_nv12`` follows, one launch more.  H and W even;
     ``reverse_channels`` is refused.  With ``out`` given a warm call allocates nothing.
 
-    ``out_format`` and ``yuv_matrix`` are keyword-only, and so is ``fast_denoise_scene``: it stays the last parameter
-    (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in front of it is unchanged."""
-    F._need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3:
-        raise ValueError('expected (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    ``raw_format='raw10'`` / ``'raw12'`` takes MIPI-packed frames as a sensor delivers them: (N,H,stride) uint8, rows of
+    ``stride`` bytes that hold ``raw_width`` pixels (None: all they can, ``stride * 8 // bits``) - four pixels in five bytes
+    or two in three, include/risp.h has the layout -, padding behind them never read, any start address.  The bytes returned
+    are those of the same call on ``F.raw_unpack(frames, bits, raw_width)``, on the route that call takes.  ``'fused'`` and
+    ``'classical'`` decode the groups in their one launch where ``serve_load`` says 'fused' (``risp_serve_packed``,
+    ``risp_serve_classical_packed``); every other route unpacks once into uint16 frames kept per shape, device and stream
+    (``risp_raw_unpack``, one launch more) and runs as for them.  ``white_level`` is not implied by the format.  H even,
+    ``raw_width`` a multiple of 4.  With ``out`` given a warm call allocates nothing.  ``raw_format='u16'`` is the call
+    without the keyword.
+
+    ``out_format``, ``yuv_matrix``, ``raw_format`` and ``raw_width`` are keyword-only, and so is ``fast_denoise_scene``: it
+    stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
+    front of it is unchanged."""
+    packed = None
+    if raw_format != 'u16':
+        bits, w = _packed_plan(raw_u16, raw_format, raw_width, (3,))
+        F._need_gpu(raw_u16, 'raw')
+        raw_u16 = raw_u16.contiguous()
+        packed = (raw_u16, bits, w, raw_format)
+        n, h = raw_u16.shape[:2]
+    else:
+        F._need_gpu(raw_u16, 'raw')
+        if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3:
+            raise ValueError('expected (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
     code = F.cfa_code(cfa)
     if black_level != int(black_level) or not 0 <= black_level < white_level:
         raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-    raw_u16 = raw_u16.contiguous()
-    n, h, w = raw_u16.shape
+    if packed is None:
+        raw_u16 = raw_u16.contiguous()
+        n, h, w = raw_u16.shape
     F._check_mirror(code, h, w)
     divisor = white_level - black_level
     coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
@@ -569,65 +629,85 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         if out is not None:
             F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out)
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed)
         return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
     return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-                      fast_denoise, fast_cond, fast_denoise_scene)
+                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed)
 
 
 def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None):
+               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None):
     """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
-    NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch"""
-    n, h, w = raw_u16.shape
+    NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
+    With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
+    from the allocator take, 'fused' and 'classical' load the packed bytes where ``serve_load`` says so, and every other
+    route runs on ``frames()``, the cached uint16 stack the unpack launch fills"""
+    device = raw_u16.device
+    if packed is None:
+        n, h, w = raw_u16.shape
+        aligned = raw_u16.data_ptr() % 8 == 0
+
+        def frames():
+            return raw_u16
+    else:
+        (n, h), w, aligned = raw_u16.shape[:2], packed[2], True
+
+        def frames():
+            return F.raw_unpack(packed[0], packed[1], w, _packed_u16((n, h, w), device))
     code = F.cfa_code(cfa)
     # where a route without the NV12 store writes its packed image
-    dst = (lambda: out) if coef is None else (lambda: _nv12_bgr((n, h, w, 3), raw_u16.device))
-    if fast_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+    dst = (lambda: out) if coef is None else (lambda: _nv12_bgr((n, h, w, 3), device))
+    if fast_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
         plan = scene_plan(modules)
         if plan is not None:
-            return _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, dst(), black_level, cfa), 'scene'
-    if fast_denoise and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+            return _serve_scene(plan, modules, param_tensors, frames(), divisor, reverse_channels, dst(), black_level, cfa), 'scene'
+    if fast_denoise and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
         plan = denoise_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
         if args is not None:
             pre_ops, pre_params = _stage_lists(modules, param_tensors, plan[1])
             post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
-            return F.serve_denoise_u8(raw_u16, divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
+            return F.serve_denoise_u8(frames(), divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
                                       reverse_channels, dst(), black_level, cfa), 'denoise'
-    if fast_denoise_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+    if fast_denoise_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
         plan = denoise_scene_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
         if args is not None:
-            return _serve_denoise_scene(plan, args, modules, param_tensors, raw_u16, divisor, reverse_channels, dst(), black_level,
+            return _serve_denoise_scene(plan, args, modules, param_tensors, frames(), divisor, reverse_channels, dst(), black_level,
                                         cfa), 'denoise_scene'
-    if (fast_cond and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0
+    if (fast_cond and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned
             and h * w <= 1 << 24):
         plan = cond_plan(modules)
         if plan is not None and _cond_heads_ok(plan, modules, param_tensors):
-            return _serve_cond(plan, modules, param_tensors, raw_u16, divisor, reverse_channels, dst(), black_level, cfa), 'cond'
+            return _serve_cond(plan, modules, param_tensors, frames(), divisor, reverse_channels, dst(), black_level, cfa), 'cond'
     split = _serve_split(modules)
-    if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and raw_u16.data_ptr() % 8 == 0:
+    if split is not None and h % 2 == 0 and w % 4 == 0 and n <= 65535 and aligned:
         bil, chain = split
         # (the bilateral joins a launch under fused_forward's own conditions, so both routes run the same kernel arithmetic)
         args = _bilateral_args(modules[bil], param_tensors[bil]) if bil is not None else None
         if args is None or (args[3] <= 3 and min(h, w) > 8):
             ops = [_CHAIN_OP[type(modules[k])] for k in chain]
             params = [_chain_param(modules[k], param_tensors[k]) for k in chain]
+            if packed is not None and serve_load('fused', packed[3]) == 'fused':
+                return F.serve_packed(packed[0], packed[1], w, divisor, ops, params, args, reverse_channels, coef,
+                                      out if coef is None else nv12_out, black_level, cfa), 'fused'
             if coef is not None:
-                return F.serve_nv12(raw_u16, divisor, ops, params, args, coef, nv12_out, black_level, cfa), 'fused'
-            return F.serve_u8(raw_u16, divisor, ops, params, args, reverse_channels, out, black_level, cfa), 'fused'
+                return F.serve_nv12(frames(), divisor, ops, params, args, coef, nv12_out, black_level, cfa), 'fused'
+            return F.serve_u8(frames(), divisor, ops, params, args, reverse_channels, out, black_level, cfa), 'fused'
     if (serve_route(modules) == 'classical' and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535
-            and raw_u16.data_ptr() % 8 == 0):
+            and aligned):
         kind, stages = _classical_split(modules)
         ops, params = _stage_lists(modules, param_tensors, stages)
+        if packed is not None and serve_load('classical', packed[3]) == 'fused':
+            return F.serve_classical_packed(packed[0], packed[1], w, divisor, kind, ops, params, reverse_channels, coef,
+                                            out if coef is None else nv12_out, black_level, cfa), 'classical'
         if coef is not None:
-            return F.serve_classical_nv12(raw_u16, divisor, kind, ops, params, coef, nv12_out, black_level, cfa), 'classical'
-        return F.serve_classical_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa), 'classical'
+            return F.serve_classical_nv12(frames(), divisor, kind, ops, params, coef, nv12_out, black_level, cfa), 'classical'
+        return F.serve_classical_u8(frames(), divisor, kind, ops, params, reverse_channels, out, black_level, cfa), 'classical'
     from ...data.gpu_input import raw_crops
-    sel = torch.zeros((n, 3), device=raw_u16.device, dtype=torch.int32)
-    sel[:, 0] = torch.arange(n, device=raw_u16.device, dtype=torch.int32)
-    x = raw_crops(raw_u16, sel, (h, w), white_level, black_level, cfa)
+    sel = torch.zeros((n, 3), device=device, dtype=torch.int32)
+    sel[:, 0] = torch.arange(n, device=device, dtype=torch.int32)
+    x = raw_crops(frames(), sel, (h, w), white_level, black_level, cfa)
     if h % 2 == 0 and w % 2 == 0:
         x, _ = fused_forward(modules, param_tensors, x)
     else:
@@ -657,7 +737,8 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
-                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full'):
+                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16',
+                raw_width=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -672,10 +753,17 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     of images (a shorter last slice takes the first rows of its blocks).
     ``out_format='nv12'`` returns (3H/2,W) or (N,3H/2,W) YUV 4:2:0 as ``serve`` does: ``risp_tile_blend_u8`` blends each frame
     into a packed image kept per shape, device and stream and ``risp_bgr8_to_nv12`` converts it with ``yuv_matrix``.
+    ``raw_format='raw10'`` / ``'raw12'`` (keyword-only, with ``raw_width``) takes (H,stride) or (N,H,stride) uint8 MIPI-packed
+    frames as ``serve`` does: ``risp_raw_unpack`` writes them into uint16 frames kept per shape, device and stream, one launch
+    in front of everything else (``raw_crops`` has no packed load).
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
+    if raw_format != 'u16':
+        bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
+        F._need_gpu(raw_u16, 'raw')
+        raw_u16 = F.raw_unpack(raw_u16.contiguous(), bits, w, _packed_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
     F._need_gpu(raw_u16, 'raw')
     if raw_u16.dtype != torch.uint16 or raw_u16.dim() not in (2, 3):
         raise ValueError('expected (H,W) or (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))

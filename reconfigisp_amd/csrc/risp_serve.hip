@@ -19,9 +19,15 @@
 // store is the RGGB kernel's, so the bytes are those of flip -> risp_serve_u8 -> flip (tests/test_gpu_serve_cfa.py, torch.equal).
 // The black level is subtracted in integers, clamped at 0, before the conversion to float.  Both are a further template parameter:
 // the instantiations risp_serve_u8 launches do not see them.
+//
+// MIPI-packed RAW10 / RAW12 in (risp_serve_packed): a third template parameter, PACK = 0 / 10 / 12, which replaces row_at / ld2 /
+// ld4 - the three places that know where samples are - by the loads of risp_rawpack.h.  A thread's four centre pixels are one
+// 5-byte group or two 3-byte groups, the pairs at xl / xr half a group or one group, and mirrored along x the group at W-4-x is
+// read and reversed.  Everything behind the sample is the CFA form's; the PACK = 0 instantiations do not see the parameter.
 #include "risp_common.h"
 #include "risp_nv12.h"
 #include "risp_ops.h"
+#include "risp_rawpack.h"
 
 namespace {
 
@@ -128,6 +134,14 @@ struct ServeNv12Args : ServeCfaArgs {
 template <bool CFA, bool NV12 = false> struct serve_args { using type = ServeArgs; };
 template <> struct serve_args<true, false> { using type = ServeCfaArgs; };
 template <bool CFA> struct serve_args<CFA, true> { using type = ServeNv12Args; };
+// risp_serve_packed: the block of risp_serve_nv12 (`raw` holds the byte pointer; BGR out reads `reverse`, NV12 out `yuv`), then
+// the row pitch
+struct ServePackedArgs : ServeNv12Args {
+    int stride;                 // bytes from a packed row to the next
+};
+template <bool CFA, bool NV12, int PACK> struct serve_args_of { using type = typename serve_args<CFA, NV12>::type; };
+template <bool NV12> struct serve_args_of<true, NV12, 10> { using type = ServePackedArgs; };
+template <bool NV12> struct serve_args_of<true, NV12, 12> { using type = ServePackedArgs; };
 
 __device__ __forceinline__ float q8f(float v) {
     return floorf(__builtin_amdgcn_fmed3f(v, 0.f, 255.f) + 0.5f);   // clamp in one instruction (v is never NaN here)
@@ -152,8 +166,10 @@ constexpr int STX = 16, STY = 256 / STX, PXT = 4;      // threads across and dow
 // CFA: black level and mirror (wave-uniform at run time).  px, py and every coordinate derived from them are those of the mirrored
 // image, which is RGGB; only ld2 / ld4 / smp and the store know where the samples really are.  NV12: the store epilogue alone
 // differs - the patch's eight codes leave as two Y dwords and one UV dword of a (3H/2, W) image (risp_nv12.h)
-template <bool BIL, bool WBQ, bool CFA = false, bool NV12 = false>
-__global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CFA, NV12>::type a) {
+// PACK (with CFA): the mosaic is MIPI-packed RAW10 / RAW12 and row_at / ld2 / ld4 alone differ (risp_rawpack.h)
+template <bool BIL, bool WBQ, bool CFA = false, bool NV12 = false, int PACK = 0>
+__global__ __launch_bounds__(256) void serve_kernel(const typename serve_args_of<CFA, NV12, PACK>::type a) {
+    static_assert(PACK == 0 || CFA, "the packed instantiations use the CFA form");
     const int H = a.H, W = a.W;
     int bxi, byi, bzi;
     xcd_tile(bxi, byi, bzi);
@@ -167,11 +183,17 @@ __global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CF
     if constexpr (CFA) black = a.black, flip = a.flip;
     // row y of the mirrored image; its samples x, x + 1 (x even) and x .. x + 3 (x % 4 == 0); (float)max(s - black, 0)
     auto row_at = [&](int y) {
-        if constexpr (CFA) return bay + (size_t)(flip & 2 ? H - 1 - y : y) * W;
+        if constexpr (PACK != 0)
+            return reinterpret_cast<const uint8_t *>(a.raw) + ((size_t)n * H + (flip & 2 ? H - 1 - y : y)) * a.stride;
+        else if constexpr (CFA) return bay + (size_t)(flip & 2 ? H - 1 - y : y) * W;
         else return bay + (size_t)y * W;
     };
-    auto ld2 = [&](const uint16_t *row, int x) {
-        if constexpr (CFA) {
+    auto ld2 = [&](auto *row, int x) {
+        if constexpr (PACK != 0) {
+            const bool fx = flip & 1;
+            const ushort2 v = risp_rawpack::ld2<PACK>(row, fx ? W - 2 - x : x);
+            return fx ? ushort2{v.y, v.x} : v;
+        } else if constexpr (CFA) {
             const bool fx = flip & 1;
             const ushort2 v = *reinterpret_cast<const ushort2 *>(row + (fx ? W - 2 - x : x));
             return fx ? ushort2{v.y, v.x} : v;
@@ -179,8 +201,12 @@ __global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CF
             return *reinterpret_cast<const ushort2 *>(row + x);
         }
     };
-    auto ld4 = [&](const uint16_t *row, int x) {
-        if constexpr (CFA) {
+    auto ld4 = [&](auto *row, int x) {
+        if constexpr (PACK != 0) {
+            const bool fx = flip & 1;
+            const ushort4 v = risp_rawpack::ld4<PACK>(row, fx ? W - 4 - x : x);
+            return fx ? ushort4{v.w, v.z, v.y, v.x} : v;
+        } else if constexpr (CFA) {
             const bool fx = flip & 1;
             const ushort4 v = *reinterpret_cast<const ushort4 *>(row + (fx ? W - 4 - x : x));
             return fx ? ushort4{v.w, v.z, v.y, v.x} : v;
@@ -206,7 +232,7 @@ __global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CF
             // (the RGGB instantiations keep their own statements, here and at the store: their instruction stream stays the one
             // profiles/serve_u8.txt timed)
             if constexpr (CFA) {
-                const uint16_t *row = row_at(2 * jr[k >> 1] + (k & 1));
+                const auto *row = row_at(2 * jr[k >> 1] + (k & 1));
                 ml[k] = ld2(row, xl);
                 mc[k] = ld4(row, px);
                 mr[k] = ld2(row, xr);
@@ -322,7 +348,7 @@ __global__ __launch_bounds__(256) void serve_kernel(const typename serve_args<CF
 // the rules both serving entry points share (include/risp.h), and the argument block; `name` is the entry point's, for the message
 int serve_args_fill(const char *name, ServeArgs &a, bool &wbq, const uint16_t *raw, float divisor, const int32_t *window,
                     const float *sigma_color, const float *sigma_space, int max_window, int n_ops, const int *ops,
-                    const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W) {
+                    const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W, int raw_align = 8) {
     RISP_CHECK_ARG(raw && out, "%s: null argument", name);
     RISP_CHECK_ARG(divisor > 0.f, "%s: divisor %g", name, (double)divisor);
     RISP_CHECK_ARG(max_window == 0 || max_window == 1 || max_window == 3, "%s: window %d (0 = no bilateral, 1 or 3)", name, max_window);
@@ -330,8 +356,8 @@ int serve_args_fill(const char *name, ServeArgs &a, bool &wbq, const uint16_t *r
     RISP_CHECK_ARG(n_ops >= 0 && n_ops <= RISP_MAX_CHAIN && (n_ops == 0 || (ops && params)), "%s: bad op list", name);
     RISP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 2 && H % 2 == 0 && W >= 4 && W % 4 == 0,
                    "%s: bad shape N=%d H=%d W=%d (H even, W a multiple of 4)", name, N, H, W);
-    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(raw) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
-                   "%s: raw must be 8-byte and out 4-byte aligned", name);
+    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(raw) % raw_align == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
+                   "%s: raw must be %d-byte and out 4-byte aligned", name, raw_align);
     a.raw = raw;
     a.out = out;
     a.win = window;
@@ -361,6 +387,17 @@ int serve_args_fill(const char *name, ServeArgs &a, bool &wbq, const uint16_t *r
 }
 
 dim3 serve_grid(int N, int H, int W) { return dim3((W / 4 + STX - 1) / STX, (H / 2 + STY - 1) / STY, N); }
+
+template <int PACK, bool NV12>
+void launch_packed(bool bil, bool wbq, dim3 grid, hipStream_t s, const ServePackedArgs &a) {
+    if (bil) {
+        if (wbq) hipLaunchKernelGGL((serve_kernel<true, true, true, NV12, PACK>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((serve_kernel<true, false, true, NV12, PACK>), grid, dim3(256), 0, s, a);
+    } else {
+        if (wbq) hipLaunchKernelGGL((serve_kernel<false, true, true, NV12, PACK>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((serve_kernel<false, false, true, NV12, PACK>), grid, dim3(256), 0, s, a);
+    }
+}
 
 }  // namespace
 
@@ -489,6 +526,37 @@ int risp_serve_nv12(const uint16_t *raw, float divisor, const int32_t *window, c
         else hipLaunchKernelGGL((serve_kernel<false, false, true, true>), grid, dim3(256), 0, s, a);
     }
     RISP_LAUNCH_CHECK("risp_serve_nv12");
+    return 0;
+}
+
+int risp_serve_packed(const uint8_t *raw, int bits, int stride, float divisor, const int32_t *window, const float *sigma_color,
+                      const float *sigma_space, int max_window, int n_ops, const int *ops, const float *const *params, uint8_t *out,
+                      int reverse_channels, const int32_t *coef, int N, int H, int W, int black_level, int cfa, void *stream) {
+    const char *name = "risp_serve_packed";
+    RISP_CHECK_ARG(cfa >= 0 && cfa <= 3, "%s: cfa %d (RISP_CFA_RGGB 0, GRBG 1, GBRG 2, BGGR 3)", name, cfa);
+    RISP_CHECK_ARG(black_level >= 0 && black_level <= 65535, "%s: black_level %d outside 0 .. 65535", name, black_level);
+    ServePackedArgs a;
+    bool wbq = false;
+    if (int err = serve_args_fill(name, a, wbq, reinterpret_cast<const uint16_t *>(raw), divisor, window, sigma_color, sigma_space,
+                                  max_window, n_ops, ops, params, out, coef ? 0 : reverse_channels, N, H, W, 1))
+        return err;
+    if (int err = risp_rawpack::rawpack_check(name, bits, W, stride)) return err;
+    for (int i = 0; i < 12; ++i) a.yuv.k[i] = 0;
+    if (coef)
+        if (int err = risp_nv12::nv12_check(name, coef, a.yuv)) return err;
+    a.black = black_level;
+    a.flip = cfa;
+    a.stride = stride;
+    const dim3 grid = serve_grid(N, H, W);
+    hipStream_t s = (hipStream_t)stream;
+    if (bits == 10) {
+        if (coef) launch_packed<10, true>(max_window != 0, wbq, grid, s, a);
+        else launch_packed<10, false>(max_window != 0, wbq, grid, s, a);
+    } else {
+        if (coef) launch_packed<12, true>(max_window != 0, wbq, grid, s, a);
+        else launch_packed<12, false>(max_window != 0, wbq, grid, s, a);
+    }
+    RISP_LAUNCH_CHECK(name);
     return 0;
 }
 

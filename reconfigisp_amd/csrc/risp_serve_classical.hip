@@ -14,9 +14,13 @@
 // tonemap_kernel's pixel expression with both scales 255 (risp_origin.hip), apply_op for the rest.  With -ffp-contract=off the
 // bytes are the composed route's (tests/test_gpu_serve_classical.py, torch.equal).  Black level and Bayer phase as in
 // risp_serve_u8_cfa: the phase is a mirror of addresses, coordinates, reflection and parity live in the mirrored (RGGB) image.
+//
+// MIPI-packed RAW10 / RAW12 in (risp_serve_classical_packed): a template parameter PACK = 0 / 10 / 12 replaces row_at / ld2 / ld4
+// by the loads of risp_rawpack.h, as in serve_kernel; the PACK = 0 instantiations do not see it.
 #include "risp_common.h"
 #include "risp_nv12.h"
 #include "risp_ops.h"
+#include "risp_rawpack.h"
 
 namespace {
 
@@ -53,8 +57,13 @@ struct ClassicalArgs {
 struct ClassicalNv12Args : ClassicalArgs {
     risp_nv12::Coef yuv;
 };
-template <bool NV12> struct classical_args { using type = ClassicalArgs; };
-template <> struct classical_args<true> { using type = ClassicalNv12Args; };
+// risp_serve_classical_packed: that block (`raw` holds the byte pointer; BGR out reads `reverse`, NV12 out `yuv`), then the pitch
+struct ClassicalPackedArgs : ClassicalNv12Args {
+    int stride;                 // bytes from a packed row to the next
+};
+template <bool NV12, int PACK = 0> struct classical_args { using type = ClassicalPackedArgs; };
+template <> struct classical_args<false, 0> { using type = ClassicalArgs; };
+template <> struct classical_args<true, 0> { using type = ClassicalNv12Args; };
 
 // XCD-aware tile order, as in risp_serve.hip: XCD k works through the k-th contiguous eighth of the tile list
 __device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz) {
@@ -88,8 +97,8 @@ __device__ __forceinline__ void tone_all(float p0, float p1, f3 *px) {
 // KIND: RISP_DEMOSAIC_*.  px, py and every coordinate derived from them are those of the mirrored image, which is RGGB; only
 // row_at / ld2 / ld4 and the store know where the samples really are.  NV12: the store epilogue alone differs - the patch's
 // eight codes leave as two Y dwords and one UV dword of a (3H/2, W) image (risp_nv12.h)
-template <int KIND, bool WBQ, bool NV12 = false>
-__global__ __launch_bounds__(256) void serve_classical_kernel(const typename classical_args<NV12>::type a) {
+template <int KIND, bool WBQ, bool NV12 = false, int PACK = 0>
+__global__ __launch_bounds__(256) void serve_classical_kernel(const typename classical_args<NV12, PACK>::type a) {
     const int H = a.H, W = a.W;
     int bxi, byi, bzi;
     xcd_tile(bxi, byi, bzi);
@@ -100,15 +109,23 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
     const float div = a.divisor;
     const int black = a.black, flip = a.flip;
     f3 pix[2][PXT];
-    auto row_at = [&](int y) { return bay + (size_t)(flip & 2 ? H - 1 - y : y) * W; };
-    auto ld2 = [&](const uint16_t *row, int x) {       // samples x, x + 1 of the mirrored row (x even)
+    auto row_at = [&](int y) {
+        if constexpr (PACK != 0)
+            return reinterpret_cast<const uint8_t *>(a.raw) + ((size_t)n * H + (flip & 2 ? H - 1 - y : y)) * a.stride;
+        else return bay + (size_t)(flip & 2 ? H - 1 - y : y) * W;
+    };
+    auto ld2 = [&](auto *row, int x) {                  // samples x, x + 1 of the mirrored row (x even)
         const bool fx = flip & 1;
-        const ushort2 v = *reinterpret_cast<const ushort2 *>(row + (fx ? W - 2 - x : x));
+        ushort2 v;
+        if constexpr (PACK != 0) v = risp_rawpack::ld2<PACK>(row, fx ? W - 2 - x : x);
+        else v = *reinterpret_cast<const ushort2 *>(row + (fx ? W - 2 - x : x));
         return fx ? ushort2{v.y, v.x} : v;
     };
-    auto ld4 = [&](const uint16_t *row, int x) {       // x .. x + 3 (x % 4 == 0)
+    auto ld4 = [&](auto *row, int x) {                  // x .. x + 3 (x % 4 == 0)
         const bool fx = flip & 1;
-        const ushort4 v = *reinterpret_cast<const ushort4 *>(row + (fx ? W - 4 - x : x));
+        ushort4 v;
+        if constexpr (PACK != 0) v = risp_rawpack::ld4<PACK>(row, fx ? W - 4 - x : x);
+        else v = *reinterpret_cast<const ushort4 *>(row + (fx ? W - 4 - x : x));
         return fx ? ushort4{v.w, v.z, v.y, v.x} : v;
     };
     auto smp = [&](unsigned short s) { return (float)((int)s > black ? (int)s - black : 0); };
@@ -137,7 +154,7 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
         for (int r = R0; r < R1; ++r) {
             int y = py - 2 + r;
             y = y < 0 ? -y : (y >= H ? 2 * H - 2 - y : y);
-            const uint16_t *row = row_at(y);
+            const auto *row = row_at(y);
             const ushort2 l = ld2(row, xl), e = ld2(row, xr);
             const ushort4 c = ld4(row, px);
             const unsigned short s[8] = {left ? l.x : c.z, left ? l.y : c.y, c.x, c.y, c.z, c.w, right ? e.x : c.z, right ? e.y : c.y};
@@ -225,16 +242,16 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
     }
 }
 
-template <int KIND, bool NV12, class Args>
+template <int KIND, bool NV12, int PACK, class Args>
 void launch_kind(bool wbq, dim3 grid, hipStream_t s, const Args &a) {
-    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true, NV12>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false, NV12>), grid, dim3(256), 0, s, a);
+    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true, NV12, PACK>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false, NV12, PACK>), grid, dim3(256), 0, s, a);
 }
 
 // the rules both entry points share (include/risp.h), and the argument block; `name` is the entry point's, for the message
 int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const uint16_t *raw, float divisor, int demosaic, int n_ops,
                         const int *ops, const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W,
-                        int black_level, int cfa) {
+                        int black_level, int cfa, int raw_align = 8) {
     RISP_CHECK_ARG(raw && out, "%s: null argument", name);
     RISP_CHECK_ARG(divisor > 0.f, "%s: divisor %g", name, (double)divisor);
     RISP_CHECK_ARG(demosaic >= RISP_DEMOSAIC_NEAREST && demosaic <= RISP_DEMOSAIC_LAPLACIAN,
@@ -244,8 +261,8 @@ int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const uin
     RISP_CHECK_ARG(n_ops >= 0 && n_ops <= RISP_MAX_CHAIN && (n_ops == 0 || (ops && params)), "%s: bad op list", name);
     RISP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 4 && H % 2 == 0 && W >= 4 && W % 4 == 0,
                    "%s: bad shape N=%d H=%d W=%d (H even and >= 4, W a multiple of 4)", name, N, H, W);
-    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(raw) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
-                   "%s: raw must be 8-byte and out 4-byte aligned", name);
+    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(raw) % raw_align == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
+                   "%s: raw must be %d-byte and out 4-byte aligned", name, raw_align);
     a.raw = raw;
     a.out = out;
     a.divisor = divisor;
@@ -272,12 +289,12 @@ int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const uin
     return 0;
 }
 
-template <bool NV12, class Args>
+template <bool NV12, int PACK = 0, class Args>
 void launch_classical(int demosaic, bool wbq, hipStream_t s, const Args &a) {
     const dim3 grid((a.W / 4 + STX - 1) / STX, (a.H / 2 + STY - 1) / STY, a.N);
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, NV12>(wbq, grid, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, NV12>(wbq, grid, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST, NV12>(wbq, grid, s, a);
+    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, NV12, PACK>(wbq, grid, s, a);
+    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, NV12, PACK>(wbq, grid, s, a);
+    else launch_kind<RISP_DEMOSAIC_NEAREST, NV12, PACK>(wbq, grid, s, a);
 }
 
 }  // namespace
@@ -306,5 +323,31 @@ extern "C" int risp_serve_classical_nv12(const uint16_t *raw, float divisor, int
     if (int err = risp_nv12::nv12_check("risp_serve_classical_nv12", coef, a.yuv)) return err;
     launch_classical<true>(demosaic, wbq, (hipStream_t)stream, a);
     RISP_LAUNCH_CHECK("risp_serve_classical_nv12");
+    return 0;
+}
+
+extern "C" int risp_serve_classical_packed(const uint8_t *raw, int bits, int stride, float divisor, int demosaic, int n_ops,
+                                           const int *ops, const float *const *params, uint8_t *out, int reverse_channels,
+                                           const int32_t *coef, int N, int H, int W, int black_level, int cfa, void *stream) {
+    const char *name = "risp_serve_classical_packed";
+    ClassicalPackedArgs a;
+    bool wbq = false;
+    if (int err = classical_args_fill(name, a, wbq, reinterpret_cast<const uint16_t *>(raw), divisor, demosaic, n_ops, ops, params, out,
+                                      coef ? 0 : reverse_channels, N, H, W, black_level, cfa, 1))
+        return err;
+    if (int err = risp_rawpack::rawpack_check(name, bits, W, stride)) return err;
+    for (int i = 0; i < 12; ++i) a.yuv.k[i] = 0;
+    if (coef)
+        if (int err = risp_nv12::nv12_check(name, coef, a.yuv)) return err;
+    a.stride = stride;
+    hipStream_t s = (hipStream_t)stream;
+    if (bits == 10) {
+        if (coef) launch_classical<true, 10>(demosaic, wbq, s, a);
+        else launch_classical<false, 10>(demosaic, wbq, s, a);
+    } else {
+        if (coef) launch_classical<true, 12>(demosaic, wbq, s, a);
+        else launch_classical<false, 12>(demosaic, wbq, s, a);
+    }
+    RISP_LAUNCH_CHECK(name);
     return 0;
 }

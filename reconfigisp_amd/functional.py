@@ -784,6 +784,132 @@ def serve_classical_nv12(raw_u16, divisor, demosaic, ops, params, matrix='bt601_
     return out
 
 
+# MIPI-packed sensor frames in: the sample width of ``raw_format`` (include/risp.h states the layout); 0: one sample per
+# uint16 word
+RAW_FORMAT = {'u16': 0, 'raw10': 10, 'raw12': 12}
+
+
+def raw_format_bits(raw_format):
+    """a key of ``RAW_FORMAT`` -> its sample width (0 for 'u16')"""
+    bits = RAW_FORMAT.get(raw_format) if isinstance(raw_format, str) else None
+    if bits is None:
+        raise ValueError('unknown raw_format %r: one of %s' % (raw_format, ', '.join(RAW_FORMAT)))
+    return bits
+
+
+def packed_width(bits, stride, width=None):
+    """The pixels per row of packed frames whose rows are ``stride`` bytes: ``width``, or with None all the row holds,
+    ``stride * 8 // bits``.  A multiple of 4 (whole groups) that fits the row, else ValueError."""
+    if bits not in (10, 12):
+        raise ValueError('bits %r: 10 (RAW10) or 12 (RAW12)' % (bits,))
+    if width is None:
+        width = stride * 8 // bits
+        if width < 4 or width % 4:
+            raise ValueError('rows of %d bytes hold %d %d-bit samples, not a multiple of 4: pass the width' % (stride, width, bits))
+        return width
+    if width != int(width) or width < 4 or width % 4:
+        raise ValueError('raw width %r: a multiple of 4, at least 4' % (width,))
+    if width * bits // 8 > stride:
+        raise ValueError('raw width %d needs %d bytes per row of %d-bit samples, the rows have %d' % (width, width * bits // 8, bits, stride))
+    return int(width)
+
+
+def _packed_frames(packed_u8, bits, width, what='raw'):
+    """(N,H,stride) contiguous uint8 frames on the device -> (n, h, w, stride)"""
+    _need_gpu(packed_u8, what)
+    if packed_u8.dtype != torch.uint8 or packed_u8.dim() != 3 or not packed_u8.is_contiguous():
+        raise ValueError('expected contiguous (N,H,stride) uint8 packed frames, got %s %s' % (packed_u8.dtype, tuple(packed_u8.shape)))
+    n, h, stride = packed_u8.shape
+    return n, h, packed_width(bits, stride, width), stride
+
+
+def raw_unpack(packed_u8, bits, width=None, out=None):
+    """MIPI-packed RAW10 / RAW12 frames to one sample per word in ONE launch (``risp_raw_unpack``): (N,H,stride) or
+    (H,stride) ``torch.uint8`` on the device, ``bits`` 10 or 12 -> (N,H,W) or (H,W) ``torch.uint16``.  RAW10 keeps four
+    pixels in five bytes, RAW12 two in three (include/risp.h has the layout to the bit); ``width`` defaults to all the rows
+    hold, ``stride * 8 // bits``, which must then be a multiple of 4, and the bytes of a row behind ``width * bits / 8`` are
+    padding that is never read.  The frames may start at any byte.  With ``out`` (contiguous, 8-byte aligned) given nothing
+    is allocated and the host does not wait."""
+    _need_gpu(packed_u8, 'packed')
+    single = packed_u8.dim() == 2
+    n, h, w, stride = _packed_frames(packed_u8[None] if single else packed_u8, bits, width, 'packed')
+    shape = (h, w) if single else (n, h, w)
+    if out is None:
+        out = torch.empty(shape, device=packed_u8.device, dtype=torch.uint16)
+    elif (out.dtype != torch.uint16 or out.device != packed_u8.device or tuple(out.shape) != shape or not out.is_contiguous()
+            or out.data_ptr() % 8):
+        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
+                         % (shape, packed_u8.device, out.dtype, tuple(out.shape)))
+    L.call('risp_raw_unpack', _p(packed_u8), _p(out), bits, n, h, w, stride, _stream())
+    return out
+
+
+def _packed_out(matrix, reverse_channels, out, n, h, w, device):
+    """the matrix argument and the output of a packed serving call: BGR (N,H,W,3) without a matrix, NV12 (N,3H/2,W) with one"""
+    if matrix is None:
+        return None, _u8_out(out, (n, h, w, 3), device, 4)
+    if reverse_channels:
+        raise ValueError('reverse_channels has no meaning with a yuv matrix: the conversion knows the channel order')
+    if h % 2 or w % 2:
+        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
+    return (C.c_int * 12)(*nv12_matrix(matrix)), _u8_out(out, (n, h + h // 2, w), device, 4)
+
+
+def serve_packed(packed_u8, bits, width, divisor, ops, params, bilateral=None, reverse_channels=False, matrix=None, out=None,
+                 black_level=0, cfa='rggb'):
+    """``serve_u8`` / ``serve_nv12`` on MIPI-packed frames, still ONE launch (``risp_serve_packed``): (N,H,stride)
+    ``torch.uint8`` RAW10 / RAW12 (``bits`` 10 / 12, ``width`` pixels per row or None for all the rows hold, as in
+    ``raw_unpack``) -> (N,H,W,3) ``torch.uint8``, or with ``matrix`` (``nv12_matrix``) (N,3H/2,W) NV12.  The kernel decodes
+    the groups where it loads them; byte for byte ``serve_u8(raw_unpack(packed_u8, bits, width), ...)`` /
+    ``serve_nv12(...)`` without the uint16 frames ever being written.  The frames may start at any byte.  H even,
+    W % 4 == 0.  With ``out`` given nothing is allocated and the host does not wait."""
+    n, h, w, stride = _packed_frames(packed_u8, bits, width)
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    _check_mirror(code, h, w)
+    coef, out = _packed_out(matrix, reverse_channels, out, n, h, w, packed_u8.device)
+    keep = [_dev(p) if p is not None else None for p in params]
+    if bilateral is not None:
+        win, sc, ss, wmax = bilateral
+        if win.dtype != torch.int32 or not win.is_cuda:
+            raise ValueError('window must be an int32 device tensor')
+        keep += [win.contiguous(), _dev(sc), _dev(ss)]
+        bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
+    else:
+        bil = (None, None, None, 0)
+    L.call('risp_serve_packed', _p(packed_u8), bits, stride, float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
+           _p(out), int(bool(reverse_channels)), coef, n, h, w, int(black_level), code, _stream())
+    return out
+
+
+def serve_classical_packed(packed_u8, bits, width, divisor, demosaic, ops, params, reverse_channels=False, matrix=None, out=None,
+                           black_level=0, cfa='rggb'):
+    """``serve_classical_u8`` / ``serve_classical_nv12`` on MIPI-packed frames, still ONE launch
+    (``risp_serve_classical_packed``): ``packed_u8``, ``bits``, ``width`` and ``matrix`` as in ``serve_packed``, every other
+    argument ``serve_classical_u8``'s; byte for byte that call on ``raw_unpack(packed_u8, bits, width)``.  H even and >= 4,
+    W % 4 == 0.  With ``out`` given nothing is allocated and the host does not wait."""
+    n, h, w, stride = _packed_frames(packed_u8, bits, width)
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
+    if kind is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    _check_mirror(code, h, w)
+    coef, out = _packed_out(matrix, reverse_channels, out, n, h, w, packed_u8.device)
+    keep = [_dev(p) if p is not None else None for p in params]
+    L.call('risp_serve_classical_packed', _p(packed_u8), bits, stride, float(divisor), kind, len(ops),
+           (C.c_int * max(1, len(ops)))(*ops), L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]),
+           _p(out), int(bool(reverse_channels)), coef, n, h, w, int(black_level), code, _stream())
+    return out
+
+
 DENOISE = {'bilateral': 0, 'median': 1, 'fastnlm': 2}          # RISP_DENOISE_*
 
 

@@ -191,6 +191,11 @@ SIGNATURES = {
     'risp_bgr8_to_nv12': (_i, [_f, _f, C.POINTER(_i), _i, _i, _i, _i, _s]),
     'risp_serve_nv12': (_i, [_f, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _s]),
     'risp_serve_classical_nv12': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _s]),
+    'risp_raw_unpack': (_i, [_f, _f, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_packed': (_i, [_f, _i, _i, _fl, _f, _f, _f, _i, _i, C.POINTER(_i), _pp, _f, _i, C.POINTER(_i), _i, _i, _i, _i, _i,
+                               _s]),
+    'risp_serve_classical_packed': (_i, [_f, _i, _i, _fl, _i, _i, C.POINTER(_i), _pp, _f, _i, C.POINTER(_i), _i, _i, _i, _i, _i,
+                                         _s]),
     'risp_serve_scene_groups': (_i, [_i, _i]),
     'risp_serve_scene_stats': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _f, _i, _i, _i, _i, _i, _s]),
     'risp_serve_scene_finish': (_i, [_i, _f, _f, _f, _f, _i, _i, _i, _s]),
