@@ -1025,6 +1025,28 @@ int risp_serve_denoise_u8(const uint16_t *raw, float divisor, int demosaic, int 
                           const float *den_b, int n_post, const int *post_ops, const float *const *post_params, uint8_t *out,
                           int reverse_channels, int N, int H, int W, int black_level, int cfa, void *stream);
 
+/* risp_serve_denoise_u8's median at the other sizes OriginNoiseMedian's rule gives below a saturated parameter, one launch
+ * (risp_serve_median.hip): raw (N,H,W) uint16 mosaic of the sensor -> out (N,H,W,3) bytes.  Per pixel: risp_serve_classical_u8's
+ * input expression and demosaic, the n_pre stages pre_ops, the size x size median of the 8-bit codes, the n_post stages post_ops,
+ * the conversion of risp_quantise_u8.  Only the result is stored; its bytes are those of risp_raw_crop_cfa -> demosaic -> stages ->
+ * risp_origin_median (that size, in_scale 255, out_div 255) -> stages -> risp_quantise_u8_flip, every stage as
+ * risp_serve_classical_u8 states it: the median is the smallest code whose rank among the size * size codes of the window reaches
+ * size * size / 2 + 1, and the image border is reflect-101 in the image the median sees (the pipeline evaluated at the reflected
+ * coordinate).  pre_ops[k], post_ops[k]: the stages risp_serve_classical_u8 accepts, n_pre + n_post <= RISP_MAX_CHAIN, every stage
+ * but a SKIP needs its parameter block.
+ * A workgroup owns a 64 x 32 pixel tile: it evaluates demosaic and pre-stages for the tile and a ring (size / 2 rounded up to even
+ * rows, 4 columns up to size 9 and 8 above) into LDS as codes packed four to a dword (7776 .. 11520 bytes), one barrier (two on
+ * the image border), then the median - byte windows in registers, rank counts by sums of absolute differences, a bisection on the
+ * code - and the post-stages per thread.  black_level and cfa as in risp_serve_u8_cfa.
+ * Rules (anything else is refused before a launch and the message names it): size 5, 7, 9, 11, 13 or 15 (3 is
+ * risp_serve_denoise_u8's, 17 is not served); H even, >= 4 and > size / 2; W % 4 == 0 and > size / 2; and everything
+ * risp_serve_denoise_u8 asks: raw and out not NULL, raw 8-byte and out 4-byte aligned, whole contiguous frames; divisor > 0;
+ * demosaic 0 .. 2; 1 <= N <= 65535; cfa 0 .. 3; 0 <= black_level <= 65535. */
+int risp_serve_median_u8(const uint16_t *raw, float divisor, int demosaic, int n_pre, const int *pre_ops,
+                         const float *const *pre_params, int size, int n_post, const int *post_ops,
+                         const float *const *post_params, uint8_t *out, int reverse_channels, int N, int H, int W,
+                         int black_level, int cfa, void *stream);
+
 /* A classical denoiser beside gray-world / white-world on the serving path (risp_serve_denoise_scene.hip): the statistic of an
  * image that lies BEHIND a denoiser, and a serving launch that takes a denoiser and the scene constants together.  With
  * risp_serve_scene_stats (a scene stage whose prefix holds no denoiser) and risp_serve_scene_finish a pipeline with S scene stages

@@ -125,12 +125,13 @@ class IspModel(BaseModel):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', raw_format='u16', raw_width=None,
-              fast_denoise_scene=False):
+              fast_median=False, fast_denoise_scene=False):
         """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
         describe the sensor; ``fast_scene=True`` opts gray-world / white-world / Reinhard pipelines in to the scene route,
         whose bytes agree with the float64 reference under its tie rule - white-world-only pipelines byte for byte;
         ``fast_denoise=True`` opts pipelines with one classical bilateral / median / non-local means in to the one-launch
-        denoise route, whose bytes are the default call's; ``fast_cond=True`` opts pipelines with one to three conditional
+        denoise route, whose bytes are the default call's, at the sizes 3 / 3 / (3, 3); ``fast_median=True`` opts a median of
+        every learned size the route was measured faster at (5 .. 15) in to it as well; ``fast_cond=True`` opts pipelines with one to three conditional
         heads in to the conditional route - one more read of the mosaic per head instead of fp32 planes -, whose bytes are
         the default call's too; ``fast_denoise_scene=True`` opts pipelines with one such denoiser AND one or two of gray-world /
         white-world in to the denoise + scene route - white-world-only lists byte for byte, gray-world with the composed route's
@@ -141,7 +142,7 @@ class IspModel(BaseModel):
         with torch.no_grad():
             return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                         out_format=out_format, yuv_matrix=yuv_matrix, raw_format=raw_format, raw_width=raw_width,
-                                        fast_denoise_scene=fast_denoise_scene)
+                                        fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16', raw_width=None):

@@ -43,7 +43,7 @@ class _FixedPipeline(nn.Module):
             else:
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
-        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
+        self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' (a median of size 5 .. 15 under fast_median too) | 'denoise_scene' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
         self.last_serve_store = None            # with out_format='nv12': 'fused' (the serving launch stored NV12) | 'pass' (the conversion launch did); None for 'bgr8'
         self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
 
@@ -97,7 +97,7 @@ class _FixedPipeline(nn.Module):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', raw_format='u16', raw_width=None,
-              fast_denoise_scene=False):
+              fast_median=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -117,6 +117,12 @@ class _FixedPipeline(nn.Module):
         demosaic in to the ``'denoise'`` route (``pipeline_fusion.denoise_plan``; H even and >= 4, W % 4 == 0, learned sizes
         3 / 3 / (3, 3)): one launch with the composed route's bytes.  Where the route does not apply the call runs as
         without the flag.
+
+        ``fast_median=True`` opts a pipeline with one classical median of ANY learned size below a saturated parameter in to that
+        route (``pipeline_fusion._median_args``: 2 * int(p * 7) + 3 from image 0's parameter): size 3 takes the launch above, a
+        size in ``pipeline_fusion._MEDIAN_SIZES`` with min(H, W) > size // 2 takes ``risp_serve_median_u8`` - one launch, the
+        composed route's bytes, ``last_serve_route`` 'denoise'.  Where it does not apply (size 17, any other denoiser) the
+        call runs as without the flag.
 
         ``fast_cond=True`` opts a pipeline with one to three conditional heads (ConditionalGamma / ConditionalWbManual /
         ConditionalWbQuadratic) among element-wise stages and Crysis / Filmic curves behind a classical demosaic in to the
@@ -141,14 +147,15 @@ class _FixedPipeline(nn.Module):
         (None: all the rows hold) - the bytes of the same call on ``functional.raw_unpack`` of them, on the same route.
         ``last_serve_load`` records who decoded them, as ``pipeline_fusion.serve_load`` tells: 'fused' (the one launch of the
         'fused' / 'classical' route) or 'pass' (``risp_raw_unpack`` in front of any other route); None for 'u16'.
-        ``white_level`` is not implied by the format.  ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width`` and
+        ``white_level`` is not implied by the format.  ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width``, ``fast_median`` and
         ``fast_denoise_scene`` are keyword-only (``pipeline_fusion.serve``)."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                                     out_format=out_format, yuv_matrix=yuv_matrix, raw_format=raw_format,
-                                                    raw_width=raw_width, fast_denoise_scene=fast_denoise_scene)
+                                                    raw_width=raw_width, fast_median=fast_median,
+                                                    fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
             self.last_serve_load = serve_load(self.last_serve_route, raw_format)

@@ -388,6 +388,24 @@ def _denoise_args(mod, par):
     return cached[1]
 
 
+# the median sizes ``serve(fast_median=True)`` sends to ``risp_serve_median_u8``.  A size is listed only where
+# tools/bench_serve_median.py found the launch faster than the default call by more than the larger spread of the two legs at both
+# of its sizes, 64 x 256 x 256 and 1 x 3000 x 4000, with the bilinear and with the Malvar-He-Cutler demosaic
+# (profiles/serve_median.txt); any other size stays composed under the keyword.  functional.serve_median_u8
+# serves all six either way
+_MEDIAN_SIZES = frozenset({5, 7, 9, 11, 13, 15})
+
+
+def _median_args(mod, par):
+    """the size OriginNoiseMedian's rule gives for ``par``: 2 * int(p * 7) + 3 from image 0's parameter alone, 3 .. 17 - derived
+    once per parameter version (one host read), under a key of its own beside ``_denoise_args``' cache"""
+    key = (par.data_ptr(), par._version, tuple(par.shape))
+    cached = mod.__dict__.get('_risp_median_size')
+    if cached is None or cached[0] != key:
+        cached = mod.__dict__['_risp_median_size'] = (key, int(mod._params(par.detach(), {})['size']), par)
+    return cached[1]
+
+
 def _stage_lists(modules, param_tensors, stages):
     """(op codes, parameter blocks) of element-wise / Crysis / Filmic stages as the classical and the denoise launch take them"""
     ops =[_TONE_OP.get(type(modules[k])) or _CHAIN_OP[type(modules[k])] for k in stages]
@@ -529,7 +547,7 @@ def _packed_u16(shape, device):
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          raw_format='u16', raw_width=None, fast_denoise_scene=False):
+          raw_format='u16', raw_width=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -552,6 +570,17 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     it.  The bytes are the composed route's (``torch.equal``); the keyword exists because the default call's route is pinned by
     tests.  The denoiser's arguments are derived once per parameter version: with ``out`` given a warm call launches once,
     allocates nothing and never waits for the device.
+
+    ``fast_median=True`` opts a median of every learned size in to the ``'denoise'`` route: OriginNoiseMedian's rule gives
+    2 * int(p * 7) + 3 from image 0's parameter, which is 3 only below p = 1/7 and 9 at the initial value, so for most found
+    pipelines ``fast_denoise=True`` composes.  Where ``denoise_plan`` is not None, the denoiser is OriginNoiseMedian and the
+    geometry is the classical route's, size 3 takes ``risp_serve_denoise_u8`` as under ``fast_denoise`` and a size in
+    ``_MEDIAN_SIZES`` with min(H, W) > size // 2 takes ``risp_serve_median_u8`` - one launch, packed 8-bit codes in LDS, the
+    composed route's bytes (``torch.equal``); the route reported is ``'denoise'``, the same route at another size.  Anything
+    else - size 17 (a saturated parameter), a size measured no faster (profiles/serve_median.txt), every other denoiser, two
+    denoisers, scene stages, proxies, other geometry - runs exactly as without the keyword.  The size is derived once per
+    parameter version: with ``out`` given a warm call launches once, allocates nothing and never waits for the device.
+    ``fast_denoise=True`` keeps its meaning: it alone still composes at size 5.
 
     ``fast_cond=True`` opts in to the ``'cond'`` route where ``cond_plan`` is not None - one to three conditional heads among
     element-wise stages and Crysis / Filmic curves behind a classical demosaic -, the geometry is the classical route's,
@@ -602,8 +631,8 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     ``raw_width`` a multiple of 4.  With ``out`` given a warm call allocates nothing.  ``raw_format='u16'`` is the call
     without the keyword.
 
-    ``out_format``, ``yuv_matrix``, ``raw_format`` and ``raw_width`` are keyword-only, and so is ``fast_denoise_scene``: it
-    stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
+    ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width`` and ``fast_median`` are keyword-only, and so is
+    ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
     if raw_format != 'u16':
@@ -629,14 +658,14 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         if out is not None:
             F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed)
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median)
         return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
     return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed)
+                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median)
 
 
 def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None):
+               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False):
     """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
     NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
     With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
@@ -669,6 +698,18 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
             post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
             return F.serve_denoise_u8(frames(), divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
                                       reverse_channels, dst(), black_level, cfa), 'denoise'
+    if fast_median and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
+        plan = denoise_plan(modules)
+        if plan is not None and type(modules[plan[2]]) is T.OriginNoiseMedian:
+            size = _median_args(modules[plan[2]], param_tensors[plan[2]])
+            if size == 3 or (size in _MEDIAN_SIZES and min(h, w) > size // 2):
+                pre_ops, pre_params = _stage_lists(modules, param_tensors, plan[1])
+                post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
+                if size == 3:
+                    return F.serve_denoise_u8(frames(), divisor, plan[0], pre_ops, pre_params, 'median', (3,), post_ops, post_params,
+                                              reverse_channels, dst(), black_level, cfa), 'denoise'
+                return F.serve_median_u8(frames(), divisor, plan[0], pre_ops, pre_params, size, post_ops, post_params,
+                                         reverse_channels, dst(), black_level, cfa), 'denoise'
     if fast_denoise_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
         plan = denoise_scene_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None

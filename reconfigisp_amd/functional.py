@@ -966,6 +966,45 @@ def serve_denoise_u8(raw_u16, divisor, kind, pre_ops, pre_params, denoise, denoi
     return out
 
 
+MEDIAN_SIZES = (5, 7, 9, 11, 13, 15)          # what risp_serve_median_u8 serves: OriginNoiseMedian's sizes for 1/7 <= p < 1
+
+
+def serve_median_u8(raw_u16, divisor, kind, pre_ops, pre_params, size, post_ops, post_params, reverse_channels=False, out=None,
+                    black_level=0, cfa='rggb'):
+    """``serve_denoise_u8`` with a median of ``size`` 5, 7, 9, 11, 13 or 15, still ONE launch (``risp_serve_median_u8``):
+    (N,H,W) ``torch.uint16`` frames on the device -> (N,H,W,3) ``torch.uint8``.  ``serve_classical_u8``'s input expression and
+    demosaic ``kind``, the stages ``pre_ops`` / ``pre_params``, the ``size`` x ``size`` median of the 8-bit codes, the stages
+    ``post_ops`` / ``post_params`` (both lists hold what ``serve_classical_u8`` accepts, at most 8 stages together), then
+    ``quantise_u8``'s conversion.  Only the result is stored; its bytes are those of ``raw_crops`` -> ``origin_demosaic`` /
+    ``chain_forward`` / ``origin_tonemap`` -> ``origin_denoise(x, 'median', {'size': size}, (255, 255))`` -> stages ->
+    ``quantise_u8``.  Size 3 is ``serve_denoise_u8``'s and 17 (a saturated parameter) is not served: both are refused.  H even,
+    >= 4 and > size // 2, W % 4 == 0 and > size // 2; ``black_level`` and ``cfa`` as in ``serve_u8``.  With ``out`` given nothing
+    is allocated and the host does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(pre_ops) != len(pre_params) or len(post_ops) != len(post_params):
+        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(pre_ops), len(post_ops), len(pre_params), len(post_params)))
+    code_d = DEMOSAIC.get(kind) if isinstance(kind, str) else None
+    if code_d is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (kind, ', '.join(DEMOSAIC)))
+    if size != int(size) or int(size) not in MEDIAN_SIZES:
+        raise ValueError('median size %r: one of %s (3 is serve_denoise_u8\'s)' % (size, ', '.join(str(k) for k in MEDIAN_SIZES)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = raw_u16.shape
+    _check_mirror(code, h, w)
+    out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
+    pre = [_dev(p) if p is not None else None for p in pre_params]
+    post = [_dev(p) if p is not None else None for p in post_params]
+    L.call('risp_serve_median_u8', _p(raw_u16), float(divisor), code_d, len(pre_ops), (C.c_int * max(1, len(pre_ops)))(*pre_ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in pre] or [None]), int(size), len(post_ops),
+           (C.c_int * max(1, len(post_ops)))(*post_ops), L.ptr_array([p.data_ptr() if p is not None else None for p in post] or [None]),
+           _p(out), int(bool(reverse_channels)), n, h, w, int(black_level), code, _stream())
+    return out
+
+
 OP_GAIN3_Q8, OP_TONE_REINHARD = 9, 10      # stages of serve_scene_u8 / serve_scene_stats only: they take serve_scene_finish's constants
 SCENE_MEAN3, SCENE_MAX3, SCENE_LOGLUM = 0, 1, 2       # RISP_SCENE_*
 # (device, stream, tag, shape) -> float32 scratch of the scene route (partials, constants), kept until release_scene_scratch()

@@ -204,6 +204,7 @@ SIGNATURES = {
     'risp_serve_cond_finish': (_i, [_f, _i, _f, C.POINTER(_i), _i, _fl, _f, _i, _s]),
     'risp_serve_denoise_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, _i, _f, _f, _i, C.POINTER(_i), _pp, _f,
                                    _i, _i, _i, _i, _i, _i, _s]),
+    'risp_serve_median_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, C.POINTER(_i), _pp, _f, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_denoise_stats': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, _i, _f, _f, _i, C.POINTER(_i), _pp, _i, _f,
                                       _i, _i, _i, _i, _i, _s]),
     'risp_serve_denoise_scene_u8': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _i, _i, _f, _f, _i, C.POINTER(_i), _pp, _f,
