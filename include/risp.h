@@ -909,6 +909,41 @@ int risp_serve_classical_packed(const uint8_t *raw, int bits, int stride, float 
                                 const float *const *params, uint8_t *out, int reverse_channels, const int32_t *coef, int N,
                                 int H, int W, int black_level, int cfa, void *stream);
 
+/* Lens-shading (vignetting and colour-shading) correction into the serving path (risp_shade.hip, risp_shade.h): a gain per pixel
+ * and Bayer plane, interpolated from a coarse mesh - DNG's GainMap, the LSC block of a hardware ISP.  An integer function, fixed
+ * to the bit.  A map is gains (GH,GW,4) uint16 contiguous, Q12 (4096 is gain 1.0; every uint16 value is allowed, so a gain is
+ * below 16), and cell_log2 = k, 2 <= k <= 8.  Node (i,j) sits at sensor pixel (i << k, j << k); GH == ((H-1) >> k) + 2 and
+ * GW == ((W-1) >> k) + 2 exactly: the node below / right of the last pixel exists and no read is conditional.  The plane of
+ * pixel (y,x) is c = 2 * (y & 1) + (x & 1), y and x being the sensor's coordinates - those of the frame as stored, before any cfa
+ * mirror: the map belongs to the sensor, not to the RGGB view.  With cell = 1 << k, i = y >> k, fy = y & (cell-1), j = x >> k,
+ * fx = x & (cell-1), G = gains:
+ *     top = (cell - fx) * G[i][j][c]   + fx * G[i][j+1][c]
+ *     bot = (cell - fx) * G[i+1][j][c] + fx * G[i+1][j+1][c]
+ *     g   = ((cell - fy) * top + fy * bot + (1 << (2k-1))) >> 2k          the Q12 gain of the pixel
+ *     s'  = min((max(s - black_level, 0) * g + 2048) >> 12, 65535)        the shaded sample
+ * in unsigned 32-bit arithmetic: the largest sums are 2^16 * 65535 + 2^15 and 65535 * 65535 + 2048, below 2^32 and not below
+ * 2^31.  The black level leaves inside the definition: s' is a sample with black level 0, and the divisor behind it is
+ * white_level - black_level.  There is no clamp at the white level.
+ *
+ * risp_raw_shade: frames -> out (N,H,W) uint16 contiguous of shaded samples, one launch, bits / 8 bytes read and 2 written per
+ * pixel plus the map.  The front of every serving route without a fused shading load.  bits 16: raw is rows of `stride` bytes
+ * of uint16 (stride even and >= 2 W, raw 2-byte aligned; image n starts at byte n * H * stride); bits 10 / 12: the packed
+ * layouts above with their rules - the launch decodes and shades, risp_raw_unpack is not needed.  Rules (anything else is
+ * refused before a launch, the message names the value): no NULL, N and H >= 1, W >= 4 and W % 4 == 0, the rules of the map,
+ * gains and out 8-byte aligned, black_level 0 .. 65535. */
+int risp_raw_shade(const void *raw, int bits, int stride, uint16_t *out, const uint16_t *gains, int cell_log2, int GH, int GW,
+                   int black_level, int N, int H, int W, void *stream);
+
+/* risp_serve_classical_u8 / risp_serve_classical_nv12 with the shading inside the load, still one launch: coef NULL stores BGR
+ * (N,H,W,3) with reverse_channels, non-NULL stores NV12 (N,3H/2,W) with that matrix, as in risp_serve_classical_packed; divisor
+ * is white_level - black_level.  The float that enters the demosaic is (float)s' / divisor; nothing behind the sample changes, so
+ *     out == risp_serve_classical_u8 | risp_serve_classical_nv12 (risp_raw_shade(raw, black_level), divisor, ..., black_level 0, cfa)
+ * byte for byte.  uint16 frames only.  Rules: those of risp_serve_classical_u8 plus the rules of the map. */
+int risp_serve_classical_shaded(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                                const float *const *params, uint8_t *out, int reverse_channels, const int32_t *coef,
+                                const uint16_t *gains, int cell_log2, int GH, int GW, int N, int H, int W, int black_level,
+                                int cfa, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

@@ -545,9 +545,37 @@ def _packed_u16(shape, device):
     return F._scene_buffer(device, 'raw_u16', shape, torch.uint16)
 
 
+# (route, raw_format) whose one launch applies the lens-shading correction in its load.  Only ('classical', 'u16') has such a
+# launch (risp_serve_classical_shaded), and it is listed only if it beats risp_raw_shade followed by the uint16 call by more than
+# the larger spread of the two legs in all four rows of profiles/serve_shade.txt (two pipelines, two sizes) - the
+# rule of _FUSED_LOAD and _MEDIAN_SIZES.  The verdict line of that file is this table.  Measured: the fused launch is 2.7 to 4.8 us
+# faster in all four rows (0.86-0.97 x), which clears the spread in three of them; in the fourth one round of the two-launch leg ran
+# 9.5 us long.  Not all four, so the table is empty and the classical route takes the shade launch too;
+# functional.serve_classical_shaded keeps the one-launch form.  The headline kernel gets no fused shading: its 6 x 8 neighbourhood
+# per thread lost with packed loads already, and nobody has measured it with shading.
+_FUSED_SHADE = frozenset()
+
+
+def serve_shade(route, raw_format):
+    """Who applies a lens shading on ``route`` (a name of ``SERVE_ROUTES``) for frames of ``raw_format``: 'fused' - the route's
+    one launch shades in its load (``risp_serve_classical_shaded``) - or 'pass' - ``risp_raw_shade`` writes shaded uint16 frames
+    first (decoding packed ones on the way) and the route runs as for them.  A pure function of its arguments: what ``serve``
+    does and what ``last_serve_shade`` reports for a call with ``lens_shading``."""
+    if route not in SERVE_ROUTES:
+        raise ValueError('unknown route %r: one of %s' % (route, ', '.join(SERVE_ROUTES)))
+    F.raw_format_bits(raw_format)
+    return 'fused' if (route, raw_format) in _FUSED_SHADE else 'pass'
+
+
+def _shaded_u16(shape, device):
+    """the uint16 frames a route without a fused shading load shades into, kept per (shape, device, stream); not the unpack
+    buffer: a caller may hold that one's frames"""
+    return F._scene_buffer(device, 'shaded_u16', shape, torch.uint16)
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          raw_format='u16', raw_width=None, fast_median=False, fast_denoise_scene=False):
+          raw_format='u16', raw_width=None, lens_shading=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -631,7 +659,17 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     ``raw_width`` a multiple of 4.  With ``out`` given a warm call allocates nothing.  ``raw_format='u16'`` is the call
     without the keyword.
 
-    ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width`` and ``fast_median`` are keyword-only, and so is
+    ``lens_shading=(gains, cell)`` corrects vignetting and colour shading in front of everything else: a contiguous (GH,GW,4)
+    uint16 device tensor of Q12 gains on a mesh of ``cell`` pixels (a power of two from 4 to 256; ``F.shading_check``,
+    ``F.shading_map`` builds one), per plane 2 * (y & 1) + (x & 1) of the frame as stored, whatever ``cfa`` - include/risp.h has
+    the integer definition.  The bytes returned are those of the same call on ``F.raw_shade(frames, lens_shading, black_level)``
+    with ``white_level - black_level`` and black level 0, on the route that call takes.  Where ``serve_shade`` says 'fused' the
+    classical route shades in its one launch (``risp_serve_classical_shaded``); everywhere else ``risp_raw_shade`` writes the
+    shaded frames once into uint16 frames kept per shape, device and stream, one launch more, and with packed input decodes them
+    on the way: no ``risp_raw_unpack`` is issued.  The gains are never read on the host.  With ``out`` given a warm call
+    allocates nothing and never waits for the device.  None is the call without the keyword.
+
+    ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width``, ``lens_shading`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -653,26 +691,44 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         n, h, w = raw_u16.shape
     F._check_mirror(code, h, w)
     divisor = white_level - black_level
+    shade = None
+    if lens_shading is not None:
+        if w % 4:
+            raise ValueError('lens_shading on frames %d wide: W must be a multiple of 4' % w)
+        F.shading_check(lens_shading, h, w, raw_u16.device)
+        # behind the shading the samples have black level 0 and the white level white_level - black_level
+        shade, white_level, black_level = (lens_shading, int(black_level)), divisor, 0
     coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
     if coef is not None:
         if out is not None:
             F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median)
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade)
         return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
     return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median)
+                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade)
 
 
 def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False):
+               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False, shade=None):
     """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
     NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
     With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
     from the allocator take, 'fused' and 'classical' load the packed bytes where ``serve_load`` says so, and every other
-    route runs on ``frames()``, the cached uint16 stack the unpack launch fills"""
+    route runs on ``frames()``, the cached uint16 stack the unpack launch fills.
+    With ``shade`` = ((gains, cell), the sensor's black level), ``black_level`` being 0 and ``white_level`` the divisor: the
+    route is again the one uint16 frames from the allocator take, 'classical' shades in its load where ``serve_shade`` says so
+    (uint16 input, 8-byte aligned), and every other route runs on ``frames()``, the cached uint16 stack the shade launch fills
+    from the uint16 or the packed frames"""
     device = raw_u16.device
-    if packed is None:
+    if shade is not None:
+        (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
+        fmt, bits = ('u16', 16) if packed is None else (packed[3], packed[1])
+
+        def frames():
+            return F.raw_shade(raw_u16, shade[0], shade[1], bits, w, _shaded_u16((n, h, w), device))
+        packed = None                                       # the shade launch decodes: nothing behind it sees packed bytes
+    elif packed is None:
         n, h, w = raw_u16.shape
         aligned = raw_u16.data_ptr() % 8 == 0
 
@@ -739,6 +795,9 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
             and aligned):
         kind, stages = _classical_split(modules)
         ops, params = _stage_lists(modules, param_tensors, stages)
+        if shade is not None and fmt == 'u16' and serve_shade('classical', fmt) == 'fused' and raw_u16.data_ptr() % 8 == 0:
+            return F.serve_classical_shaded(raw_u16, shade[0], divisor, kind, ops, params, reverse_channels, coef,
+                                            out if coef is None else nv12_out, shade[1], cfa), 'classical'
         if packed is not None and serve_load('classical', packed[3]) == 'fused':
             return F.serve_classical_packed(packed[0], packed[1], w, divisor, kind, ops, params, reverse_channels, coef,
                                             out if coef is None else nv12_out, black_level, cfa), 'classical'
@@ -779,7 +838,7 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
                 out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16',
-                raw_width=None):
+                raw_width=None, lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -797,10 +856,29 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     ``raw_format='raw10'`` / ``'raw12'`` (keyword-only, with ``raw_width``) takes (H,stride) or (N,H,stride) uint8 MIPI-packed
     frames as ``serve`` does: ``risp_raw_unpack`` writes them into uint16 frames kept per shape, device and stream, one launch
     in front of everything else (``raw_crops`` has no packed load).
+    ``lens_shading=(gains, cell)`` (keyword-only, as in ``serve``) shades the whole frame once in front of ``raw_crops``:
+    ``risp_raw_shade`` writes uint16 frames kept per shape, device and stream - from packed frames too, in place of the unpack
+    launch - and everything behind it runs with ``white_level - black_level`` and black level 0.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
+    if lens_shading is not None:
+        if raw_format != 'u16':
+            bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
+        else:
+            if (not isinstance(raw_u16, torch.Tensor) or raw_u16.dtype != torch.uint16 or raw_u16.dim() not in (2, 3)
+                    or raw_u16.shape[-1] % 4):
+                raise ValueError('lens_shading takes (H,W) or (N,H,W) uint16 frames with W a multiple of 4, got %s %s'
+                                 % (getattr(raw_u16, 'dtype', type(raw_u16)), tuple(getattr(raw_u16, 'shape', ()))))
+            bits, w = 16, raw_u16.shape[-1]
+        F._need_gpu(raw_u16, 'raw')
+        if black_level != int(black_level) or not 0 <= black_level < white_level:
+            raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
+        F.shading_check(lens_shading, raw_u16.shape[-2], w, raw_u16.device)
+        raw_u16 = F.raw_shade(raw_u16.contiguous(), lens_shading, int(black_level), bits, w,
+                              _shaded_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
+        white_level, black_level, raw_format = white_level - black_level, 0, 'u16'
     if raw_format != 'u16':
         bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
         F._need_gpu(raw_u16, 'raw')

@@ -17,10 +17,19 @@
 //
 // MIPI-packed RAW10 / RAW12 in (risp_serve_classical_packed): a template parameter PACK = 0 / 10 / 12 replaces row_at / ld2 / ld4
 // by the loads of risp_rawpack.h, as in serve_kernel; the PACK = 0 instantiations do not see it.
+//
+// Lens-shading correction in (risp_serve_classical_shaded): a template parameter SHADE replaces smp alone - the float that enters
+// smp(s) / div is the shaded sample of risp_shade.h - on uint16 frames (PACK == 0).  The map belongs to the sensor, the kernel
+// works in mirrored coordinates: a row's eight columns px-2 .. px+5 are the eight sensor columns b .. b+7 (b = px - 2, or
+// W - 6 - px read backwards), b = 2 mod 4, so they fall into the aligned groups [b, b+1], [b+2, b+5], [b+6, b+7], each inside one
+// cell.  Per row and group the two planes of the node columns beside it are interpolated down the cell (a group in the cell of
+// the one before it reuses them: at cell >= 8 two of three do), then each sample interpolates across.  A reflected sample
+// carries the gain of the place it was read from.  The existing instantiations do not see the parameter.
 #include "risp_common.h"
 #include "risp_nv12.h"
 #include "risp_ops.h"
 #include "risp_rawpack.h"
+#include "risp_shade.h"
 
 namespace {
 
@@ -61,9 +70,15 @@ struct ClassicalNv12Args : ClassicalArgs {
 struct ClassicalPackedArgs : ClassicalNv12Args {
     int stride;                 // bytes from a packed row to the next
 };
-template <bool NV12, int PACK = 0> struct classical_args { using type = ClassicalPackedArgs; };
-template <> struct classical_args<false, 0> { using type = ClassicalArgs; };
-template <> struct classical_args<true, 0> { using type = ClassicalNv12Args; };
+// risp_serve_classical_shaded: the NV12 block (BGR out reads `reverse`, NV12 out `yuv`), then the map
+struct ClassicalShadedArgs : ClassicalNv12Args {
+    const uint16_t *gains;      // (GH,GW,4) Q12
+    int cell_log2, GW;
+};
+template <bool NV12, int PACK = 0, bool SHADE = false> struct classical_args { using type = ClassicalPackedArgs; };
+template <> struct classical_args<false, 0, false> { using type = ClassicalArgs; };
+template <> struct classical_args<true, 0, false> { using type = ClassicalNv12Args; };
+template <bool NV12> struct classical_args<NV12, 0, true> { using type = ClassicalShadedArgs; };
 
 // XCD-aware tile order, as in risp_serve.hip: XCD k works through the k-th contiguous eighth of the tile list
 __device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz) {
@@ -97,8 +112,9 @@ __device__ __forceinline__ void tone_all(float p0, float p1, f3 *px) {
 // KIND: RISP_DEMOSAIC_*.  px, py and every coordinate derived from them are those of the mirrored image, which is RGGB; only
 // row_at / ld2 / ld4 and the store know where the samples really are.  NV12: the store epilogue alone differs - the patch's
 // eight codes leave as two Y dwords and one UV dword of a (3H/2, W) image (risp_nv12.h)
-template <int KIND, bool WBQ, bool NV12 = false, int PACK = 0>
-__global__ __launch_bounds__(256) void serve_classical_kernel(const typename classical_args<NV12, PACK>::type a) {
+template <int KIND, bool WBQ, bool NV12 = false, int PACK = 0, bool SHADE = false>
+__global__ __launch_bounds__(256) void serve_classical_kernel(const typename classical_args<NV12, PACK, SHADE>::type a) {
+    static_assert(!SHADE || PACK == 0, "the fused shading load reads uint16 frames");
     const int H = a.H, W = a.W;
     int bxi, byi, bzi;
     xcd_tile(bxi, byi, bzi);
@@ -128,13 +144,56 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
         else v = *reinterpret_cast<const ushort4 *>(row + (fx ? W - 4 - x : x));
         return fx ? ushort4{v.w, v.z, v.y, v.x} : v;
     };
-    auto smp = [&](unsigned short s) { return (float)((int)s > black ? (int)s - black : 0); };
+    // g: the sample's Q12 gain (SHADE only)
+    auto smp = [&](unsigned short s, [[maybe_unused]] unsigned g) {
+        if constexpr (SHADE) return (float)risp_shade::shade(s, (unsigned)black, g);
+        else return (float)((int)s > black ? (int)s - black : 0);
+    };
+    // SHADE: g[t] = the gain at mirrored row y (already reflected into the image), mirrored column px - 2 + t.  The centre four
+    // always; the pairs left / right of them only with `lo` / `hi` (false at a border patch, and for the nearest demosaic, which
+    // has no stencil): no node is read for a column outside the image, and such a g[t] is not used
+    [[maybe_unused]] auto row_gains = [&](int y, bool lo, bool hi, unsigned *g) {
+        if constexpr (SHADE) {
+            const int k = a.cell_log2;
+            const bool fx = flip & 1;
+            const risp_shade::MapRow map(a.gains, a.GW, k, flip & 2 ? H - 1 - y : y);
+            const int b = fx ? W - 6 - px : px - 2;     // sensor column of gs[0]
+            const bool va = fx ? hi : lo, vc = fx ? lo : hi;
+            unsigned gs[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // in sensor order
+            const int jb = (b + 2) >> k;
+            const uint2 nl = map.node(jb), nr = map.node(jb + 1);
+            const risp_shade::Cell cb{nl, nr};
+            const unsigned fb = risp_shade::cell_fx(b + 2, k);
+            gs[2] = cb.gain<0>(fb, k), gs[3] = cb.gain<1>(fb + 1, k), gs[4] = cb.gain<0>(fb + 2, k), gs[5] = cb.gain<1>(fb + 3, k);
+            if constexpr (KIND != RISP_DEMOSAIC_NEAREST) {
+                if (va) {
+                    const int ja = b >> k;
+                    risp_shade::Cell ca = cb;
+                    if (ja != jb) ca = risp_shade::Cell{map.node(ja), nl};       // the cell before: ja + 1 == jb
+                    const unsigned fa = risp_shade::cell_fx(b, k);
+                    gs[0] = ca.gain<0>(fa, k), gs[1] = ca.gain<1>(fa + 1, k);
+                }
+                if (vc) {
+                    const int jc = (b + 6) >> k;
+                    risp_shade::Cell cc = cb;
+                    if (jc != jb) cc = risp_shade::Cell{nr, map.node(jc + 1)};   // the cell behind: jc == jb + 1
+                    const unsigned fc = risp_shade::cell_fx(b + 6, k);
+                    gs[6] = cc.gain<0>(fc, k), gs[7] = cc.gain<1>(fc + 1, k);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 8; ++t) g[t] = fx ? gs[7 - t] : gs[t];
+        }
+    };
 
     if constexpr (KIND == RISP_DEMOSAIC_NEAREST) {
         // ---- no stencil: the patch's own two quads, in the [0,1] domain (serve_kernel's branch)
         const ushort4 r0 = ld4(row_at(py), px), r1 = ld4(row_at(py + 1), px);
-        const float R0 = smp(r0.x) / div, G10 = smp(r0.y) / div, R1 = smp(r0.z) / div, G11 = smp(r0.w) / div;
-        const float G20 = smp(r1.x) / div, B0 = smp(r1.y) / div, G21 = smp(r1.z) / div, B1 = smp(r1.w) / div;
+        [[maybe_unused]] unsigned g0[8] = {}, g1[8] = {};                   // columns px .. px + 3 are [2] .. [5]
+        row_gains(py, false, false, g0);
+        row_gains(py + 1, false, false, g1);
+        const float R0 = smp(r0.x, g0[2]) / div, G10 = smp(r0.y, g0[3]) / div, R1 = smp(r0.z, g0[4]) / div, G11 = smp(r0.w, g0[5]) / div;
+        const float G20 = smp(r1.x, g1[2]) / div, B0 = smp(r1.y, g1[3]) / div, G21 = smp(r1.z, g1[4]) / div, B1 = smp(r1.w, g1[5]) / div;
         pix[0][0] = pix[0][1] = {B0, G10, R0};
         pix[0][2] = pix[0][3] = {B1, G11, R1};
         pix[1][0] = pix[1][1] = {B0, G20, R0};
@@ -158,8 +217,16 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
             const ushort2 l = ld2(row, xl), e = ld2(row, xr);
             const ushort4 c = ld4(row, px);
             const unsigned short s[8] = {left ? l.x : c.z, left ? l.y : c.y, c.x, c.y, c.z, c.w, right ? e.x : c.z, right ? e.y : c.y};
+            [[maybe_unused]] unsigned gm[8] = {}, g[8] = {};
+            if constexpr (SHADE) {
+                row_gains(y, left, right, gm);
+                const unsigned gr[8] = {left ? gm[0] : gm[4], left ? gm[1] : gm[3], gm[2], gm[3], gm[4], gm[5], right ? gm[6] : gm[4],
+                                        right ? gm[7] : gm[3]};
 #pragma unroll
-            for (int k = 0; k < 8; ++k) m[r][k] = (smp(s[k]) / div) * 255.f;       // risp_raw_crop_cfa's expression, x 255 on load
+                for (int k = 0; k < 8; ++k) g[k] = gr[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) m[r][k] = (smp(s[k], g[k]) / div) * 255.f; // risp_raw_crop_cfa's expression, x 255 on load
         }
 #pragma unroll
         for (int p = 0; p < 2; ++p)
@@ -242,10 +309,10 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
     }
 }
 
-template <int KIND, bool NV12, int PACK, class Args>
+template <int KIND, bool NV12, int PACK, bool SHADE, class Args>
 void launch_kind(bool wbq, dim3 grid, hipStream_t s, const Args &a) {
-    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true, NV12, PACK>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false, NV12, PACK>), grid, dim3(256), 0, s, a);
+    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true, NV12, PACK, SHADE>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false, NV12, PACK, SHADE>), grid, dim3(256), 0, s, a);
 }
 
 // the rules both entry points share (include/risp.h), and the argument block; `name` is the entry point's, for the message
@@ -289,12 +356,12 @@ int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const uin
     return 0;
 }
 
-template <bool NV12, int PACK = 0, class Args>
+template <bool NV12, int PACK = 0, bool SHADE = false, class Args>
 void launch_classical(int demosaic, bool wbq, hipStream_t s, const Args &a) {
     const dim3 grid((a.W / 4 + STX - 1) / STX, (a.H / 2 + STY - 1) / STY, a.N);
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, NV12, PACK>(wbq, grid, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, NV12, PACK>(wbq, grid, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST, NV12, PACK>(wbq, grid, s, a);
+    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, NV12, PACK, SHADE>(wbq, grid, s, a);
+    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, NV12, PACK, SHADE>(wbq, grid, s, a);
+    else launch_kind<RISP_DEMOSAIC_NEAREST, NV12, PACK, SHADE>(wbq, grid, s, a);
 }
 
 }  // namespace
@@ -348,6 +415,30 @@ extern "C" int risp_serve_classical_packed(const uint8_t *raw, int bits, int str
         if (coef) launch_classical<true, 12>(demosaic, wbq, s, a);
         else launch_classical<false, 12>(demosaic, wbq, s, a);
     }
+    RISP_LAUNCH_CHECK(name);
+    return 0;
+}
+
+extern "C" int risp_serve_classical_shaded(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
+                                           const float *const *params, uint8_t *out, int reverse_channels, const int32_t *coef,
+                                           const uint16_t *gains, int cell_log2, int GH, int GW, int N, int H, int W,
+                                           int black_level, int cfa, void *stream) {
+    const char *name = "risp_serve_classical_shaded";
+    ClassicalShadedArgs a;
+    bool wbq = false;
+    if (int err = classical_args_fill(name, a, wbq, raw, divisor, demosaic, n_ops, ops, params, out, coef ? 0 : reverse_channels, N, H,
+                                      W, black_level, cfa))
+        return err;
+    if (int err = risp_shade::shade_check(name, gains, cell_log2, GH, GW, black_level, H, W)) return err;
+    for (int i = 0; i < 12; ++i) a.yuv.k[i] = 0;
+    if (coef)
+        if (int err = risp_nv12::nv12_check(name, coef, a.yuv)) return err;
+    a.gains = gains;
+    a.cell_log2 = cell_log2;
+    a.GW = GW;
+    hipStream_t s = (hipStream_t)stream;
+    if (coef) launch_classical<true, 0, true>(demosaic, wbq, s, a);
+    else launch_classical<false, 0, true>(demosaic, wbq, s, a);
     RISP_LAUNCH_CHECK(name);
     return 0;
 }

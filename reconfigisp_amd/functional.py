@@ -910,6 +910,139 @@ def serve_classical_packed(packed_u8, bits, width, divisor, demosaic, ops, param
     return out
 
 
+def shading_check(shading, h, w, device=None):
+    """A lens shading ``(gains, cell)`` for H x W frames, checked on the host before anything is launched -> (gains, k, GH, GW)
+    with cell = 1 << k.  ``gains``: a contiguous (GH,GW,4) ``torch.uint16`` device tensor, Q12 (4096 is gain 1.0; every value
+    is legal, so none is read here and the host never waits), 8-byte aligned, node (i,j) at sensor pixel (i * cell, j * cell)
+    and plane 2 * (y & 1) + (x & 1) of the frame as stored; ``cell``: a power of two from 4 to 256;
+    GH == (H-1) // cell + 2 and GW == (W-1) // cell + 2 exactly (include/risp.h has the definition)."""
+    try:
+        gains, cell = shading
+    except (TypeError, ValueError):
+        raise ValueError('a lens shading is (gains, cell): a (GH,GW,4) uint16 device tensor and the cell size in pixels') from None
+    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
+        raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
+    k = cell.bit_length() - 1
+    if not isinstance(gains, torch.Tensor) or gains.dtype != torch.uint16:
+        raise ValueError('lens shading gains must be a uint16 tensor (Q12), got %s' % (getattr(gains, 'dtype', type(gains)),))
+    gh, gw = ((int(h) - 1) >> k) + 2, ((int(w) - 1) >> k) + 2
+    if tuple(gains.shape) != (gh, gw, 4) or not gains.is_contiguous():
+        raise ValueError('lens shading gains of a %d x %d frame with cell %d must be contiguous (%d,%d,4): (H-1) // cell + 2 by '
+                         '(W-1) // cell + 2 nodes of four planes; got %s' % (h, w, cell, gh, gw, tuple(gains.shape)))
+    _need_gpu(gains, 'lens shading gains')
+    if device is not None and gains.device != device:
+        raise ValueError('lens shading gains live on %s, the frames on %s' % (gains.device, device))
+    if gains.data_ptr() % 8:
+        raise ValueError('lens shading gains must be 8-byte aligned')
+    return gains, k, gh, gw
+
+
+def shading_map(gain, H, W, cell):
+    """Host helper: a float gain image -> the (GH,GW,4) ``torch.uint16`` Q12 node grid of a lens shading for H x W frames (on
+    the CPU; move it to the device once).  ``gain``: (4,h,w) - a plane per Bayer position 2 * (y & 1) + (x & 1) - or (h,w) for
+    all four, any size from 1 x 1, DNG GainMap style: its corner samples sit on the frame's corners (0,0) and (H-1,W-1).  It is
+    resampled bilinearly in float64 at the nodes (i * cell, j * cell) - the nodes behind the last pixel take the image's linear
+    continuation - and rounded to Q12.  A resampled value outside 0 .. 65535 / 4096 or not finite is refused."""
+    import numpy as np
+    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
+        raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
+    if H != int(H) or W != int(W) or H < 1 or W < 1:
+        raise ValueError('frame size %r x %r' % (H, W))
+    g = np.asarray(gain.detach().cpu().numpy() if isinstance(gain, torch.Tensor) else gain, dtype=np.float64)
+    if g.ndim == 2:
+        g = np.broadcast_to(g, (4,) + g.shape)
+    if g.ndim != 3 or g.shape[0] != 4 or g.shape[1] < 1 or g.shape[2] < 1:
+        raise ValueError('a gain image is (4,h,w) or (h,w), got %s' % (tuple(g.shape),))
+    if not np.isfinite(g).all():
+        raise ValueError('the gain image has values that are not finite')
+    k = cell.bit_length() - 1
+    gh, gw = ((int(H) - 1) >> k) + 2, ((int(W) - 1) >> k) + 2
+
+    def axis(nodes, full, size):
+        # node positions in image samples, the two samples beside each and the weight of the second
+        pos = np.arange(nodes, dtype=np.float64) * cell * ((size - 1) / (full - 1) if full > 1 else 0.0)
+        if size == 1:
+            return np.zeros(nodes, dtype=np.int64), np.zeros(nodes, dtype=np.int64), np.zeros(nodes)
+        lo = np.clip(np.floor(pos).astype(np.int64), 0, size - 2)
+        return lo, lo + 1, pos - lo
+
+    y0, y1, ty = axis(gh, int(H), g.shape[1])
+    x0, x1, tx = axis(gw, int(W), g.shape[2])
+    ty, tx = ty[None, :, None], tx[None, None, :]
+    top = g[:, y0][:, :, x0] * (1 - tx) + g[:, y0][:, :, x1] * tx
+    bot = g[:, y1][:, :, x0] * (1 - tx) + g[:, y1][:, :, x1] * tx
+    q = np.rint((top * (1 - ty) + bot * ty) * 4096.0)
+    if not np.isfinite(q).all() or q.min() < 0 or q.max() > 65535:
+        raise ValueError('gains outside 0 .. 65535 / 4096 at the nodes (%g .. %g): Q12 in uint16 cannot hold them'
+                         % (q.min() / 4096.0, q.max() / 4096.0))
+    return torch.from_numpy(np.ascontiguousarray(q.transpose(1, 2, 0).astype(np.uint16)))
+
+
+def raw_shade(frames, shading, black_level=0, bits=16, width=None, out=None):
+    """Lens-shading correction of sensor frames in ONE launch (``risp_raw_shade``): (N,H,W) or (H,W) ``torch.uint16`` frames
+    on the device (``bits=16``), or (N,H,stride) / (H,stride) ``torch.uint8`` MIPI-packed RAW10 / RAW12 (``bits`` 10 / 12,
+    ``width`` as in ``raw_unpack``) -> (N,H,W) or (H,W) ``torch.uint16`` shaded samples
+    min((max(s - black_level, 0) * g + 2048) >> 12, 65535), g the Q12 gain interpolated from ``shading`` = (gains, cell)
+    (``shading_check``; include/risp.h has the definition to the bit).  The black level leaves here: what comes out has black
+    level 0 and the divisor white_level - black_level.  W % 4 == 0.  With ``out`` (contiguous, 8-byte aligned) given nothing
+    is allocated and the host does not wait."""
+    _need_gpu(frames, 'frames')
+    if bits == 16:
+        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
+        if width is not None and width != frames.shape[-1]:
+            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
+        single = frames.dim() == 2
+        (n, h, w), stride = ((1,) + tuple(frames.shape) if single else tuple(frames.shape)), 2 * frames.shape[-1]
+        if w < 4 or w % 4:
+            raise ValueError('frames %d wide: W must be a multiple of 4' % w)
+    else:
+        single = frames.dim() == 2
+        n, h, w, stride = _packed_frames(frames[None] if single else frames, bits, width, 'frames')
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    gains, k, gh, gw = shading_check(shading, h, w, frames.device)
+    shape = (h, w) if single else (n, h, w)
+    if out is None:
+        out = torch.empty(shape, device=frames.device, dtype=torch.uint16)
+    elif (out.dtype != torch.uint16 or out.device != frames.device or tuple(out.shape) != shape or not out.is_contiguous()
+            or out.data_ptr() % 8):
+        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
+                         % (shape, frames.device, out.dtype, tuple(out.shape)))
+    L.call('risp_raw_shade', _p(frames), int(bits), stride, _p(out), _p(gains), k, gh, gw, int(black_level), n, h, w, _stream())
+    return out
+
+
+def serve_classical_shaded(raw_u16, shading, divisor, demosaic, ops, params, reverse_channels=False, matrix=None, out=None,
+                           black_level=0, cfa='rggb'):
+    """``serve_classical_u8`` / ``serve_classical_nv12`` with the lens-shading correction inside the load, still ONE launch
+    (``risp_serve_classical_shaded``): (N,H,W) ``torch.uint16`` frames and ``shading`` = (gains, cell) as in ``raw_shade`` ->
+    (N,H,W,3) ``torch.uint8``, or with ``matrix`` (``nv12_matrix``) (N,3H/2,W) NV12.  ``divisor`` is
+    white_level - black_level.  Byte for byte ``serve_classical_u8(raw_shade(raw_u16, shading, black_level), divisor, ...,
+    black_level=0, cfa=cfa)`` without the shaded frames ever being written.  H even and >= 4, W % 4 == 0.  With ``out`` given
+    nothing is allocated and the host does not wait."""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    if len(ops) != len(params):
+        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
+    if kind is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = raw_u16.shape
+    _check_mirror(code, h, w)
+    gains, k, gh, gw = shading_check(shading, h, w, raw_u16.device)
+    coef, out = _packed_out(matrix, reverse_channels, out, n, h, w, raw_u16.device)
+    keep = [_dev(p) if p is not None else None for p in params]
+    L.call('risp_serve_classical_shaded', _p(raw_u16), float(divisor), kind, len(ops), (C.c_int * max(1, len(ops)))(*ops),
+           L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), _p(out),
+           int(bool(reverse_channels)), coef, _p(gains), k, gh, gw, n, h, w, int(black_level), code, _stream())
+    return out
+
+
 DENOISE = {'bilateral': 0, 'median': 1, 'fastnlm': 2}          # RISP_DENOISE_*
 
 

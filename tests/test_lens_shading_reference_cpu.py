@@ -1,0 +1,233 @@
+"""No GPU: the lens-shading definition of include/risp.h as tests/lens_shading_reference.py restates it - hand-worked vectors, the
+extremes that signed 32-bit arithmetic gets wrong, the wrong variants that the GPU test's frames and maps tell apart -, the host
+helper ``functional.shading_map``, the host refusals, and the plumbing: signatures, ``serve_shade`` and its table against the
+verdict line of profiles/serve_shade.txt."""
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import lens_shading_reference as LS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(4, 4), (4, 8), (6, 12), (34, 68)]
+CELLS = [4, 8, 16, 64]
+
+
+def _hand_map():
+    """4 x 4 frame, k = 2: a 2 x 2 map; plane 0 and plane 3 by hand, planes 1 and 2 far away"""
+    g = np.zeros((2, 2, 4), dtype=np.uint16)
+    g[..., 0] = [[4096, 8192], [12288, 16384]]
+    g[..., 1] = 111
+    g[..., 2] = 222
+    g[..., 3] = [[4000, 5000], [6000, 7001]]
+    return g
+
+
+def test_hand_worked_vectors():
+    g = _hand_map()
+    gain = LS.gain_ref(g, 2, 4, 4)
+    # a pixel on a node: the node's own gain, 1.0 - the sample minus the black level
+    assert gain[0, 0] == 4096
+    # mid-cell (2,2), plane 0: top = 2 * 4096 + 2 * 8192 = 24576, bot = 2 * 12288 + 2 * 16384 = 57344,
+    # (2 * 24576 + 2 * 57344 + 8) >> 4 = 163848 >> 4 = 10240 = 2.5
+    assert gain[2, 2] == 10240
+    # the last pixel (3,3), plane 3: top = 4000 + 3 * 5000 = 19000, bot = 6000 + 3 * 7001 = 27003,
+    # (19000 + 3 * 27003 + 8) >> 4 = 100017 >> 4 = 6251
+    assert gain[3, 3] == 6251
+    # planes 1 and 2 hold constants: (0,1) and (1,0)
+    assert gain[0, 1] == 111 and gain[1, 0] == 222 and gain[1, 1] != gain[0, 0]
+    raw = np.zeros((4, 4), dtype=np.uint16)
+    raw[0, 0], raw[2, 2], raw[3, 3] = 1000, 1001, 100
+    out = LS.shade_ref(raw, 0, g, 2)
+    assert out[0, 0] == 1000
+    assert out[3, 3] == 153                                  # (100 * 6251 + 2048) >> 12 = 627148 >> 12
+    out = LS.shade_ref(raw, 1, g, 2)
+    assert out[2, 2] == 2500                                 # (1000 * 10240 + 2048) >> 12 = 10242048 >> 12 = 2500 (2500.5 down)
+    assert out[0, 1] == 0                                    # below the black level: clamped, not wrapped
+    raw[3, 3] = 65535
+    assert LS.shade_ref(raw, 0, g, 2)[3, 3] == 65535         # 100014 clamps
+
+
+@pytest.mark.parametrize('h,w', SHAPES)
+@pytest.mark.parametrize('k', [2, 3, 4, 6, 8])
+def test_a_flat_map_is_the_black_level_alone(k, h, w):
+    rng = np.random.default_rng(h + k)
+    raw = rng.integers(0, 65536, (2, h, w)).astype(np.uint16)
+    flat = np.full(LS.map_shape(h, w, k) + (4,), 4096, dtype=np.uint16)
+    for b in (0, 64):
+        assert np.array_equal(LS.shade_ref(raw, b, flat, k), np.maximum(raw.astype(np.int64) - b, 0).astype(np.uint16))
+
+
+def test_the_extremes_need_unsigned_arithmetic():
+    h, w, k = 4, 8, 8
+    full = np.full(LS.map_shape(h, w, k) + (4,), 65535, dtype=np.uint16)
+    assert (LS.gain_ref(full, k, h, w) == 65535).all()       # (2^16 * 65535 + 2^15) >> 16
+    raw = np.full((h, w), 65535, dtype=np.uint16)
+    out = LS.shade_ref(raw, 0, full, k)                      # (65535 * 65535 + 2048) >> 12 = 1048544, clamped
+    assert (out == 65535).all()
+    assert not np.array_equal(LS.shade_signed32(raw, 0, full, k), out)
+    raw[...] = 4097                                          # 4097 * 65535 + 2048 < 2^31: the gain's sum alone is wrong when signed
+    assert not np.array_equal(LS.shade_signed32(raw, 0, full, k), LS.shade_ref(raw, 0, full, k))
+    # and with everything small the signed form is the definition: the variant is a faithful restatement
+    small = LS.random_map(h, w, 2, 1, 2048, 8191)
+    raw = np.random.default_rng(0).integers(0, 4096, (h, w)).astype(np.uint16)
+    assert np.array_equal(LS.shade_signed32(raw, 7, small, 2), LS.shade_ref(raw, 7, small, 2))
+
+
+def test_the_four_planes_are_told_apart():
+    h, w, k = 6, 12, 2
+    g = np.zeros(LS.map_shape(h, w, k) + (4,), dtype=np.uint16)
+    g[..., :] = [4096, 8192, 12288, 16384]
+    gain = LS.gain_ref(g, k, h, w)
+    assert (gain[0::2, 0::2] == 4096).all() and (gain[0::2, 1::2] == 8192).all()
+    assert (gain[1::2, 0::2] == 12288).all() and (gain[1::2, 1::2] == 16384).all()
+
+
+@pytest.mark.parametrize('h,w', SHAPES)
+@pytest.mark.parametrize('cell', CELLS)
+def test_the_wrong_variants_show_on_the_gpu_tests_frames(cell, h, w):
+    """in the shaded samples of the full-range frames, and in the bytes a nearest-demosaic, stage-free pipeline serves for a frame
+    of samples 0 .. 15: gains below 8 keep the shaded samples below 128, the white level, so nothing clips and one LSB of a shaded
+    sample is two 8-bit codes"""
+    import raw_packed_reference as PR
+    k = cell.bit_length() - 1
+    g = LS.random_map(h, w, k, seed=h + cell)
+    assert g.min() >= 2048 and g.max() <= 32767 and len(np.unique(g[0, 0])) == 4
+    full = PR.full_range_frame(1, h, w, 12, seed=3)[0]
+    low = PR.low_bit_frame(1, h, w, seed=4)[0]
+    good_low = LS.shade_ref(low, 0, g, k)
+    assert good_low.max() < 128
+    good_bytes = LS.nearest_bytes(good_low, 128)
+    for variant in ('swap_x', 'nearest', 'trunc'):
+        assert not np.array_equal(LS.shade_ref(full, 64, g, k, variant), LS.shade_ref(full, 64, g, k)), variant
+        assert not np.array_equal(LS.nearest_bytes(LS.shade_ref(low, 0, g, k, variant), 128), good_bytes), variant
+
+
+def test_nearest_bytes_is_the_kernels_expression():
+    s = np.array([[10, 20], [30, 40]], dtype=np.uint16)
+    out = LS.nearest_bytes(s, 128)
+    code = lambda v: int(np.float32(v) / np.float32(128) * np.float32(255))
+    assert out[0, 0].tolist() == [code(40), code(20), code(10)] and out[1, 1].tolist() == [code(40), code(30), code(10)]
+
+
+# ---------------------------------------------------------------- functional.shading_map
+def test_shading_map_of_a_constant_and_of_a_ramp():
+    import reconfigisp_amd.functional as F
+    m = F.shading_map(np.full((3, 5), 1.5), 34, 68, 16)
+    assert m.dtype == torch.uint16 and tuple(m.shape) == LS.map_shape(34, 68, 4) + (4,) and (m == 6144).all()
+    m = F.shading_map(torch.full((4, 1, 1), 2.0), 6, 12, 4)
+    assert tuple(m.shape) == (3, 4, 4) and (m == 8192).all()
+    # a ramp over the frame: gain 1 + y / 64 + x / 128 at pixel (y,x), given as a 5 x 9 image with its corners on the frame's
+    h, w, cell = 33, 65, 8
+    ys, xs = np.linspace(0, h - 1, 5)[:, None], np.linspace(0, w - 1, 9)[None, :]
+    planes = np.stack([(1 + c) + ys / 64 + xs / 128 for c in range(4)])
+    m = F.shading_map(planes, h, w, cell).numpy()
+    gh, gw = LS.map_shape(h, w, 3)
+    assert m.shape == (gh, gw, 4)
+    i, j = np.mgrid[0:gh, 0:gw]
+    for c in range(4):
+        want = np.rint(((1 + c) + i * cell / 64 + j * cell / 128) * 4096)       # the nodes behind the last pixel included
+        assert np.array_equal(m[..., c], want.astype(np.uint16)), c
+
+
+def test_shading_map_refusals():
+    import reconfigisp_amd.functional as F
+    with pytest.raises(ValueError, match='65535'):
+        F.shading_map(np.full((2, 2), 16.0), 8, 8, 4)         # 65536 in Q12
+    with pytest.raises(ValueError, match='65535'):
+        F.shading_map(np.full((2, 2), -0.5), 8, 8, 4)
+    with pytest.raises(ValueError, match='finite'):
+        F.shading_map(np.array([[1.0, np.nan]]), 8, 8, 4)
+    with pytest.raises(ValueError, match='cell'):
+        F.shading_map(np.ones((2, 2)), 8, 8, 3)
+    with pytest.raises(ValueError, match='cell'):
+        F.shading_map(np.ones((2, 2)), 8, 8, 512)
+    with pytest.raises(ValueError, match=r'\(4,h,w\)'):
+        F.shading_map(np.ones((3, 2, 2)), 8, 8, 4)
+    assert F.shading_map(np.full((2, 2), 65535 / 4096), 8, 8, 4).numpy().max() == 65535
+
+
+# ---------------------------------------------------------------- plumbing
+def _serve_functions():
+    from reconfigisp_amd.codes.models.isp_model import IspModel
+    from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
+    from reconfigisp_amd.codes.models.modules.isp_universal import IspUniversal
+    from reconfigisp_amd.codes.models.modules.origin_universal import OriginUniversal
+    return [(PF.serve, 'serve'), (PF.serve_frame, 'serve_frame')] + [
+        (getattr(cls, name), name) for cls in (IspUniversal, OriginUniversal, IspModel) for name in ('serve', 'serve_frame')]
+
+
+def test_lens_shading_is_keyword_only_with_default_none_on_all_eight_functions():
+    fns = _serve_functions()
+    assert len(fns) == 8
+    for fn, name in fns:
+        pars = inspect.signature(fn).parameters
+        p = pars['lens_shading']
+        assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is None, fn
+        names = list(pars)
+        if name == 'serve':
+            assert names[-2:] == ['fast_median', 'fast_denoise_scene'], fn
+            assert names[names.index('lens_shading') - 1] == 'raw_width', fn
+        else:
+            assert names[-1] == 'lens_shading', fn
+
+
+def test_serve_shade_is_a_pure_table_and_the_table_is_the_measured_verdict():
+    from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
+    for route in PF.SERVE_ROUTES:
+        for fmt in ('u16', 'raw10', 'raw12'):
+            answer = PF.serve_shade(route, fmt)
+            assert answer in ('fused', 'pass')
+            assert answer == ('fused' if (route, fmt) in PF._FUSED_SHADE else 'pass')
+    assert PF._FUSED_SHADE <= {('classical', 'u16')}
+    with pytest.raises(ValueError, match='unknown route'):
+        PF.serve_shade('nope', 'u16')
+    with pytest.raises(ValueError, match='raw_format'):
+        PF.serve_shade('classical', 'raw14')
+    text = open(os.path.join(ROOT, 'profiles', 'serve_shade.txt')).read()
+    lines = re.findall(r'^verdict: _FUSED_SHADE = (.*)$', text, flags=re.M)
+    assert len(lines) == 1, 'profiles/serve_shade.txt states the verdict in one line'
+    measured = frozenset() if lines[0].strip() == 'none' else frozenset(tuple(t.split('/')) for t in lines[0].split())
+    assert measured == PF._FUSED_SHADE
+
+
+def test_host_refusals_come_before_the_device():
+    """on CPU tensors: whatever is wrong with the map is named before the device is asked for, and a right map on the CPU is
+    refused for being there"""
+    import reconfigisp_amd.functional as F
+    from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
+    h, w = 34, 68
+    good = torch.zeros(LS.map_shape(h, w, 4) + (4,), dtype=torch.uint16)
+    with pytest.raises(ValueError, match=r'\(4,6,4\)'):
+        F.shading_check((torch.zeros((3, 6, 4), dtype=torch.uint16), 16), h, w)      # GH one too small
+    with pytest.raises(ValueError, match=r'\(4,6,4\)'):
+        F.shading_check((torch.zeros((4, 7, 4), dtype=torch.uint16), 16), h, w)
+    with pytest.raises(ValueError, match='uint16'):
+        F.shading_check((good.to(torch.int16), 16), h, w)
+    with pytest.raises(ValueError, match='uint16'):
+        F.shading_check((good.float(), 16), h, w)
+    for cell in (3, 512, 2, 16.0, True):
+        with pytest.raises(ValueError, match='cell'):
+            F.shading_check((good, cell), h, w)
+    with pytest.raises(ValueError, match='gains, cell'):
+        F.shading_check(good, h, w)
+    with pytest.raises(RuntimeError, match='lens shading gains'):
+        F.shading_check((good, 16), h, w)                    # a CPU tensor
+    # serve and serve_frame check before they launch: CPU frames never reach a kernel
+    raw = torch.zeros((1, h, w), dtype=torch.uint16)
+    for call in (lambda: PF.serve([], [], raw, 1023.0, lens_shading=(good, 16)),
+                 lambda: PF.serve_frame([], [], raw, 1023.0, 32, 16, lens_shading=(good, 3))):
+        with pytest.raises((RuntimeError, ValueError)):
+            call()
+
+
+def test_both_entry_points_are_declared():
+    from reconfigisp_amd import lib as L
+    header = open(os.path.join(ROOT, 'include', 'risp.h')).read()
+    for name, nargs in (('risp_raw_shade', 13), ('risp_serve_classical_shaded', 19)):
+        assert re.search(r'^int %s\(' % name, header, flags=re.M), name
+        assert name in L.SIGNATURES and len(L.SIGNATURES[name][1]) == nargs
