@@ -14,9 +14,8 @@
 //     image      36x72  40x72  40x72  44x80  44x80  48x80   bytes per channel; 7776 .. 11520 bytes of LDS in all
 //     patches    324    360    360    440    440    480     against the 256 inside the tile
 //
-//   phase 1  the patches of 2 x 4 pixels that cover the LDS image - demosaic and the P stages restated from
-//            serve_denoise_kernel's phase 1 expression for expression (risp_serve_denoise.hip: the same loads, reflection inside
-//            the mosaic, per-site expressions, 8-bit rounding, tone curves) - stored as the codes q8(value x 255), the median's
+//   phase 1  the patches of 2 x 4 pixels that cover the LDS image - demosaic and the P stages as every route evaluates a patch
+//            (risp_serve_patch.h: the loads, reflection inside the mosaic, per-site expressions, 8-bit rounding, tone curves) - stored as the codes q8(value x 255), the median's
 //            input (stage_tile4<true> / median4_kernel's staging form them from the fp32 planes of the composed route).
 //            Patches outside the image are skipped; after a barrier the ring positions outside the image that a window can
 //            reach copy the code at the reflect-101 IMAGE coordinate from LDS.  H > K/2 and W > K/2 make that a single
@@ -33,89 +32,18 @@
 // With -ffp-contract=off the bytes are the composed route's (tests/test_gpu_serve_median.py, torch.equal).  Black level and
 // Bayer phase as in risp_serve_u8_cfa: the phase is a mirror of addresses; coordinates, reflection, parity and the tile grid
 // live in the mirrored (RGGB) image.
-#include "risp_common.h"
-#include "risp_ops.h"
+#include "risp_serve_patch.h"
 
 namespace {
 
-using namespace risp_ops;
+using namespace risp_patch;
 
-// clip(v * 255, 0, 255).astype(uint8): the product in fp32, the conversion truncates (risp_quantise_u8)
-__device__ __forceinline__ unsigned u8(float v) {
-    float t = v * 255.f;
-    t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
-    return (unsigned)(int)t;
-}
-
-// the 8-bit code of a value in the 0..255 domain (risp_origin.hip q8; v is never NaN here)
-__device__ __forceinline__ float q8(float v) { return floorf(__builtin_amdgcn_fmed3f(v, 0.f, 255.f) + 0.5f); }
-
-__device__ __forceinline__ float hable(float t) {
-    const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f;
-    return (t * (A * t + C * B) + D * E) / (t * (A * t + B) + D * F) - E / F;
-}
-
-struct MedianArgs {
-    const uint16_t *raw;        // (N,H,W) mosaic of the sensor
+struct MedianArgs : PatchArgs {
     uint8_t *out;               // (N,H,W,3)
-    float divisor;
-    int n_pre, n_ops, N, H, W;  // stages 0 .. n_pre - 1 run in front of the median, n_pre .. n_ops - 1 behind it
     int reverse;                // store R, G, B instead of B, G, R
-    int black;                  // subtracted from every sample in integers, clamped at 0
-    int flip;                   // RISP_CFA_*: bit 0 mirrors x, bit 1 mirrors y
-    int ops[RISP_MAX_CHAIN];
-    const float *params[RISP_MAX_CHAIN];
 };
 
-// XCD-aware tile order, as in risp_serve.hip: XCD k works through the k-th contiguous eighth of the tile list
-__device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz) {
-    bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-    if ((total & 7u) == 0) {
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned t = (lin & 7u) * (total >> 3) + (lin >> 3);
-        bx = t % gridDim.x;
-        by = (t / gridDim.x) % gridDim.y;
-        bz = t / (gridDim.x * gridDim.y);
-    }
-}
-
-constexpr int STX = 16, STY = 256 / STX, PXT = 4;      // threads across and down a workgroup: a 64 x 32 pixel tile
-constexpr int TILE_W = STX * PXT, TILE_H = STY * 2;
-
-// a tone curve on NPX pixels: tonemap_kernel's pixel expression with si = so = 255, p0 / p1 as tonemap_prepare_kernel forms them
-template <bool FILMIC, int NPX>
-__device__ __forceinline__ void tone_all(float p0, float p1, f3 *px) {
-    auto curve = [&](float x) {
-        float v = x * 255.f / 255.f;
-        v = fmaxf(v, 0.f);
-        if (FILMIC) v = hable(v * p0) * p1;
-        else v = 1.f - __expf(-v * p0);
-        return q8(v * 255.f) * (1.f / 255.f);
-    };
-#pragma unroll
-    for (int i = 0; i < NPX; ++i) px[i] = {curve(px[i].b), curve(px[i].g), curve(px[i].r)};
-}
-
-// stages k0 .. k1 - 1 on NPX pixels in registers: the two tone curves here (their per-image constants are cheap enough to form
-// in every thread), the rest in risp_ops.h
-template <int NPX, bool WBQ>
-__device__ __forceinline__ void run_stages(const MedianArgs &a, int k0, int k1, int n, f3 *px) {
-    for (int k = k0; k < k1; ++k) {
-        const int op = a.ops[k];
-        const float *p = a.params[k];
-        if (op == RISP_OP_TONE_CRYSIS) {               // p (N,1): lum_adapted
-            tone_all<false, NPX>(0.5f / (p[n] + 0.05f), 0.f, px);
-        } else if (op == RISP_OP_TONE_FILMIC) {        // p (N,2): white_point, exposure_bias
-            tone_all<true, NPX>(p[2 * n + 1], 1.f / hable(fmaxf(p[2 * n], 0.01f) * 11.2f), px);
-        } else {
-            apply_op<NPX, WBQ>(op, p, n, px);
-        }
-    }
-}
-
-// KIND: RISP_DEMOSAIC_*, K: the median's size.  Every coordinate is one of the mirrored image, which is RGGB; only row_at /
-// ld2 / ld4 and the store know where the samples really are
+// KIND: RISP_DEMOSAIC_*, K: the median's size.  Every coordinate is one of the mirrored image, which is RGGB
 template <int KIND, int K, bool WBQ>
 __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
     constexpr int R = K / 2;
@@ -128,21 +56,8 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
     int bxi, byi, bzi;
     xcd_tile(bxi, byi, bzi);
     const int n = bzi, x0 = bxi * TILE_W, y0 = byi * TILE_H;
-    const uint16_t *bay = a.raw + (size_t)n * H * W;
-    const float div = a.divisor;
-    const int black = a.black, flip = a.flip;
-    auto row_at = [&](int y) { return bay + (size_t)(flip & 2 ? H - 1 - y : y) * W; };
-    auto ld2 = [&](const uint16_t *row, int x) {       // samples x, x + 1 of the mirrored row (x even)
-        const bool fx = flip & 1;
-        const ushort2 v = *reinterpret_cast<const ushort2 *>(row + (fx ? W - 2 - x : x));
-        return fx ? ushort2{v.y, v.x} : v;
-    };
-    auto ld4 = [&](const uint16_t *row, int x) {       // x .. x + 3 (x % 4 == 0)
-        const bool fx = flip & 1;
-        const ushort4 v = *reinterpret_cast<const ushort4 *>(row + (fx ? W - 4 - x : x));
-        return fx ? ushort4{v.w, v.z, v.y, v.x} : v;
-    };
-    auto smp = [&](unsigned short s) { return (float)((int)s > black ? (int)s - black : 0); };
+    const int flip = a.flip;
+    const Mosaic mo(a, n);
 
     // ---- phase 1: demosaic and the stages in front of the median for every patch of the LDS image that lies in the image
 #pragma unroll 1
@@ -150,68 +65,10 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
         const int pr = t / PCOLS, pc = t - pr * PCOLS;
         const int px = x0 - RING_X + pc * PXT, py = y0 - RING_Y + pr * 2;
         if (px < 0 || px >= W || py < 0 || py >= H) continue;      // W % 4 == 0, H % 2 == 0: a patch is in or out as a whole
-        f3 pix[2][PXT];
-        if constexpr (KIND == RISP_DEMOSAIC_NEAREST) {
-            // no stencil: the patch's own two quads, in the [0,1] domain (serve_kernel's branch)
-            const ushort4 r0 = ld4(row_at(py), px), r1 = ld4(row_at(py + 1), px);
-            const float R0 = smp(r0.x) / div, G10 = smp(r0.y) / div, R1 = smp(r0.z) / div, G11 = smp(r0.w) / div;
-            const float G20 = smp(r1.x) / div, B0 = smp(r1.y) / div, G21 = smp(r1.z) / div, B1 = smp(r1.w) / div;
-            pix[0][0] = pix[0][1] = {B0, G10, R0};
-            pix[0][2] = pix[0][3] = {B1, G11, R1};
-            pix[1][0] = pix[1][1] = {B0, G20, R0};
-            pix[1][2] = pix[1][3] = {B1, G21, R1};
-        } else {
-            // m[r][c]: mosaic row py - 2 + r, column px - 2 + c in the 0..255 domain, reflect-101 over radius 2 - the loads and
-            // border rules of serve_classical_kernel.  Bilinear needs the inner ring alone: rows 1 .. 4
-            constexpr bool LAP = KIND == RISP_DEMOSAIC_LAPLACIAN;
-            constexpr int R0 = LAP ? 0 : 1, R1 = LAP ? 6 : 5;
-            const bool left = px > 0, right = px + 4 < W;
-            const int xl = left ? px - 2 : 0, xr = right ? px + 4 : px;
-            float m[6][8];
+        const Patch d = mo.patch<KIND>(px, py);
+        f3 pix[2][PXT];                                            // (the patch is copied into the kernel's own array: risp_serve_patch.h)
 #pragma unroll
-            for (int r = R0; r < R1; ++r) {
-                int y = py - 2 + r;
-                y = y < 0 ? -y : (y >= H ? 2 * H - 2 - y : y);
-                const uint16_t *row = row_at(y);
-                const ushort2 l = ld2(row, xl), e = ld2(row, xr);
-                const ushort4 c = ld4(row, px);
-                const unsigned short s[8] = {left ? l.x : c.z, left ? l.y : c.y, c.x, c.y, c.z, c.w, right ? e.x : c.z, right ? e.y : c.y};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) m[r][k] = (smp(s[k]) / div) * 255.f;       // risp_raw_crop_cfa's expression, x 255 on load
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int i = 0; i < PXT; ++i) {
-                    // origin_demosaic_kernel's expressions; py is even and px a multiple of 4: the site is known at compile time
-                    auto s = [&](int dy, int dx) { return m[2 + p + dy][2 + i + dx]; };
-                    const float c = s(0, 0);
-                    const float cross = s(-1, 0) + s(1, 0) + s(0, -1) + s(0, 1);
-                    const float diag = s(-1, -1) + s(-1, 1) + s(1, -1) + s(1, 1);
-                    const float hor = s(0, -1) + s(0, 1), ver = s(-1, 0) + s(1, 0);
-                    float g_rb, rb_hor, rb_ver, rb_diag;
-                    if constexpr (LAP) {
-                        const float fh = s(0, -2) + s(0, 2), fv = s(-2, 0) + s(2, 0), far = fh + fv;
-                        g_rb = (4.f * c + 2.f * cross - far) / 8.f;
-                        rb_hor = (5.f * c + 4.f * hor - diag - fh + 0.5f * fv) / 8.f;
-                        rb_ver = (5.f * c + 4.f * ver - diag - fv + 0.5f * fh) / 8.f;
-                        rb_diag = (6.f * c + 2.f * diag - 1.5f * far) / 8.f;
-                    } else {
-                        g_rb = cross / 4.f;
-                        rb_hor = hor / 2.f;
-                        rb_ver = ver / 2.f;
-                        rb_diag = diag / 4.f;
-                    }
-                    const bool er = p == 0, ec = (i & 1) == 0;      // R at (even,even), B at (odd,odd)
-                    float R_, G_, B_;
-                    if (er && ec) { R_ = c; G_ = g_rb; B_ = rb_diag; }
-                    else if (er && !ec) { G_ = c; R_ = rb_hor; B_ = rb_ver; }
-                    else if (!er && ec) { G_ = c; R_ = rb_ver; B_ = rb_hor; }
-                    else { B_ = c; G_ = g_rb; R_ = rb_diag; }
-                    const float inv255 = 1.f / 255.f;
-                    pix[p][i] = {q8(B_) * inv255, q8(G_) * inv255, q8(R_) * inv255};
-                }
-        }
+        for (int i = 0; i < 2 * PXT; ++i) (&pix[0][0])[i] = (&d.p[0][0])[i];
         run_stages<2 * PXT, WBQ>(a, 0, a.n_pre, n, &pix[0][0]);
         // the median's domain: the 8-bit code of value x in_scale (255), four of a row to a dword
         auto code = [&](float v) { return (unsigned)q8(v * 255.f); };
@@ -335,24 +192,7 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
                     (float)((cr >> (8 * i)) & 0xffu) * inv255};
 
         run_stages<PXT, WBQ>(a, a.n_pre, a.n_ops, n, o);
-
-        // the result alone: 4 pixels x 3 bytes of a row are three dwords (the row offset is a multiple of 12 bytes).  Mirrored
-        // along x the four pixels land at W-4-px in reverse order (the bytes of a pixel keep theirs)
-        unsigned b[PXT][3];
-#pragma unroll
-        for (int c = 0; c < PXT; ++c) {
-            const f3 v = o[c], m = o[PXT - 1 - c];
-            const bool fx = flip & 1;
-            const unsigned vb = u8(fx ? m.b : v.b), vg = u8(fx ? m.g : v.g), vr = u8(fx ? m.r : v.r);
-            b[c][0] = a.reverse ? vr : vb;
-            b[c][1] = vg;
-            b[c][2] = a.reverse ? vb : vr;
-        }
-        unsigned *dst = reinterpret_cast<unsigned *>(
-            a.out + (((size_t)n * H + (flip & 2 ? H - 1 - py - p : py + p)) * W + (flip & 1 ? W - 4 - px : px)) * 3);
-        dst[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
-        dst[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
-        dst[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+        store_bgr4(a.out, n, H, W, py + p, px, flip, a.reverse, o);
     }
 }
 
@@ -379,50 +219,21 @@ extern "C" int risp_serve_median_u8(const uint16_t *raw, float divisor, int demo
                                     const float *const *post_params, uint8_t *out, int reverse_channels, int N, int H, int W,
                                     int black_level, int cfa, void *stream) {
     const char *name = "risp_serve_median_u8";
-    RISP_CHECK_ARG(raw && out, "%s: null argument", name);
-    RISP_CHECK_ARG(divisor > 0.f, "%s: divisor %g", name, (double)divisor);
-    RISP_CHECK_ARG(demosaic >= RISP_DEMOSAIC_NEAREST && demosaic <= RISP_DEMOSAIC_LAPLACIAN,
-                   "%s: demosaic %d (RISP_DEMOSAIC_NEAREST 0, BILINEAR 1, LAPLACIAN 2)", name, demosaic);
     RISP_CHECK_ARG(size >= 5 && size <= 15 && (size & 1),
                    "%s: median size %d (5, 7, .. 15 are served here; 3 is risp_serve_denoise_u8's, 17 composes)", name, size);
-    RISP_CHECK_ARG(cfa >= 0 && cfa <= 3, "%s: cfa %d (RISP_CFA_RGGB 0, GRBG 1, GBRG 2, BGGR 3)", name, cfa);
-    RISP_CHECK_ARG(black_level >= 0 && black_level <= 65535, "%s: black_level %d outside 0 .. 65535", name, black_level);
-    RISP_CHECK_ARG(n_pre >= 0 && n_post >= 0 && n_pre <= RISP_MAX_CHAIN && n_post <= RISP_MAX_CHAIN && n_pre + n_post <= RISP_MAX_CHAIN,
-                   "%s: bad op list: %d + %d stages (at most %d in all)", name, n_pre, n_post, RISP_MAX_CHAIN);
-    RISP_CHECK_ARG((n_pre == 0 || (pre_ops && pre_params)) && (n_post == 0 || (post_ops && post_params)), "%s: bad op list: null",
-                   name);
     RISP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 4 && H % 2 == 0 && H > size / 2 && W >= 4 && W % 4 == 0 && W > size / 2,
                    "%s: bad shape N=%d H=%d W=%d for size %d (H even, >= 4 and > size / 2, W a multiple of 4 and > size / 2)", name,
                    N, H, W, size);
-    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(raw) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
-                   "%s: raw must be 8-byte and out 4-byte aligned", name);
+    ArgRules r;
+    r.split = true;
     MedianArgs a;
-    a.raw = raw;
+    bool wbq;
+    if (int e = serve_args(name, r, a, wbq, raw, out, divisor, demosaic, n_pre, pre_ops, pre_params, n_post, post_ops, post_params, N, H, W,
+                           black_level, cfa))
+        return e;
     a.out = out;
-    a.divisor = divisor;
-    a.n_pre = n_pre;
-    a.n_ops = n_pre + n_post;
-    a.N = N;
-    a.H = H;
-    a.W = W;
     a.reverse = reverse_channels ? 1 : 0;
-    a.black = black_level;
-    a.flip = cfa;
-    bool wbq = false;
-    for (int k = 0; k < RISP_MAX_CHAIN; ++k) {
-        a.ops[k] = RISP_OP_SKIP;
-        a.params[k] = nullptr;
-    }
-    for (int k = 0; k < n_pre + n_post; ++k) {
-        const int op = k < n_pre ? pre_ops[k] : post_ops[k - n_pre];
-        const float *p = k < n_pre ? pre_params[k] : post_params[k - n_pre];
-        RISP_CHECK_ARG(op == RISP_OP_SKIP || (op >= RISP_OP_WB_MANUAL && op <= RISP_OP_TONE_FILMIC), "%s: op %d not allowed", name, op);
-        RISP_CHECK_ARG(op == RISP_OP_SKIP || p, "%s: stage %d has no parameter block", name, k);
-        a.ops[k] = op;
-        a.params[k] = op == RISP_OP_SKIP ? nullptr : p;
-        wbq |= op == RISP_OP_WB_QUADRATIC;
-    }
-    const dim3 grid((W + TILE_W - 1) / TILE_W, (H + TILE_H - 1) / TILE_H, N);
+    const dim3 grid = patch_grid(N, H, W);
     hipStream_t s = (hipStream_t)stream;
     if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN>(size, wbq, grid, s, a);
     else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR>(size, wbq, grid, s, a);

@@ -545,6 +545,63 @@ def _check_mirror(flip, h, w):
                          % (h, w, 'x' if flip & 1 and w % 2 else 'y'))
 
 
+# ---- what the serve_* wrappers share: each check stated once, in the order the wrappers apply them
+DEMOSAIC = {'nearest': 0, 'bilinear': 1, 'laplacian': 2}      # RISP_DEMOSAIC_*
+
+
+def _u16_frames(raw_u16):
+    """contiguous (N,H,W) uint16 frames on the device -> (n, h, w)"""
+    _need_gpu(raw_u16, 'raw')
+    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
+    return tuple(raw_u16.shape)
+
+
+def _check_counts(ops, params, post_ops=None, post_params=None):
+    """one parameter block per stage, in one list or in the two around a stencil"""
+    if post_ops is None:
+        if len(ops) != len(params):
+            raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
+    elif len(ops) != len(params) or len(post_ops) != len(post_params):
+        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(ops), len(post_ops), len(params), len(post_params)))
+
+
+def _demosaic_code(demosaic):
+    """a key of ``DEMOSAIC`` -> its RISP_DEMOSAIC_* code"""
+    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
+    if kind is None:
+        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
+    return kind
+
+
+def _sensor(black_level, cfa, h=None, w=None):
+    """-> (black level as an int, RISP_CFA_* code); with ``h`` and ``w`` the mirror the phase asks for is checked against them"""
+    code = cfa_code(cfa)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    if h is not None:
+        _check_mirror(code, h, w)
+    return int(black_level), code
+
+
+def _stage_args(ops, params):
+    """-> (count, the ops as a C int array, the blocks as a C pointer array, the float32 device tensors to keep alive across the call)"""
+    keep = [_dev(p) if p is not None else None for p in params]
+    return (len(ops), (C.c_int * max(1, len(ops)))(*ops),
+            L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), keep)
+
+
+def _bilateral_args(bilateral):
+    """None or (window_i32, sigma_color, sigma_space, max_window) -> (the four C arguments, the tensors to keep alive)"""
+    if bilateral is None:
+        return (None, None, None, 0), []
+    win, sc, ss, wmax = bilateral
+    if win.dtype != torch.int32 or not win.is_cuda:
+        raise ValueError('window must be an int32 device tensor')
+    keep = [win.contiguous(), _dev(sc), _dev(ss)]
+    return (_p(keep[0]), _p(keep[1]), _p(keep[2]), int(wmax)), keep
+
+
 def quantise_u8(x, reverse_channels=False, out=None, flip=0):
     """``util.tensor2bgr`` on the device, batched: planar (N,C,H,W) in [0,1] -> packed (N,H,W,C) ``torch.uint8`` =
     clip(x * 255, 0, 255) truncated.  C is 1 or 3; ``reverse_channels`` stores RGB.  ``flip`` (bit 0: x, bit 1: y, the
@@ -602,37 +659,18 @@ def serve_u8(raw_u16, divisor, ops, params, bilateral=None, reverse_channels=Fal
     becomes max(sample - black_level, 0) / divisor, the subtraction in integers (``divisor`` is then white level - black
     level), and a GRBG / GBRG / BGGR mosaic is read mirrored and its image stored un-mirrored - still one launch
     (``risp_serve_u8_cfa``) and byte for byte ``flip(serve_u8(flip(clamp(raw - black_level)), divisor, ...))``."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    n, h, w = raw_u16.shape
-    _check_mirror(code, h, w)
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(ops, params)
+    black, code = _sensor(black_level, cfa, h, w)
     out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
-    keep = [_dev(p) if p is not None else None for p in params]
-    if bilateral is not None:
-        win, sc, ss, wmax = bilateral
-        if win.dtype != torch.int32 or not win.is_cuda:
-            raise ValueError('window must be an int32 device tensor')
-        keep += [win.contiguous(), _dev(sc), _dev(ss)]
-        bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
-    else:
-        bil = (None, None, None, 0)
-    args = (_p(raw_u16), float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-            L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
-            _p(out), int(bool(reverse_channels)), n, h, w)
-    if code or black_level:
-        L.call('risp_serve_u8_cfa', *args, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    bil, keep_bil = _bilateral_args(bilateral)
+    args = (_p(raw_u16), float(divisor), *bil, count, oparr, blocks, _p(out), int(bool(reverse_channels)), n, h, w)
+    if code or black:
+        L.call('risp_serve_u8_cfa', *args, black, code, _stream())
     else:
         L.call('risp_serve_u8', *args, _stream())
     return out
-
-
-DEMOSAIC = {'nearest': 0, 'bilinear': 1, 'laplacian': 2}      # RISP_DEMOSAIC_*
 
 
 def serve_classical_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels=False, out=None, black_level=0, cfa='rggb'):
@@ -645,24 +683,14 @@ def serve_classical_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels
     are those of ``raw_crops`` -> ``origin_demosaic`` / ``chain_forward`` / ``origin_tonemap`` -> ``quantise_u8``.  No
     bilateral.  H even and >= 4, W % 4 == 0; ``black_level`` and ``cfa`` as in ``serve_u8``.  With ``out`` given nothing
     is allocated and the host does not wait."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
-    if kind is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    n, h, w = raw_u16.shape
-    _check_mirror(code, h, w)
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(ops, params)
+    kind = _demosaic_code(demosaic)
+    black, code = _sensor(black_level, cfa, h, w)
     out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
-    keep = [_dev(p) if p is not None else None for p in params]
-    L.call('risp_serve_classical_u8', _p(raw_u16), float(divisor), kind, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), _p(out),
-           int(bool(reverse_channels)), n, h, w, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    L.call('risp_serve_classical_u8', _p(raw_u16), float(divisor), kind, count, oparr, blocks, _p(out),
+           int(bool(reverse_channels)), n, h, w, black, code, _stream())
     return out
 
 
@@ -728,31 +756,17 @@ def serve_nv12(raw_u16, divisor, ops, params, bilateral=None, matrix='bt601_full
     (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte
     ``bgr8_to_nv12(serve_u8(...), matrix)`` without the packed image ever being written.  H even, W % 4 == 0.  With ``out``
     given nothing is allocated and the host does not wait."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(ops, params)
+    black, code = _sensor(black_level, cfa)             # (4:2:0 asks for even axes below: no mirror check)
     coef = nv12_matrix(matrix)
-    n, h, w = raw_u16.shape
     if h % 2 or w % 2:
         raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
     out = _u8_out(out, (n, h + h // 2, w), raw_u16.device, 4)
-    keep = [_dev(p) if p is not None else None for p in params]
-    if bilateral is not None:
-        win, sc, ss, wmax = bilateral
-        if win.dtype != torch.int32 or not win.is_cuda:
-            raise ValueError('window must be an int32 device tensor')
-        keep += [win.contiguous(), _dev(sc), _dev(ss)]
-        bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
-    else:
-        bil = (None, None, None, 0)
-    L.call('risp_serve_nv12', _p(raw_u16), float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
-           _p(out), (C.c_int * 12)(*coef), n, h, w, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    bil, keep_bil = _bilateral_args(bilateral)
+    L.call('risp_serve_nv12', _p(raw_u16), float(divisor), *bil, count, oparr, blocks, _p(out), (C.c_int * 12)(*coef), n, h, w,
+           black, code, _stream())
     return out
 
 
@@ -761,26 +775,17 @@ def serve_classical_nv12(raw_u16, divisor, demosaic, ops, params, matrix='bt601_
     ``matrix`` (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte
     ``bgr8_to_nv12(serve_classical_u8(...), matrix)``.  H even and >= 4, W % 4 == 0.  With ``out`` given nothing is allocated
     and the host does not wait."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
-    if kind is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(ops, params)
+    kind = _demosaic_code(demosaic)
+    black, code = _sensor(black_level, cfa)             # (4:2:0 asks for even axes below: no mirror check)
     coef = nv12_matrix(matrix)
-    n, h, w = raw_u16.shape
     if h % 2 or w % 2:
         raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
     out = _u8_out(out, (n, h + h // 2, w), raw_u16.device, 4)
-    keep = [_dev(p) if p is not None else None for p in params]
-    L.call('risp_serve_classical_nv12', _p(raw_u16), float(divisor), kind, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), _p(out), (C.c_int * 12)(*coef),
-           n, h, w, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    L.call('risp_serve_classical_nv12', _p(raw_u16), float(divisor), kind, count, oparr, blocks, _p(out), (C.c_int * 12)(*coef),
+           n, h, w, black, code, _stream())
     return out
 
 
@@ -864,25 +869,13 @@ def serve_packed(packed_u8, bits, width, divisor, ops, params, bilateral=None, r
     ``serve_nv12(...)`` without the uint16 frames ever being written.  The frames may start at any byte.  H even,
     W % 4 == 0.  With ``out`` given nothing is allocated and the host does not wait."""
     n, h, w, stride = _packed_frames(packed_u8, bits, width)
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    _check_mirror(code, h, w)
+    _check_counts(ops, params)
+    black, code = _sensor(black_level, cfa, h, w)
     coef, out = _packed_out(matrix, reverse_channels, out, n, h, w, packed_u8.device)
-    keep = [_dev(p) if p is not None else None for p in params]
-    if bilateral is not None:
-        win, sc, ss, wmax = bilateral
-        if win.dtype != torch.int32 or not win.is_cuda:
-            raise ValueError('window must be an int32 device tensor')
-        keep += [win.contiguous(), _dev(sc), _dev(ss)]
-        bil = (_p(keep[-3]), _p(keep[-2]), _p(keep[-1]), int(wmax))
-    else:
-        bil = (None, None, None, 0)
-    L.call('risp_serve_packed', _p(packed_u8), bits, stride, float(divisor), *bil, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in keep[:len(ops)]] or [None]),
-           _p(out), int(bool(reverse_channels)), coef, n, h, w, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    bil, keep_bil = _bilateral_args(bilateral)
+    L.call('risp_serve_packed', _p(packed_u8), bits, stride, float(divisor), *bil, count, oparr, blocks, _p(out),
+           int(bool(reverse_channels)), coef, n, h, w, black, code, _stream())
     return out
 
 
@@ -893,20 +886,13 @@ def serve_classical_packed(packed_u8, bits, width, divisor, demosaic, ops, param
     argument ``serve_classical_u8``'s; byte for byte that call on ``raw_unpack(packed_u8, bits, width)``.  H even and >= 4,
     W % 4 == 0.  With ``out`` given nothing is allocated and the host does not wait."""
     n, h, w, stride = _packed_frames(packed_u8, bits, width)
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
-    if kind is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    _check_mirror(code, h, w)
+    _check_counts(ops, params)
+    kind = _demosaic_code(demosaic)
+    black, code = _sensor(black_level, cfa, h, w)
     coef, out = _packed_out(matrix, reverse_channels, out, n, h, w, packed_u8.device)
-    keep = [_dev(p) if p is not None else None for p in params]
-    L.call('risp_serve_classical_packed', _p(packed_u8), bits, stride, float(divisor), kind, len(ops),
-           (C.c_int * max(1, len(ops)))(*ops), L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]),
-           _p(out), int(bool(reverse_channels)), coef, n, h, w, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    L.call('risp_serve_classical_packed', _p(packed_u8), bits, stride, float(divisor), kind, count, oparr, blocks, _p(out),
+           int(bool(reverse_channels)), coef, n, h, w, black, code, _stream())
     return out
 
 
@@ -1021,25 +1007,15 @@ def serve_classical_shaded(raw_u16, shading, divisor, demosaic, ops, params, rev
     white_level - black_level.  Byte for byte ``serve_classical_u8(raw_shade(raw_u16, shading, black_level), divisor, ...,
     black_level=0, cfa=cfa)`` without the shaded frames ever being written.  H even and >= 4, W % 4 == 0.  With ``out`` given
     nothing is allocated and the host does not wait."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
-    if kind is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    n, h, w = raw_u16.shape
-    _check_mirror(code, h, w)
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(ops, params)
+    kind = _demosaic_code(demosaic)
+    black, code = _sensor(black_level, cfa, h, w)
     gains, k, gh, gw = shading_check(shading, h, w, raw_u16.device)
     coef, out = _packed_out(matrix, reverse_channels, out, n, h, w, raw_u16.device)
-    keep = [_dev(p) if p is not None else None for p in params]
-    L.call('risp_serve_classical_shaded', _p(raw_u16), float(divisor), kind, len(ops), (C.c_int * max(1, len(ops)))(*ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None]), _p(out),
-           int(bool(reverse_channels)), coef, _p(gains), k, gh, gw, n, h, w, int(black_level), code, _stream())
+    count, oparr, blocks, keep = _stage_args(ops, params)
+    L.call('risp_serve_classical_shaded', _p(raw_u16), float(divisor), kind, count, oparr, blocks, _p(out),
+           int(bool(reverse_channels)), coef, _p(gains), k, gh, gw, n, h, w, black, code, _stream())
     return out
 
 
@@ -1062,40 +1038,12 @@ def serve_denoise_u8(raw_u16, divisor, kind, pre_ops, pre_params, denoise, denoi
     ``chain_forward`` / ``origin_tonemap`` -> ``origin_denoise`` -> stages -> ``quantise_u8`` with scales (255, 255).  H even
     and >= 4, W % 4 == 0; ``black_level`` and ``cfa`` as in ``serve_u8``.  With ``out`` given nothing is allocated and the host
     does not wait."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(pre_ops) != len(pre_params) or len(post_ops) != len(post_params):
-        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(pre_ops), len(post_ops), len(pre_params), len(post_params)))
-    code_d = DEMOSAIC.get(kind) if isinstance(kind, str) else None
-    if code_d is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (kind, ', '.join(DEMOSAIC)))
-    code_n = DENOISE.get(denoise) if isinstance(denoise, str) else None
-    if code_n is None:
-        raise ValueError('unknown denoiser %r: one of %s' % (denoise, ', '.join(DENOISE)))
-    if len(denoise_args) != (3, 1, 3)[code_n]:
-        raise ValueError('%s takes %d arguments, got %d' % (denoise, (3, 1, 3)[code_n], len(denoise_args)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    args, code, keep = _denoise_frame_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+                                           black_level, cfa)
     n, h, w = raw_u16.shape
-    _check_mirror(code, h, w)
-    window, search, vecs = int(denoise_args[0]), 0, []
-    if code_n == 0:
-        vecs = list(denoise_args[1:])
-    elif code_n == 2:
-        search, vecs = int(denoise_args[1]), [denoise_args[2]]
-    for v in vecs:
-        if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != (n,) or not v.is_contiguous():
-            raise ValueError('%s takes contiguous float32 (%d,) device tensors for its per-image values' % (denoise, n))
     out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
-    pre = [_dev(p) if p is not None else None for p in pre_params]
-    post = [_dev(p) if p is not None else None for p in post_params]
-    L.call('risp_serve_denoise_u8', _p(raw_u16), float(divisor), code_d, len(pre_ops), (C.c_int * max(1, len(pre_ops)))(*pre_ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in pre] or [None]), code_n, window, search,
-           _p(vecs[0]) if vecs else None, _p(vecs[1]) if len(vecs) > 1 else None, len(post_ops),
-           (C.c_int * max(1, len(post_ops)))(*post_ops), L.ptr_array([p.data_ptr() if p is not None else None for p in post] or [None]),
-           _p(out), int(bool(reverse_channels)), n, h, w, int(black_level), code, _stream())
+    L.call('risp_serve_denoise_u8', _p(raw_u16), float(divisor), *args, _p(out), int(bool(reverse_channels)), n, h, w,
+           int(black_level), code, _stream())
     return out
 
 
@@ -1113,28 +1061,17 @@ def serve_median_u8(raw_u16, divisor, kind, pre_ops, pre_params, size, post_ops,
     ``quantise_u8``.  Size 3 is ``serve_denoise_u8``'s and 17 (a saturated parameter) is not served: both are refused.  H even,
     >= 4 and > size // 2, W % 4 == 0 and > size // 2; ``black_level`` and ``cfa`` as in ``serve_u8``.  With ``out`` given nothing
     is allocated and the host does not wait."""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(pre_ops) != len(pre_params) or len(post_ops) != len(post_params):
-        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(pre_ops), len(post_ops), len(pre_params), len(post_params)))
-    code_d = DEMOSAIC.get(kind) if isinstance(kind, str) else None
-    if code_d is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (kind, ', '.join(DEMOSAIC)))
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(pre_ops, pre_params, post_ops, post_params)
+    code_d = _demosaic_code(kind)
     if size != int(size) or int(size) not in MEDIAN_SIZES:
         raise ValueError('median size %r: one of %s (3 is serve_denoise_u8\'s)' % (size, ', '.join(str(k) for k in MEDIAN_SIZES)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    n, h, w = raw_u16.shape
-    _check_mirror(code, h, w)
+    black, code = _sensor(black_level, cfa, h, w)
     out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
-    pre = [_dev(p) if p is not None else None for p in pre_params]
-    post = [_dev(p) if p is not None else None for p in post_params]
-    L.call('risp_serve_median_u8', _p(raw_u16), float(divisor), code_d, len(pre_ops), (C.c_int * max(1, len(pre_ops)))(*pre_ops),
-           L.ptr_array([p.data_ptr() if p is not None else None for p in pre] or [None]), int(size), len(post_ops),
-           (C.c_int * max(1, len(post_ops)))(*post_ops), L.ptr_array([p.data_ptr() if p is not None else None for p in post] or [None]),
-           _p(out), int(bool(reverse_channels)), n, h, w, int(black_level), code, _stream())
+    pre = _stage_args(pre_ops, pre_params)
+    post = _stage_args(post_ops, post_params)
+    L.call('risp_serve_median_u8', _p(raw_u16), float(divisor), code_d, *pre[:3], int(size), *post[:3], _p(out),
+           int(bool(reverse_channels)), n, h, w, black, code, _stream())
     return out
 
 
@@ -1167,20 +1104,12 @@ def serve_scene_groups(h, w):
 
 
 def _scene_frame_args(raw_u16, demosaic, ops, params, black_level, cfa):
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(ops) != len(params):
-        raise ValueError('%d ops but %d parameter blocks' % (len(ops), len(params)))
-    kind = DEMOSAIC.get(demosaic) if isinstance(demosaic, str) else None
-    if kind is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (demosaic, ', '.join(DEMOSAIC)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    _check_mirror(code, raw_u16.shape[1], raw_u16.shape[2])
-    keep = [_dev(p) if p is not None else None for p in params]
-    return kind, code, keep, (C.c_int * max(1, len(ops)))(*ops), L.ptr_array([p.data_ptr() if p is not None else None for p in keep] or [None])
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(ops, params)
+    kind = _demosaic_code(demosaic)
+    _, code = _sensor(black_level, cfa, h, w)
+    _, oparr, blocks, keep = _stage_args(ops, params)
+    return kind, code, keep, oparr, blocks
 
 
 def serve_scene_stats(raw_u16, divisor, demosaic, ops, params, stat, partials=None, black_level=0, cfa='rggb', tag=0):
@@ -1242,27 +1171,18 @@ def serve_scene_u8(raw_u16, divisor, demosaic, ops, params, reverse_channels=Fal
     return out
 
 
-def _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params, black_level, cfa):
+def _denoise_frame_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params, black_level, cfa):
     """what ``serve_denoise_u8`` checks and forms, for the two launches that take a denoiser and scene constants together:
     (leading C arguments through post_params, CFA code, the tensors to keep alive across the call)"""
-    _need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3 or not raw_u16.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    if len(pre_ops) != len(pre_params) or len(post_ops) != len(post_params):
-        raise ValueError('%d + %d ops but %d + %d parameter blocks' % (len(pre_ops), len(post_ops), len(pre_params), len(post_params)))
-    code_d = DEMOSAIC.get(kind) if isinstance(kind, str) else None
-    if code_d is None:
-        raise ValueError('unknown demosaic %r: one of %s' % (kind, ', '.join(DEMOSAIC)))
+    n, h, w = _u16_frames(raw_u16)
+    _check_counts(pre_ops, pre_params, post_ops, post_params)
+    code_d = _demosaic_code(kind)
     code_n = DENOISE.get(denoise) if isinstance(denoise, str) else None
     if code_n is None:
         raise ValueError('unknown denoiser %r: one of %s' % (denoise, ', '.join(DENOISE)))
     if len(denoise_args) != (3, 1, 3)[code_n]:
         raise ValueError('%s takes %d arguments, got %d' % (denoise, (3, 1, 3)[code_n], len(denoise_args)))
-    code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    n, h, w = raw_u16.shape
-    _check_mirror(code, h, w)
+    _, code = _sensor(black_level, cfa, h, w)
     window, search, vecs = int(denoise_args[0]), 0, []
     if code_n == 0:
         vecs = list(denoise_args[1:])
@@ -1271,13 +1191,10 @@ def _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_arg
     for v in vecs:
         if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != (n,) or not v.is_contiguous():
             raise ValueError('%s takes contiguous float32 (%d,) device tensors for its per-image values' % (denoise, n))
-    pre = [_dev(p) if p is not None else None for p in pre_params]
-    post = [_dev(p) if p is not None else None for p in post_params]
-    args = (code_d, len(pre_ops), (C.c_int * max(1, len(pre_ops)))(*pre_ops),
-            L.ptr_array([p.data_ptr() if p is not None else None for p in pre] or [None]), code_n, window, search,
-            _p(vecs[0]) if vecs else None, _p(vecs[1]) if len(vecs) > 1 else None, len(post_ops),
-            (C.c_int * max(1, len(post_ops)))(*post_ops), L.ptr_array([p.data_ptr() if p is not None else None for p in post] or [None]))
-    return args, code, (pre, post, vecs)
+    pre = _stage_args(pre_ops, pre_params)
+    post = _stage_args(post_ops, post_params)
+    args = (code_d, *pre[:3], code_n, window, search, _p(vecs[0]) if vecs else None, _p(vecs[1]) if len(vecs) > 1 else None, *post[:3])
+    return args, code, (pre[3], post[3], vecs)
 
 
 def serve_denoise_stats(raw_u16, divisor, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params, stat,
@@ -1291,7 +1208,7 @@ def serve_denoise_stats(raw_u16, divisor, kind, pre_ops, pre_params, denoise, de
     OP_GAIN3_Q8 with the constants of an earlier ``serve_scene_finish``; OP_TONE_REINHARD is refused.  MAX3 rows are the
     maxima of the composed route's plane exactly; a MEAN3 row lies within (64 * 32 - 1) * 2^-24 * sum|x| of its tile's exact
     sum.  ``partials`` None: a buffer cached per device, stream, ``tag`` and shape."""
-    args, code, keep = _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+    args, code, keep = _denoise_frame_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
                                            black_level, cfa)
     if stat not in (SCENE_MEAN3, SCENE_MAX3):
         raise ValueError('stat %r: SCENE_MEAN3 or SCENE_MAX3 (a log-average is not served behind a denoiser)' % (stat,))
@@ -1315,7 +1232,7 @@ def serve_denoise_scene_u8(raw_u16, divisor, kind, pre_ops, pre_params, denoise,
     OP_TONE_REINHARD is refused.  Same frames, rules and - for every stage both accept - bytes as ``serve_denoise_u8``;
     given the constants, the bytes are those of the composed route evaluated with the same constants (``chain_forward`` with
     OP_GAIN3, ``origin_whiteworld`` at their places).  With ``out`` given nothing is allocated and the host does not wait."""
-    args, code, keep = _denoise_scene_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
+    args, code, keep = _denoise_frame_args(raw_u16, kind, pre_ops, pre_params, denoise, denoise_args, post_ops, post_params,
                                            black_level, cfa)
     n, h, w = raw_u16.shape
     out = _u8_out(out, (n, h, w, 3), raw_u16.device, 4)
