@@ -944,6 +944,38 @@ int risp_serve_classical_shaded(const uint16_t *raw, float divisor, int demosaic
                                 const uint16_t *gains, int cell_log2, int GH, int GW, int N, int H, int W, int black_level,
                                 int cfa, void *stream);
 
+/* Defective-pixel correction (DPC) into the serving path (risp_defect.hip, risp_defect.h): hot, dead and factory-listed pixels
+ * replaced from their same-colour neighbours, in front of shading and demosaic - DNG's FixBadPixelsConstant / FixBadPixelsList, the
+ * DPC block of a hardware ISP.  An integer function of the frame, fixed to the bit (tests/defect_reference.py restates it).
+ * S(y,x) is the decoded raw sample of the frame as stored - uint16, or RAW10 / RAW12 as above -, before the black level and whatever
+ * cfa says.  An index outside the frame reflects without repeating the edge, i -> -i and i -> 2 (n-1) - i, which keeps the Bayer
+ * colour: parity is preserved for every n.  H >= 3, W >= 4, W % 4 == 0.  The neighbour pairs of pixel p = S(y,x), in this order:
+ *     H  S(y,x-2),   S(y,x+2)          V  S(y-2,x),   S(y+2,x)
+ *     D  S(y-2,x-2), S(y+2,x+2)        A  S(y-2,x+2), S(y+2,x-2)
+ *     mx, mn = the maximum and the minimum of the eight neighbours;   T(v) = threshold + ((v * slope) >> 8)
+ *     hot     p > mx + T(mx)
+ *     dead    p + T(mn) < mn
+ *     listed  bit (x & 31) of word (x >> 5) of row y of the defect map is set
+ * A pixel that is hot, dead or listed becomes (a + b + 1) >> 1 of the pair (a, b) with the smallest |a - b|; on a tie the first
+ * pair in the order H, V, D, A wins.  Every other pixel passes through.  Neighbours are always the input's, never corrected
+ * output: the result is a pure function of the frame.  All arithmetic is unsigned 32-bit.  Nothing wraps there, but mx + T(mx),
+ * p + T(mn) and a + b + 1 pass 2^16, so a form that keeps them in packed 16-bit lanes is wrong.
+ * threshold: 0 .. 65535 in raw codes, or -1 for no dynamic test (then slope is not used); slope: 0 .. 255, Q8 - photon noise grows
+ * with the signal.  defects: (H, (W + 31) / 32) uint32 words, contiguous, 4-byte aligned, one map for all N frames, bits at x >= W
+ * ignored; NULL for no map.  One of the two must be on.  Not covered: green's nearer diagonal neighbours, clusters of adjacent
+ * defects (a defective neighbour enters as it is), thresholds per Bayer plane.
+ *
+ * risp_raw_defect: frames -> out (N,H,W) uint16 contiguous, one launch, bits / 8 bytes read and 2 written per pixel plus the maps.
+ * raw, bits and stride as in risp_raw_shade: uint16 rows (2-byte aligned, wider loads when raw and stride are 8-byte aligned) or
+ * packed rows from any byte, decoded on the way.  gains NULL: out holds the corrected raw codes, black level kept, and cell_log2,
+ * GH, GW and black_level must be 0.  gains not NULL: each corrected sample is shaded exactly as risp_raw_shade shades it,
+ *     out == risp_raw_shade(risp_raw_defect(raw, ..., gains NULL), gains, ..., black_level)   word for word,
+ * with the rules of the map.  out must not overlap raw: a thread reads rows other threads write.  Rules (anything else is
+ * refused before a launch, the message names the value): raw and out not NULL, N >= 1, H >= 3, W >= 4 and W % 4 == 0, the stride
+ * rules of the format, threshold -1 .. 65535, slope 0 .. 255, threshold >= 0 or defects, out 8-byte aligned. */
+int risp_raw_defect(const void *raw, int bits, int stride, uint16_t *out, int threshold, int slope, const uint32_t *defects,
+                    const uint16_t *gains, int cell_log2, int GH, int GW, int black_level, int N, int H, int W, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

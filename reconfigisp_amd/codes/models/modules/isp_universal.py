@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import fused_forward, serve, serve_frame, serve_load, serve_shade, wants_grad
+from .pipeline_fusion import defect_shade, fused_forward, serve, serve_frame, serve_load, serve_shade, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -46,6 +46,7 @@ class _FixedPipeline(nn.Module):
         self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' (a median of size 5 .. 15 under fast_median too) | 'denoise_scene' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
         self.last_serve_store = None            # with out_format='nv12': 'fused' (the serving launch stored NV12) | 'pass' (the conversion launch did); None for 'bgr8'
         self.last_serve_shade = None            # with lens_shading: 'fused' (the serving launch shaded in its load) | 'pass' (risp_raw_shade did, decoding packed frames too); None without the keyword
+        self.last_serve_defect = None           # with defect_correction: 'fused' (one risp_raw_defect launch corrected and shaded) | 'pass' (risp_raw_defect corrected; risp_raw_shade follows where lens_shading is given); None without the keyword
         self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
 
     def _apply(self, fn, *args, **kwargs):
@@ -98,7 +99,7 @@ class _FixedPipeline(nn.Module):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', raw_format='u16', raw_width=None,
-              lens_shading=None, fast_median=False, fast_denoise_scene=False):
+              lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -156,15 +157,25 @@ class _FixedPipeline(nn.Module):
         ``white_level - black_level`` and black level 0, on the same route.  ``last_serve_shade`` records who shaded, as
         ``pipeline_fusion.serve_shade`` tells: 'fused' (the one launch of the 'classical' route, 8-byte aligned uint16 frames)
         or 'pass' (``risp_raw_shade`` in front of the route, which decodes packed frames too: ``last_serve_load`` is then
-        'pass'); None without the keyword.  ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width``, ``lens_shading``,
-        ``fast_median`` and ``fast_denoise_scene`` are keyword-only (``pipeline_fusion.serve``)."""
+        'pass'); None without the keyword.
+
+        ``defect_correction=(threshold, slope, defects)`` replaces hot, dead and factory-listed pixels from their same-colour
+        neighbours in front of everything else (``functional.defect_check``, ``functional.defect_map``; include/risp.h has the
+        integer definition) - the bytes of the same call on ``functional.raw_defect(frames, defect_correction, bits, raw_width)``
+        as uint16 input, with ``lens_shading`` on ``functional.raw_shade`` of those, on the route that call takes.  One
+        ``risp_raw_defect`` launch in front of the route, which decodes packed frames too (``last_serve_load`` is then 'pass',
+        ``last_serve_shade`` 'pass' with a shading).  ``last_serve_defect`` records the pre-pass as
+        ``pipeline_fusion.defect_shade`` tells: 'fused' (that one launch shaded as well) or 'pass' (it corrected alone;
+        ``risp_raw_shade`` follows where a shading is given); None without the keyword.  ``out_format``, ``yuv_matrix``,
+        ``raw_format``, ``raw_width``, ``lens_shading``, ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are
+        keyword-only (``pipeline_fusion.serve``)."""
         with torch.no_grad():
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                                     out_format=out_format, yuv_matrix=yuv_matrix, raw_format=raw_format,
                                                     raw_width=raw_width, lens_shading=lens_shading,
-                                                    fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
+                                                    defect_correction=defect_correction, fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
             self.last_serve_load = serve_load(self.last_serve_route, raw_format)
@@ -173,11 +184,18 @@ class _FixedPipeline(nn.Module):
                 self.last_serve_shade = serve_shade(self.last_serve_route, raw_format) if raw_u16.data_ptr() % 8 == 0 else 'pass'
                 if self.last_serve_load is not None:
                     self.last_serve_load = 'pass'
+            self.last_serve_defect = None
+            if defect_correction is not None:
+                self.last_serve_defect = defect_shade(raw_format) if lens_shading is not None else 'pass'
+                if self.last_serve_load is not None:
+                    self.last_serve_load = 'pass'
+                if lens_shading is not None:
+                    self.last_serve_shade = 'pass'
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16', raw_width=None,
-                    lens_shading=None):
+                    defect_correction=None, lens_shading=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
         ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
@@ -188,14 +206,18 @@ class _FixedPipeline(nn.Module):
         ``yuv_matrix`` as in ``serve``: (3H/2,W) or (N,3H/2,W), converted per frame behind the blend (``last_serve_store``
         'pass').  ``raw_format`` and ``raw_width`` as in ``serve``, (H,stride) included: unpacked once in front of the tiles
         (``last_serve_load`` 'pass').  ``lens_shading`` as in ``serve``: the whole frame is shaded once in front of the tiles
-        (``last_serve_shade`` 'pass'), packed frames in that same launch."""
+        (``last_serve_shade`` 'pass'), packed frames in that same launch.  ``defect_correction`` as in ``serve``: the whole
+        frame is corrected once in front of the tiles and of the shading (``last_serve_defect`` as there), packed frames in
+        that same launch."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
                               reverse_channels, out, black_level, cfa, out_format, yuv_matrix, raw_format=raw_format,
-                              raw_width=raw_width, lens_shading=lens_shading)
+                              raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
             self.last_serve_route = 'tiled'
             self.last_serve_load = serve_load('tiled', raw_format)
             self.last_serve_shade = None if lens_shading is None else serve_shade('tiled', raw_format)
+            self.last_serve_defect = None if defect_correction is None else (
+                defect_shade(raw_format) if lens_shading is not None else 'pass')
             self.last_serve_store = None if out_format == 'bgr8' else 'pass'
         return out
 

@@ -573,9 +573,45 @@ def _shaded_u16(shape, device):
     return F._scene_buffer(device, 'shaded_u16', shape, torch.uint16)
 
 
+# raw formats whose defective-pixel correction and lens shading run as ONE risp_raw_defect launch (with gains) instead of
+# risp_raw_defect followed by risp_raw_shade.  A format is listed only if the one launch beats the two by more than the larger
+# spread of the two legs in every measured row of profiles/serve_defect.txt (two sizes per format) - the rule of
+# _FUSED_LOAD, _FUSED_SHADE and _MEDIAN_SIZES.  The verdict line of that file is this table.  Measured: the one launch is 7.8 to
+# 9.9 us faster in all six rows (0.83-0.92 x) against spreads of 0.2 to 2.0 us - the second launch costs a launch and a second trip
+# of the frames through the cache, the gains cost the first one three multiplies per sample beside some sixty instructions.
+_DEFECT_SHADE_FUSED = frozenset({'u16', 'raw10', 'raw12'})
+
+
+def defect_shade(raw_format):
+    """How a call with both ``defect_correction`` and ``lens_shading`` runs its pre-pass for frames of ``raw_format``: 'fused' -
+    one ``risp_raw_defect`` launch with the gains - or 'pass' - ``risp_raw_defect``, then ``risp_raw_shade`` on its frames.  A
+    pure function of its argument: what ``serve`` / ``serve_frame`` do and what ``last_serve_defect`` reports for such a call."""
+    F.raw_format_bits(raw_format)
+    return 'fused' if raw_format in _DEFECT_SHADE_FUSED else 'pass'
+
+
+def _defect_u16(shape, device):
+    """the uint16 frames the defective-pixel correction writes, kept per (shape, device, stream); neither the unpack buffer nor
+    the shade buffer: a caller may hold their frames, and the shade launch behind the correction reads these"""
+    return F._scene_buffer(device, 'defect_u16', shape, torch.uint16)
+
+
+def _corrected(frames, defect, bits, w, raw_format, shade):
+    """the pre-pass of a call with ``defect_correction``: contiguous uint16 or packed ``frames`` -> corrected uint16 frames in the
+    cached buffers, shaded too with ``shade`` = ((gains, cell), black level) - in the same launch where ``defect_shade`` says so"""
+    shape, device = tuple(frames.shape[:-1]) + (w,), frames.device
+    if shade is None:
+        return F.raw_defect(frames, defect, bits, w, out=_defect_u16(shape, device))
+    if defect_shade(raw_format) == 'fused':
+        return F.raw_defect(frames, defect, bits, w, shade[0], shade[1], _defect_u16(shape, device))
+    return F.raw_shade(F.raw_defect(frames, defect, bits, w, out=_defect_u16(shape, device)), shade[0], shade[1], 16, w,
+                       _shaded_u16(shape, device))
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          raw_format='u16', raw_width=None, lens_shading=None, fast_median=False, fast_denoise_scene=False):
+          raw_format='u16', raw_width=None, lens_shading=None, defect_correction=None, fast_median=False,
+          fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -669,7 +705,18 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     on the way: no ``risp_raw_unpack`` is issued.  The gains are never read on the host.  With ``out`` given a warm call
     allocates nothing and never waits for the device.  None is the call without the keyword.
 
-    ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width``, ``lens_shading`` and ``fast_median`` are keyword-only, and so is
+    ``defect_correction=(threshold, slope, defects)`` replaces hot, dead and factory-listed pixels from their same-colour
+    neighbours in front of everything else, the shading included (``F.defect_check``; ``F.defect_map`` builds the bitmap;
+    include/risp.h has the integer definition, on the frame as stored, before the black level and whatever ``cfa``).  The
+    bytes returned are those of the same call on ``F.raw_defect(frames, defect_correction, bits, raw_width)`` as uint16 input,
+    and with ``lens_shading`` on ``F.raw_shade(F.raw_defect(...), lens_shading, black_level)``, on the route that call takes -
+    the one uint16 frames from the allocator take.  ``risp_raw_defect`` is one launch in front of the route and decodes packed
+    frames on the way: no ``risp_raw_unpack`` is issued and no fused packed or shading load is taken.  With ``lens_shading``
+    the same launch shades where ``defect_shade`` says 'fused'; otherwise ``risp_raw_shade`` follows.  The corrected frames
+    live in a buffer of their own per shape, device and stream.  H >= 3, W % 4 == 0.  With ``out`` given a warm call allocates
+    nothing and never waits for the device.  None is the call without the keyword.
+
+    ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -698,19 +745,24 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         F.shading_check(lens_shading, h, w, raw_u16.device)
         # behind the shading the samples have black level 0 and the white level white_level - black_level
         shade, white_level, black_level = (lens_shading, int(black_level)), divisor, 0
+    defect = defect_correction
+    if defect is not None:
+        F.defect_check(defect, h, w, raw_u16.device)        # refused before anything is launched
     coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
     if coef is not None:
         if out is not None:
             F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade)
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade, defect)
         return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
     return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade)
+                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade,
+                      defect=defect)
 
 
 def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False, shade=None):
+               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False, shade=None,
+               defect=None):
     """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
     NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
     With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
@@ -719,9 +771,20 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
     With ``shade`` = ((gains, cell), the sensor's black level), ``black_level`` being 0 and ``white_level`` the divisor: the
     route is again the one uint16 frames from the allocator take, 'classical' shades in its load where ``serve_shade`` says so
     (uint16 input, 8-byte aligned), and every other route runs on ``frames()``, the cached uint16 stack the shade launch fills
-    from the uint16 or the packed frames"""
+    from the uint16 or the packed frames.
+    With ``defect`` = (threshold, slope, defects): the route is once more the one uint16 frames from the allocator take and
+    every route runs on ``frames()``, the cached uint16 stack ``risp_raw_defect`` fills from the uint16 or the packed frames -
+    shaded too with ``shade``, by that launch or by ``risp_raw_shade`` behind it (``defect_shade``); no fused load is taken"""
     device = raw_u16.device
-    if shade is not None:
+    if defect is not None:
+        (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
+        fmt, bits = ('u16', 16) if packed is None else (packed[3], packed[1])
+        prepass = shade
+
+        def frames():
+            return _corrected(raw_u16, defect, bits, w, fmt, prepass)
+        packed = shade = None                               # the pre-pass decodes and shades: nothing behind it sees either
+    elif shade is not None:
         (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
         fmt, bits = ('u16', 16) if packed is None else (packed[3], packed[1])
 
@@ -838,7 +901,7 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
                 out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16',
-                raw_width=None, lens_shading=None):
+                raw_width=None, defect_correction=None, lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -859,26 +922,40 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     ``lens_shading=(gains, cell)`` (keyword-only, as in ``serve``) shades the whole frame once in front of ``raw_crops``:
     ``risp_raw_shade`` writes uint16 frames kept per shape, device and stream - from packed frames too, in place of the unpack
     launch - and everything behind it runs with ``white_level - black_level`` and black level 0.
+    ``defect_correction=(threshold, slope, defects)`` (keyword-only, as in ``serve``) corrects the whole frame once in front of
+    everything else: ``risp_raw_defect`` writes uint16 frames kept per shape, device and stream - from packed frames too, in
+    place of the unpack launch; with ``lens_shading`` it shades in the same launch where ``defect_shade`` says 'fused', and
+    ``risp_raw_shade`` follows otherwise.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
-    if lens_shading is not None:
+    if lens_shading is not None or defect_correction is not None:
         if raw_format != 'u16':
             bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
         else:
             if (not isinstance(raw_u16, torch.Tensor) or raw_u16.dtype != torch.uint16 or raw_u16.dim() not in (2, 3)
                     or raw_u16.shape[-1] % 4):
-                raise ValueError('lens_shading takes (H,W) or (N,H,W) uint16 frames with W a multiple of 4, got %s %s'
-                                 % (getattr(raw_u16, 'dtype', type(raw_u16)), tuple(getattr(raw_u16, 'shape', ()))))
+                raise ValueError('%s takes (H,W) or (N,H,W) uint16 frames with W a multiple of 4, got %s %s'
+                                 % ('lens_shading' if lens_shading is not None else 'defect_correction',
+                                    getattr(raw_u16, 'dtype', type(raw_u16)), tuple(getattr(raw_u16, 'shape', ()))))
             bits, w = 16, raw_u16.shape[-1]
+        if defect_correction is not None:
+            F.defect_check(defect_correction, raw_u16.shape[-2], w)
         F._need_gpu(raw_u16, 'raw')
         if black_level != int(black_level) or not 0 <= black_level < white_level:
             raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-        F.shading_check(lens_shading, raw_u16.shape[-2], w, raw_u16.device)
-        raw_u16 = F.raw_shade(raw_u16.contiguous(), lens_shading, int(black_level), bits, w,
-                              _shaded_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
-        white_level, black_level, raw_format = white_level - black_level, 0, 'u16'
+        if lens_shading is not None:
+            F.shading_check(lens_shading, raw_u16.shape[-2], w, raw_u16.device)
+        if defect_correction is not None:
+            raw_u16 = _corrected(raw_u16.contiguous(), defect_correction, bits, w, raw_format,
+                                 None if lens_shading is None else (lens_shading, int(black_level)))
+        else:
+            raw_u16 = F.raw_shade(raw_u16.contiguous(), lens_shading, int(black_level), bits, w,
+                                  _shaded_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
+        if lens_shading is not None:
+            white_level, black_level = white_level - black_level, 0
+        raw_format = 'u16'
     if raw_format != 'u16':
         bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
         F._need_gpu(raw_u16, 'raw')

@@ -999,6 +999,123 @@ def raw_shade(frames, shading, black_level=0, bits=16, width=None, out=None):
     return out
 
 
+def _small_int(v, lo, hi):
+    """v as an int when it is an integer (no bool) in lo .. hi, else None"""
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
+        return None
+    return int(v)
+
+
+def defect_check(dc, h, w, device=None):
+    """A defective-pixel correction ``(threshold, slope, defects)`` for H x W frames, checked on the host before anything is
+    launched -> (threshold, slope, defects) normalised: ints, threshold -1 for None (the C ABI's 'no dynamic test').
+    ``threshold``: an integer 0 .. 65535 in raw codes or None; ``slope``: an integer 0 .. 255, Q8, the part of the threshold
+    that grows with the signal; ``defects``: None or the factory list as a contiguous (H, (W+31)//32) ``torch.int32`` device
+    tensor, bit x & 31 of word x >> 5 of row y for pixel (y,x) (``defect_map`` builds one; bits at x >= W are ignored).  One
+    of threshold and map must be given.  H >= 3, W >= 4, W % 4 == 0.  Nothing on the device is read: the host never waits
+    (include/risp.h has the definition to the bit)."""
+    try:
+        threshold, slope, defects = dc
+    except (TypeError, ValueError):
+        raise ValueError('a defect correction is (threshold, slope, defects): raw codes or None, a Q8 slope, '
+                         'an (H,(W+31)//32) int32 device bitmap or None') from None
+    thr = -1 if threshold is None else _small_int(threshold, 0, 65535)
+    if thr is None:
+        raise ValueError('defect threshold %r: an integer in 0 .. 65535 (raw codes), or None for no dynamic test' % (threshold,))
+    slp = _small_int(slope, 0, 255)
+    if slp is None:
+        raise ValueError('defect slope %r: an integer in 0 .. 255 (Q8)' % (slope,))
+    if int(h) < 3 or int(w) < 4 or int(w) % 4:
+        raise ValueError('defect correction on %d x %d frames: H >= 3, W >= 4 and a multiple of 4' % (h, w))
+    if defects is None:
+        if thr < 0:
+            raise ValueError('a defect correction with neither a threshold nor a defect map corrects nothing')
+        return thr, slp, None
+    if not isinstance(defects, torch.Tensor) or defects.dtype != torch.int32:
+        raise ValueError('the defect map must be an int32 tensor (a bit per pixel), got %s' % (getattr(defects, 'dtype', type(defects)),))
+    words = (int(w) + 31) // 32
+    if tuple(defects.shape) != (int(h), words) or not defects.is_contiguous():
+        raise ValueError('the defect map of a %d x %d frame must be contiguous (%d,%d): a word per 32 pixels of a row; got %s'
+                         % (h, w, h, words, tuple(defects.shape)))
+    _need_gpu(defects, 'defect map')
+    if device is not None and defects.device != device:
+        raise ValueError('the defect map lives on %s, the frames on %s' % (defects.device, device))
+    return thr, slp, defects
+
+
+def defect_map(coords, H, W):
+    """Host helper: defective pixels as an iterable or (K,2) array of integer (y, x) -> the (H, (W+31)//32) ``torch.int32``
+    bitmap of ``defect_check`` (on the CPU; move it to the device once): bit x & 31 of word x >> 5 of row y, bit 31 being the
+    sign bit of its word.  A coordinate outside the frame or not an integer is refused; no coordinates give an all-zero map;
+    one given twice is set once."""
+    import numpy as np
+    if H != int(H) or W != int(W) or H < 1 or W < 1:
+        raise ValueError('frame size %r x %r' % (H, W))
+    H, W = int(H), int(W)
+    if isinstance(coords, torch.Tensor):
+        coords = coords.detach().cpu().numpy()
+    c = coords if isinstance(coords, np.ndarray) else np.asarray(list(coords))
+    words = np.zeros((H, (W + 31) // 32), dtype=np.uint32)
+    if c.size:
+        if c.ndim != 2 or c.shape[1] != 2:
+            raise ValueError('defect coordinates are (K,2) pairs of (y, x), got %s' % (tuple(c.shape),))
+        if c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError('defect coordinates must be integers, got %s' % (c.dtype,))
+        y, x = c[:, 0].astype(np.int64), c[:, 1].astype(np.int64)
+        if y.min() < 0 or y.max() >= H or x.min() < 0 or x.max() >= W:
+            raise ValueError('defect coordinates outside the %d x %d frame' % (H, W))
+        np.bitwise_or.at(words, (y, x >> 5), (np.uint32(1) << (x & 31).astype(np.uint32)))
+    return torch.from_numpy(words.view(np.int32))
+
+
+def raw_defect(frames, defect, bits=16, width=None, shading=None, black_level=0, out=None):
+    """Defective-pixel correction of sensor frames in ONE launch (``risp_raw_defect``): (N,H,W) or (H,W) ``torch.uint16``
+    frames on the device (``bits=16``), or (N,H,stride) / (H,stride) ``torch.uint8`` MIPI-packed RAW10 / RAW12 (``bits``
+    10 / 12, ``width`` as in ``raw_unpack``) -> (N,H,W) or (H,W) ``torch.uint16``.  ``defect`` = (threshold, slope, defects)
+    (``defect_check``): a pixel above the largest of its eight same-colour neighbours at distance 2 by more than
+    threshold + (slope * that neighbour >> 8), below the smallest by more than the same of the smallest, or listed in the
+    bitmap becomes the rounded mean of the pair - across, down, the two diagonals - that differs least; borders reflect;
+    neighbours are the input's (include/risp.h has the definition to the bit).  Without ``shading`` the corrected raw codes
+    come out, black level kept, and ``black_level`` must be 0.  With ``shading`` = (gains, cell) the same launch shades each
+    corrected sample: word for word ``raw_shade(raw_defect(frames, defect, bits, width), shading, black_level)``.  H >= 3,
+    W % 4 == 0.  ``out`` (contiguous, 8-byte aligned) must not share memory with the frames - the launch reads rows other
+    threads write; with it nothing is allocated and the host does not wait."""
+    _need_gpu(frames, 'frames')
+    if bits == 16:
+        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
+        if width is not None and width != frames.shape[-1]:
+            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
+        single = frames.dim() == 2
+        (n, h, w), stride = ((1,) + tuple(frames.shape) if single else tuple(frames.shape)), 2 * frames.shape[-1]
+    else:
+        single = frames.dim() == 2
+        n, h, w, stride = _packed_frames(frames[None] if single else frames, bits, width, 'frames')
+    thr, slp, defects = defect_check(defect, h, w, frames.device)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    if shading is None:
+        if black_level:
+            raise ValueError('black_level %r without a shading: the corrected codes keep their black level' % (black_level,))
+        gains, k, gh, gw = None, 0, 0, 0
+    else:
+        gains, k, gh, gw = shading_check(shading, h, w, frames.device)
+    shape = (h, w) if single else (n, h, w)
+    if out is None:
+        out = torch.empty(shape, device=frames.device, dtype=torch.uint16)
+    elif (out.dtype != torch.uint16 or out.device != frames.device or tuple(out.shape) != shape or not out.is_contiguous()
+            or out.data_ptr() % 8):
+        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
+                         % (shape, frames.device, out.dtype, tuple(out.shape)))
+    elif (out.data_ptr() < frames.data_ptr() + frames.numel() * frames.element_size()
+            and frames.data_ptr() < out.data_ptr() + out.numel() * 2):
+        raise ValueError('out shares memory with the frames: the correction reads neighbours other threads would have overwritten')
+    L.call('risp_raw_defect', _p(frames), int(bits), stride, _p(out), thr, slp, _p(defects), _p(gains), k, gh, gw, int(black_level),
+           n, h, w, _stream())
+    return out
+
+
 def serve_classical_shaded(raw_u16, shading, divisor, demosaic, ops, params, reverse_channels=False, matrix=None, out=None,
                            black_level=0, cfa='rggb'):
     """``serve_classical_u8`` / ``serve_classical_nv12`` with the lens-shading correction inside the load, still ONE launch
