@@ -976,6 +976,55 @@ int risp_serve_classical_shaded(const uint16_t *raw, float divisor, int demosaic
 int risp_raw_defect(const void *raw, int bits, int stride, uint16_t *out, int threshold, int slope, const uint32_t *defects,
                     const uint16_t *gains, int cell_log2, int GH, int GW, int black_level, int N, int H, int W, void *stream);
 
+/* A scaled, cropped output at the end of the serving path (risp_resize.hip): the scaler / crop block behind an ISP's colour
+ * pipeline.  Packed 8-bit images are resampled separably, antialiased on reduction, with an integer tap table per axis - the
+ * design of Pillow's ImagingResample, made reproducible to the bit: Q14 weights, every row of weights sums to exactly 16384, and
+ * only IEEE basic operations (+ - * /, comparisons, truncation) build the table, so every machine builds the same integers
+ * (tests/resize_reference.py restates all of it in numpy; functional.resample_taps builds the tables on the host).
+ *
+ * Tap table of one axis.  S is the length of the source window, o its offset in the image, D the output length.  The kernel f
+ * has radius r:
+ *     box       f(x) = 1 for -0.5 < x <= 0.5, else 0                                  r = 0.5
+ *     triangle  f(x) = 1 - |x| for |x| < 1, else 0                                    r = 1
+ *     bicubic   Keys, a = -0.5, in Horner form as Pillow's bicubic_filter, t = |x|:
+ *               (((a + 2) t - (a + 3)) t) t + 1 for t < 1,  (((t - 5) t + 8) t - 4) a for t < 2, else 0        r = 2
+ * All in float64:  scale = S / D,  fs = max(scale, 1),  support = r * fs;  for output index i:  c = (i + 0.5) * scale,
+ *     lo = max(int(c - support + 0.5), 0),  hi = min(int(c + support + 0.5), S)        (int truncates)
+ *     w_k = f((k + lo - c + 0.5) / fs)  for k < hi - lo;   s = the sum of the w_k, left to right
+ *     q_k = floor(w_k / s * 16384 + 0.5);  the residue 16384 - sum(q) is added to the largest q_k (the first on a tie)
+ * Zero taps at either end are trimmed (lo moves with them).  T is the longest row.  start_i = min(lo_i, S - T), the row is
+ * written at column lo_i - start_i of a zero row of T int16, and then start_i += o.  T <= S always and o <= start_i,
+ * start_i + T <= o + S: the window enters only through o, so the result equals cropping first.  Starts never decrease with box
+ * and triangle and on every reduction; a bicubic enlargement trims the exact zeros at |x| = 1, 2 of an output that falls on a
+ * sample, and that row's start lies one past its neighbour's.
+ *
+ * Pixel.  Signed 32-bit arithmetic, >> the arithmetic shift (floor); with T <= 32 and int16 weights no sum reaches 2^31.
+ *     h(y,j,c)   = clamp((sum_k wx[j][k] * img(y, xs[j]+k, c) + 8192) >> 14, 0, 255)      horizontal first, rounded to a code
+ *     out(i,j,c) = clamp((sum_k wy[i][k] * h(ys[i]+k, j, c)   + 8192) >> 14, 0, 255)
+ * per channel, so the channel order does not matter.  NV12 out is the integer function above of out, unchanged.
+ *
+ * risp_bgr8_resize: img (N,H,W,3) -> out (N,OH,OW,3), or with coef (twelve integers as in risp_bgr8_to_nv12, validated
+ * likewise; rgb_in as there) -> out (N,3*OH/2,OW) NV12.  One launch, no host synchronisation.  xstart (OW) / ystart (OH) int32
+ * and xweight (OW x tx) / yweight (OH x ty) int16 are DEVICE tables as above, tx and ty their T.  A workgroup owns
+ * RISP_RESIZE_TILE_W output columns x tile_rows output rows: it resamples the source rows its tile needs horizontally into LDS
+ * as bytes, then runs the vertical sums from there.  The rows a tile needs depend on ystart, which this side cannot read: the
+ * caller passes tile_rows and span, the largest over all tiles of (largest ystart of its rows) + ty - (their smallest); a span
+ * whose rows do not fit RISP_RESIZE_LDS_BYTES is refused (take fewer tile_rows).  Inside the kernel every start is
+ * clamped into 0 .. W-1 (H-1) as it is loaded, every source index start + k into the image again, and every LDS row into the
+ * span: a wrong table gives wrong bytes - those of the clamped table -, never an access outside img.  No alignment
+ * is asked of img or of a BGR out - a packed row starts at any byte.  Rules (anything else is refused before the launch, the
+ * message names the value): no NULL pointer but coef, 1 <= N <= 65535, H, W, OH, OW in 1 .. 2^24, 1 <= tx <= min(W,
+ * RISP_RESIZE_MAX_TAPS) and ty likewise with H, 1 <= tile_rows <= 64, span >= 1, out not overlapping img; for NV12 OH, OW and
+ * tile_rows even and out 4-byte aligned.  functional.resample_taps refuses a geometry as soon as one support window hi - lo
+ * passes 32 samples, before trimming - reductions beyond 32:1 (box), 16:1 (triangle), 8:1 (bicubic).  Not covered: Lanczos
+ * (needs sin), such reductions, chroma-aware scaling, rotation. */
+#define RISP_RESIZE_MAX_TAPS 32
+#define RISP_RESIZE_TILE_W 64
+#define RISP_RESIZE_LDS_BYTES 65536
+int risp_bgr8_resize(const uint8_t *img, uint8_t *out, const int32_t *xstart, const int16_t *xweight, int tx, const int32_t *ystart,
+                     const int16_t *yweight, int ty, int tile_rows, int span, const int32_t *coef, int rgb_in, int N, int H, int W,
+                     int OH, int OW, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

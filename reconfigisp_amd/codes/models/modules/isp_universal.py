@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import defect_shade, fused_forward, serve, serve_frame, serve_load, serve_shade, wants_grad
+from .pipeline_fusion import defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -44,7 +44,8 @@ class _FixedPipeline(nn.Module):
                 self.all_params.append(nn.Parameter(torch.zeros(0)))
         self.intermediate_results = []
         self.last_serve_route = None            # 'fused' | 'classical' | 'scene' | 'denoise' (a median of size 5 .. 15 under fast_median too) | 'denoise_scene' | 'cond' | 'composed' | 'tiled' (serve_frame): what the last serve call ran
-        self.last_serve_store = None            # with out_format='nv12': 'fused' (the serving launch stored NV12) | 'pass' (the conversion launch did); None for 'bgr8'
+        self.last_serve_store = None            # with out_format='nv12': 'fused' (the serving launch stored NV12) | 'pass' (the conversion launch did) | 'resize' (with out_size / out_window: the resize launch did); None for 'bgr8'
+        self.last_serve_resize = None           # with out_size / out_window: 'pass' (risp_bgr8_resize behind the route); None without the keywords
         self.last_serve_shade = None            # with lens_shading: 'fused' (the serving launch shaded in its load) | 'pass' (risp_raw_shade did, decoding packed frames too); None without the keyword
         self.last_serve_defect = None           # with defect_correction: 'fused' (one risp_raw_defect launch corrected and shaded) | 'pass' (risp_raw_defect corrected; risp_raw_shade follows where lens_shading is given); None without the keyword
         self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
@@ -98,8 +99,9 @@ class _FixedPipeline(nn.Module):
         return x
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', raw_format='u16', raw_width=None,
-              lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
+              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
+              resample='triangle', raw_format='u16', raw_width=None, lens_shading=None, defect_correction=None, fast_median=False,
+              fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -166,18 +168,34 @@ class _FixedPipeline(nn.Module):
         ``risp_raw_defect`` launch in front of the route, which decodes packed frames too (``last_serve_load`` is then 'pass',
         ``last_serve_shade`` 'pass' with a shading).  ``last_serve_defect`` records the pre-pass as
         ``pipeline_fusion.defect_shade`` tells: 'fused' (that one launch shaded as well) or 'pass' (it corrected alone;
-        ``risp_raw_shade`` follows where a shading is given); None without the keyword.  ``out_format``, ``yuv_matrix``,
-        ``raw_format``, ``raw_width``, ``lens_shading``, ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are
-        keyword-only (``pipeline_fusion.serve``)."""
+        ``risp_raw_shade`` follows where a shading is given); None without the keyword.
+
+        ``out_size=(OH, OW)`` and ``out_window=(y0, x0, h, w)`` deliver a scaled, cropped image (N,OH,OW,3): the window of the
+        image as returned (default: all of it) resampled to ``out_size`` (default: the window's size, a crop) with ``resample``
+        'box', 'triangle' or 'bicubic' - the bytes of ``functional.bgr8_resize`` of the same call without the keywords, on the
+        route that call takes (include/risp.h has the integer definition).  The route serves packed BGR into a cached image
+        and one ``risp_bgr8_resize`` launch writes ``out``: ``last_serve_resize`` is 'pass', None without the keywords.  With
+        ``out_format='nv12'`` (N,3*OH/2,OW), OH and OW even; ``last_serve_store`` is then 'resize' (that launch stored NV12,
+        where ``pipeline_fusion.resize_store`` says 'fused') or 'pass' (``risp_bgr8_to_nv12`` followed it).  ``out_format``,
+        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``raw_width``, ``lens_shading``,
+        ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are keyword-only (``pipeline_fusion.serve``)."""
         with torch.no_grad():
+            # (the resize keywords are refused before the stage parameters are made: that is a launch)
+            resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
-                                                    out_format=out_format, yuv_matrix=yuv_matrix, raw_format=raw_format,
+                                                    out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size,
+                                                    out_window=out_window, resample=resample, raw_format=raw_format,
                                                     raw_width=raw_width, lens_shading=lens_shading,
                                                     defect_correction=defect_correction, fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
+            self.last_serve_resize = None
+            if out_size is not None or out_window is not None:
+                self.last_serve_resize = 'pass'
+                if out_format != 'bgr8':
+                    self.last_serve_store = 'resize' if resize_store(out_format) == 'fused' else 'pass'
             self.last_serve_load = serve_load(self.last_serve_route, raw_format)
             self.last_serve_shade = None
             if lens_shading is not None:
@@ -194,8 +212,8 @@ class _FixedPipeline(nn.Module):
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
-                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16', raw_width=None,
-                    defect_correction=None, lens_shading=None):
+                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
+                    resample='triangle', raw_format='u16', raw_width=None, defect_correction=None, lens_shading=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
         ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
@@ -208,17 +226,25 @@ class _FixedPipeline(nn.Module):
         (``last_serve_load`` 'pass').  ``lens_shading`` as in ``serve``: the whole frame is shaded once in front of the tiles
         (``last_serve_shade`` 'pass'), packed frames in that same launch.  ``defect_correction`` as in ``serve``: the whole
         frame is corrected once in front of the tiles and of the shading (``last_serve_defect`` as there), packed frames in
-        that same launch."""
+        that same launch.  ``out_size``, ``out_window`` and ``resample`` as in ``serve``: the frames are blended at the sensor's
+        size into a cached image and one ``risp_bgr8_resize`` launch writes (OH,OW,3) or (N,OH,OW,3) - NV12 likewise -;
+        ``last_serve_resize`` and ``last_serve_store`` as there."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
-                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix, raw_format=raw_format,
-                              raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
+                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix, out_size=out_size,
+                              out_window=out_window, resample=resample, raw_format=raw_format, raw_width=raw_width,
+                              defect_correction=defect_correction, lens_shading=lens_shading)
             self.last_serve_route = 'tiled'
             self.last_serve_load = serve_load('tiled', raw_format)
             self.last_serve_shade = None if lens_shading is None else serve_shade('tiled', raw_format)
             self.last_serve_defect = None if defect_correction is None else (
                 defect_shade(raw_format) if lens_shading is not None else 'pass')
             self.last_serve_store = None if out_format == 'bgr8' else 'pass'
+            self.last_serve_resize = None
+            if out_size is not None or out_window is not None:
+                self.last_serve_resize = 'pass'
+                if out_format != 'bgr8':
+                    self.last_serve_store = 'resize' if resize_store(out_format) == 'fused' else 'pass'
         return out
 
     @property

@@ -608,10 +608,77 @@ def _corrected(frames, defect, bits, w, raw_format, shade):
                        _shaded_u16(shape, device))
 
 
+# output formats a resized call stores from the resize launch itself (risp_bgr8_resize with the matrix) instead of resizing to
+# packed BGR and converting that with risp_bgr8_to_nv12.  'nv12' is listed only if the fused store beats the two launches by
+# more than the larger spread of the two legs in every measured row of profiles/serve_resize.txt (two sizes, triangle and
+# bicubic) - the rule of _FUSED_LOAD, _FUSED_SHADE and _DEFECT_SHADE_FUSED.  The verdict line of that file is this
+# table.  Measured: at 64 x 256 x 256 -> 128 x 128 the fused store is 6.4 us (triangle) and 4.3 us (bicubic) faster, far beyond
+# the spread; on the 3000 x 4000 frame -> 1080 x 1920 it is 0.5 us faster against a spread of 0.4 us (triangle) and 1.4 us SLOWER
+# (bicubic) - the NV12 store keeps half the threads of phase 2 idle, and the conversion launch costs 4 us there.  Three rows of
+# four, and the rule asks for all, so the table is empty and serve takes the two launches.  Both
+# forms stay reachable through functional.bgr8_resize.
+_RESIZE_NV12_FUSED = frozenset()
+
+
+def resize_store(out_format):
+    """Who stores the image of a call with ``out_size`` / ``out_window``: None for ``out_format='bgr8'`` (the resize launch
+    stores packed bytes); for 'nv12' 'fused' - ``risp_bgr8_resize`` stores NV12 itself - or 'pass' - it stores packed BGR into a
+    cached image and ``risp_bgr8_to_nv12`` follows.  A pure function of its argument: what ``serve`` / ``serve_frame`` do, and
+    ``last_serve_store`` reports 'resize' for 'fused' and 'pass' for 'pass'."""
+    if out_format == 'bgr8':
+        return None
+    if out_format != 'nv12':
+        raise ValueError("unknown out_format %r: 'bgr8' or 'nv12'" % (out_format,))
+    return 'fused' if out_format in _RESIZE_NV12_FUSED else 'pass'
+
+
+def _resize_bgr(shape, device):
+    """the packed sensor-size image a call with ``out_size`` / ``out_window`` serves into, kept per (shape, device, stream);
+    not the NV12 route's image: the conversion launch behind a resize reads that one at the output's size"""
+    return F._scene_buffer(device, 'resize_bgr', shape, torch.uint8)
+
+
+def _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, lead, device):
+    """a call with ``out_size`` / ``out_window``, checked on the host before anything is launched: (size, window, the twelve
+    integers or None); ``lead`` is the shape in front of the image's own dimensions"""
+    size, win = F.resize_check(out_size, out_window, resample, h, w, out_format == 'nv12')
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, size[0], size[1])
+    if out is not None:
+        shape, align = ((size[0], size[1], 3), 1) if coef is None else ((size[0] + size[0] // 2, size[1]),
+                                                                         4 if resize_store('nv12') == 'fused' else 1)
+        F._u8_out(out, tuple(lead) + shape, device, align)
+    return size, win, coef
+
+
+def resize_plan(raw, raw_format, raw_width, dims, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out):
+    """``_resize_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keywords: what
+    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
+    if out_size is None and out_window is None:
+        return None
+    if not isinstance(raw, torch.Tensor) or raw.dim() not in dims:
+        raise ValueError('expected %s frames, got %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
+                                                        tuple(getattr(raw, 'shape', ()))))
+    w = raw.shape[-1] if raw_format == 'u16' else _packed_plan(raw, raw_format, raw_width, dims)[1]
+    return _resize_plan(out_size, out_window, resample, raw.shape[-2], w, out_format, yuv_matrix, reverse_channels, out,
+                        tuple(raw.shape[:-2]), raw.device)
+
+
+def _resized(img, plan, resample, out):
+    """the end of a call with ``out_size`` / ``out_window``: the served packed image -> ``out`` through ``risp_bgr8_resize``,
+    which stores NV12 itself where ``resize_store`` says so; otherwise the conversion launch follows it"""
+    size, win, coef = plan
+    if coef is None:
+        return F.bgr8_resize(img, size, win, resample, out=out)
+    if resize_store('nv12') == 'fused':
+        return F.bgr8_resize(img, size, win, resample, coef, 'bgr', out)
+    bgr = F.bgr8_resize(img, size, win, resample, out=_nv12_bgr(tuple(img.shape[:-3]) + (size[0], size[1], 3), img.device))
+    return F.bgr8_to_nv12(bgr, coef, 'bgr', out)
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          raw_format='u16', raw_width=None, lens_shading=None, defect_correction=None, fast_median=False,
-          fast_denoise_scene=False):
+          out_size=None, out_window=None, resample='triangle', raw_format='u16', raw_width=None, lens_shading=None,
+          defect_correction=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -716,7 +783,19 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     live in a buffer of their own per shape, device and stream.  H >= 3, W % 4 == 0.  With ``out`` given a warm call allocates
     nothing and never waits for the device.  None is the call without the keyword.
 
-    ``out_format``, ``yuv_matrix``, ``raw_format``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
+    ``out_size=(OH, OW)`` and ``out_window=(y0, x0, h, w)`` deliver a scaled, cropped image: the window of the image as returned
+    (default: all of it) resampled to ``out_size`` (default: the window's size, a crop) with ``resample`` 'box', 'triangle' or
+    'bicubic' (``F.resize_check``; include/risp.h has the integer definition).  The route is chosen exactly as without the
+    keywords, and so is every ``fast_*``, load, shade and defect choice; it serves packed BGR (``reverse_channels`` honoured
+    there) into an image kept per shape, device and stream, and ONE ``risp_bgr8_resize`` launch writes ``out`` (N,OH,OW,3): the
+    bytes of ``F.bgr8_resize`` of the call without the keywords.  With ``out_format='nv12'`` the routes that own a fused NV12
+    store serve BGR too; the resize launch stores (N,3*OH/2,OW) NV12 itself where ``resize_store('nv12')`` says 'fused'
+    (``out`` 4-byte aligned), otherwise ``risp_bgr8_to_nv12`` follows it; OH and OW even.  The tap tables live on the device per
+    axis geometry and kernel: with ``out`` given a warm call uploads and allocates nothing and never waits.  Bad sizes, a window
+    outside the image, an unknown kernel, more than 32 taps on an axis, odd OH / OW with NV12 and a wrong ``out`` are refused
+    before anything is launched.  With both None the call is today's call, launch for launch, and ``resample`` is not read.
+
+    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -748,6 +827,13 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     defect = defect_correction
     if defect is not None:
         F.defect_check(defect, h, w, raw_u16.device)        # refused before anything is launched
+    if out_size is not None or out_window is not None:
+        plan = _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, (n,),
+                            raw_u16.device)                 # refused before anything is launched
+        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
+                                   _resize_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
+                                   fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect)
+        return _resized(img, plan, resample, out), route
     coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
     if coef is not None:
         if out is not None:
@@ -900,8 +986,9 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
-                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, raw_format='u16',
-                raw_width=None, defect_correction=None, lens_shading=None):
+                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None,
+                out_window=None, resample='triangle', raw_format='u16', raw_width=None, defect_correction=None,
+                lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -926,10 +1013,17 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     everything else: ``risp_raw_defect`` writes uint16 frames kept per shape, device and stream - from packed frames too, in
     place of the unpack launch; with ``lens_shading`` it shades in the same launch where ``defect_shade`` says 'fused', and
     ``risp_raw_shade`` follows otherwise.
+    ``out_size``, ``out_window`` and ``resample`` (keyword-only, as in ``serve``) deliver a scaled, cropped image: every frame
+    is blended into a packed sensor-size image kept per shape, device and stream (``reverse_channels`` honoured there) and ONE
+    ``risp_bgr8_resize`` launch behind the last frame writes ``out``: (OH,OW,3) or (N,OH,OW,3), with ``out_format='nv12'``
+    (3*OH/2,OW) or (N,3*OH/2,OW) - stored by that launch where ``resize_store('nv12')`` says 'fused', by ``risp_bgr8_to_nv12``
+    behind it otherwise.  Their refusals come before anything is launched.  With both None nothing changes.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
+    plan = resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample, out_format, yuv_matrix,
+                       reverse_channels, out)               # refused before anything is launched
     if lens_shading is not None or defect_correction is not None:
         if raw_format != 'u16':
             bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
@@ -975,8 +1069,11 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     size, stride = _pair(patch_size), _pair(patch_stride)
     origins, sel = frame_geometry(H, W, size, stride, cfa, frames.device)
     count, tile_batch = origins.shape[0], int(tile_batch)
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W)
-    if coef is None:
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W) if plan is None else None
+    if plan is not None:
+        # every frame is served at the sensor's size into the cached image; the resize launch behind the loop writes `out`
+        final, out = out, _resize_bgr((H, W, 3) if single else (n, H, W, 3), frames.device)
+    elif coef is None:
         out = F._u8_out(out, (H, W, 3) if single else (n, H, W, 3), frames.device, 1)
     else:
         out = F._u8_out(out, (H + H // 2, W) if single else (n, H + H // 2, W), frames.device, 1)
@@ -999,6 +1096,8 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
             else:
                 F.tile_blend_u8(stack, origins, (H, W), stride, False, bgr, code)
                 F.bgr8_to_nv12(bgr, coef, 'bgr', out if single else out[k])
+    if plan is not None:
+        return _resized(out, plan, resample, final)
     return out
 
 

@@ -751,6 +751,245 @@ def bgr8_to_nv12(img_u8, matrix='bt601_full', channels='bgr', out=None):
     return out
 
 
+# ---- a scaled, cropped output (risp_resize.hip; include/risp.h has the definition to the bit)
+RESAMPLE = ('box', 'triangle', 'bicubic')
+RESIZE_MAX_TAPS = 32                    # RISP_RESIZE_MAX_TAPS
+RESIZE_TILE_W = 64                      # RISP_RESIZE_TILE_W: output columns of a workgroup
+RESIZE_TILE_ROWS = (16, 8, 4, 2)        # output rows of a workgroup: the first whose source-row span fits the LDS budget
+RESIZE_LDS_BYTES = 65536                # RISP_RESIZE_LDS_BYTES
+_RESAMPLE_RADIUS = {'box': 0.5, 'triangle': 1.0, 'bicubic': 2.0}
+_RESAMPLE_LIMIT = {'box': '32:1', 'triangle': '16:1', 'bicubic': '8:1'}
+
+
+def _resample_weight(kernel, x):
+    """the three kernels on a float: comparisons and + - * only"""
+    if kernel == 'box':
+        return 1.0 if -0.5 < x <= 0.5 else 0.0
+    if x < 0.0:
+        x = -x
+    if kernel == 'triangle':
+        return 1.0 - x if x < 1.0 else 0.0
+    a = -0.5
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return (((x - 5.0) * x + 8.0) * x - 4.0) * a
+    return 0.0
+
+
+RESIZE_HOST_CACHE = 256                 # host tables and tile plans kept (least recently used beyond that)
+_RESAMPLE_BASE, _RESAMPLE_TAPS = {}, {}
+
+
+def _lru_get(cache, key):
+    hit = cache.pop(key, None)
+    if hit is not None:
+        cache[key] = hit                        # a dict keeps insertion order: the most recently used key is last
+    return hit
+
+
+def _lru_put(cache, key, value):
+    while len(cache) >= RESIZE_HOST_CACHE:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
+def resample_taps(S, D, kernel, offset=0):
+    """The integer tap table of one axis, built on the host (no device is touched): a source window of ``S`` samples at
+    ``offset`` in the image resampled to ``D`` samples with ``kernel`` (a name of ``RESAMPLE``) -> (start (D,) numpy int32,
+    weight (D,T) numpy int16): output i is the Q14 sum of weight[i][k] * source[start[i] + k].  Every row sums to exactly
+    16384, offset <= start and start + T <= offset + S, starts never decrease on a reduction, and only IEEE basic operations on float64 enter, so every machine
+    builds the same integers (include/risp.h has the definition; tests/resize_reference.py restates it).  A geometry whose
+    support window hi - lo passes ``RESIZE_MAX_TAPS`` samples for some output is refused (T <= 32 for everything served):
+    reductions up to 32:1 (box), 16:1 (triangle), 8:1 (bicubic).  The offset enters by addition only: the table of (S, D, kernel)
+    is built once, a moving window of one size costs an addition per position.  The last ``RESIZE_HOST_CACHE`` tables are kept;
+    the arrays returned are read-only."""
+    import numpy as np
+    if kernel not in RESAMPLE:
+        raise ValueError('unknown resample %r: one of %s' % (kernel, ', '.join(RESAMPLE)))
+    S, D, offset = _small_int(S, 1, 1 << 24), _small_int(D, 1, 1 << 24), _small_int(offset, 0, 1 << 24)
+    if S is None or D is None or offset is None:
+        raise ValueError('resample_taps: a source length and an output length in 1 .. 2^24 and an offset >= 0')
+    key = (S, D, kernel, offset)
+    hit = _lru_get(_RESAMPLE_TAPS, key)
+    if hit is not None:
+        return hit
+    base = _lru_get(_RESAMPLE_BASE, key[:3])
+    if base is None:
+        base = _lru_put(_RESAMPLE_BASE, key[:3], _resample_table(S, D, kernel))
+    start = base[0] + np.int32(offset)
+    start.setflags(write=False)
+    return _lru_put(_RESAMPLE_TAPS, key, (start, base[1]))
+
+
+def _resample_table(S, D, kernel):
+    """``resample_taps`` at offset 0, built from the definition"""
+    import math
+    import numpy as np
+    scale = S / D
+    fs = max(scale, 1.0)
+    support = _RESAMPLE_RADIUS[kernel] * fs
+    los, rows = [], []
+    for i in range(D):
+        c = (i + 0.5) * scale
+        lo, hi = max(int(c - support + 0.5), 0), min(int(c + support + 0.5), S)
+        if hi - lo > RESIZE_MAX_TAPS:
+            # judged on the support window, not on the trimmed row: whether an edge tap rounds to zero is an accident of the
+            # quantisation, and a table is refused before it is built
+            raise ValueError('resample %r from %d to %d samples: a support window of %d samples, at most RESIZE_MAX_TAPS = %d: '
+                             'the largest served reduction is %s' % (kernel, S, D, hi - lo, RESIZE_MAX_TAPS, _RESAMPLE_LIMIT[kernel]))
+        w = [_resample_weight(kernel, (k + lo - c + 0.5) / fs) for k in range(hi - lo)]
+        s = 0.0
+        for v in w:
+            s += v
+        if not s > 0.0:
+            raise ValueError('resample %r from %d to %d samples: output %d has no weight' % (kernel, S, D, i))
+        q = [int(math.floor(v / s * 16384 + 0.5)) for v in w]
+        q[q.index(max(q))] += 16384 - sum(q)
+        while q[0] == 0:
+            q.pop(0)
+            lo += 1
+        while q[-1] == 0:
+            q.pop()
+        los.append(lo)
+        rows.append(q)
+    T = max(len(q) for q in rows)
+    start, weight = np.zeros(D, dtype=np.int32), np.zeros((D, T), dtype=np.int16)
+    for i, (lo, q) in enumerate(zip(los, rows)):
+        at = min(lo, S - T)
+        weight[i, lo - at:lo - at + len(q)] = q
+        start[i] = at
+    start.setflags(write=False)
+    weight.setflags(write=False)
+    return start, weight
+
+
+def resize_check(out_size, out_window, resample, H, W, nv12=False):
+    """The resize keywords for H x W images, checked on the host before anything is launched -> ((OH, OW), (y0, x0, h, w))
+    normalised.  ``out_window=(y0, x0, h, w)`` lies inside the image (None: the whole image); ``out_size=(OH, OW)`` is at least
+    1 x 1 (None: the window's size, a crop); ``resample`` is a name of ``RESAMPLE``; with ``nv12`` OH and OW are even; neither
+    axis needs more than ``RESIZE_MAX_TAPS`` taps; the output has at most 65535 row tiles (``resize_tile_rows``)."""
+    if resample not in RESAMPLE:
+        raise ValueError('unknown resample %r: one of %s' % (resample, ', '.join(RESAMPLE)))
+    H, W = int(H), int(W)
+    if out_window is None:
+        win = (0, 0, H, W)
+    else:
+        try:
+            win = tuple(_small_int(v, 0, 1 << 24) for v in out_window)
+        except TypeError:
+            win = ()
+        if len(win) != 4 or None in win:
+            raise ValueError('out_window %r: (y0, x0, h, w) as integers' % (out_window,))
+        if win[2] < 1 or win[3] < 1 or win[0] + win[2] > H or win[1] + win[3] > W:
+            raise ValueError('out_window %r lies outside the %d x %d image (or is empty)' % (out_window, H, W))
+    if out_size is None:
+        size = win[2:]
+    else:
+        try:
+            size = tuple(_small_int(v, 1, 1 << 24) for v in out_size)
+        except TypeError:
+            size = ()
+        if len(size) != 2 or None in size:
+            raise ValueError('out_size %r: (OH, OW) as integers >= 1' % (out_size,))
+    if nv12 and (size[0] % 2 or size[1] % 2):
+        raise ValueError('a %d x %d output has no 4:2:0 form: OH and OW must be even' % size)
+    resample_taps(win[2], size[0], resample, win[0])
+    resample_taps(win[3], size[1], resample, win[1])
+    rows = resize_tile_rows(win[2], size[0], resample, win[0])[0]
+    if (size[0] + rows - 1) // rows > 65535:
+        raise ValueError('out_size %r: %d output rows in tiles of %d are more than 65535 row tiles' % (out_size, size[0], rows))
+    return size, win
+
+
+_RESIZE_TABLES = {}
+
+
+def release_resize_tables():
+    """Drop the device tap tables of ``bgr8_resize`` (every device).  They are kept per (axis geometry with its offset, kernel,
+    device) and never dropped otherwise - a captured graph holds their addresses, as it holds ``frame_geometry``'s origins -, so
+    a caller that moves or zooms its window through many positions uploads two small tables (4 + 2 T bytes per output row or
+    column) per new position and calls this between sessions; no graph captured before may be replayed after."""
+    _RESIZE_TABLES.clear()
+
+
+def _resize_axis(S, D, kernel, offset, device):
+    """(start, weight) of ``resample_taps`` as device tensors with T and the host's start, kept per (axis geometry, kernel,
+    device) until ``release_resize_tables``: a warm call uploads nothing"""
+    key = (S, D, kernel, offset, device.type, device.index)
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        start, weight = resample_taps(S, D, kernel, offset)
+        hit = _RESIZE_TABLES[key] = (torch.from_numpy(start.copy()).to(device), torch.from_numpy(weight.copy()).to(device),
+                                     weight.shape[1], start)
+    return hit
+
+
+_RESIZE_TILES = {}
+
+
+def resize_tile_rows(S, D, kernel, offset=0):
+    """(tile rows, span) of the resize launch for the vertical axis ``resample_taps(S, D, kernel, offset)``: the first row count
+    of ``RESIZE_TILE_ROWS`` whose largest source-row span over all tiles - the largest start of the tile's rows + T - their
+    smallest - fits ``RESIZE_LDS_BYTES`` beside the table slices (the C side checks the same sum).  The last ``RESIZE_HOST_CACHE``
+    answers are kept."""
+    key = (int(S), int(D), kernel, int(offset))
+    hit = _lru_get(_RESIZE_TILES, key)
+    if hit is None:
+        start, weight = resample_taps(S, D, kernel, offset)
+        D, T = weight.shape
+        for rows in RESIZE_TILE_ROWS:
+            # (starts are not monotone everywhere - a bicubic enlargement trims the zero outer taps of an output that falls on a
+            # sample -, so a tile's rows run from its smallest start to its largest plus T)
+            span = max(int(start[i:i + rows].max()) + T - int(start[i:i + rows].min()) for i in range(0, D, rows))
+            # (the horizontal table has at most RESIZE_MAX_TAPS taps too)
+            if (span * RESIZE_TILE_W * 3 + (RESIZE_TILE_W + rows) * 4
+                    + (RESIZE_TILE_W * RESIZE_MAX_TAPS + rows * T) * 2 <= RESIZE_LDS_BYTES):
+                break
+        else:
+            raise ValueError('resample %r from %d to %d rows: %d source rows for %d output rows do not fit the launch'
+                             % (kernel, S, D, span, rows))
+        hit = _lru_put(_RESIZE_TILES, key, (rows, span))
+    return hit
+
+
+def bgr8_resize(img_u8, out_size=None, out_window=None, resample='triangle', nv12=None, channels='bgr', out=None):
+    """Packed 8-bit images scaled and cropped in ONE launch (``risp_bgr8_resize``): (N,H,W,3) or (H,W,3) ``torch.uint8`` on the
+    device -> (N,OH,OW,3) or (OH,OW,3), the window ``out_window=(y0, x0, h, w)`` of every image (default: all of it)
+    resampled to ``out_size=(OH, OW)`` (default: the window's size - a crop, one tap of 16384) with ``resample`` 'box',
+    'triangle' or 'bicubic': separable, antialiased on reduction, horizontal first, Q14 integer taps whose rows sum to 16384
+    (``resample_taps``; include/risp.h fixes every bit).  With ``nv12`` (a matrix as ``nv12_matrix`` takes it) the same launch
+    stores (N,3*OH/2,OW) YUV 4:2:0 instead, byte for byte ``bgr8_to_nv12`` of the packed result; ``channels`` 'bgr' or 'rgb'
+    then names the order of the input (OH, OW even, ``out`` 4-byte aligned).  No alignment is asked of the images or of a
+    packed ``out``; ``out`` must not share memory with the images.  The tap tables live on the device per (axis geometry,
+    kernel, device) until ``release_resize_tables``: a warm call on contiguous images uploads nothing, with ``out`` given
+    allocates nothing, and the host never waits; images that are not contiguous are copied first, which allocates."""
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
+        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
+                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
+    if channels not in ('bgr', 'rgb'):
+        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    coef = None if nv12 is None else nv12_matrix(nv12)
+    h, w = img_u8.shape[-3], img_u8.shape[-2]
+    (oh, ow), (y0, x0, wh, ww) = resize_check(out_size, out_window, resample, h, w, coef is not None)
+    _need_gpu(img_u8, 'img')
+    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
+    if n > 65535:
+        raise ValueError('%d images in one call: at most 65535' % n)
+    img_u8 = img_u8.contiguous()
+    shape = tuple(img_u8.shape[:-3]) + ((oh, ow, 3) if coef is None else (oh + oh // 2, ow))
+    out = _u8_out(out, shape, img_u8.device, 1 if coef is None else 4)
+    if (out.data_ptr() < img_u8.data_ptr() + img_u8.numel() and img_u8.data_ptr() < out.data_ptr() + out.numel()):
+        raise ValueError('out shares memory with the images: a tile reads rows other tiles would have overwritten')
+    xs, xw, tx, _ = _resize_axis(ww, ow, resample, x0, img_u8.device)
+    ys, yw, ty, _ = _resize_axis(wh, oh, resample, y0, img_u8.device)
+    rows, span = resize_tile_rows(wh, oh, resample, y0)
+    L.call('risp_bgr8_resize', _p(img_u8), _p(out), _p(xs), _p(xw), tx, _p(ys), _p(yw), ty, rows, span,
+           None if coef is None else (C.c_int * 12)(*coef), int(channels == 'rgb'), n, h, w, oh, ow, _stream())
+    return out
+
+
 def serve_nv12(raw_u16, divisor, ops, params, bilateral=None, matrix='bt601_full', out=None, black_level=0, cfa='rggb'):
     """``serve_u8`` with the NV12 store (``risp_serve_nv12``, ONE launch): the same arguments with ``matrix``
     (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte
