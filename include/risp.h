@@ -976,6 +976,34 @@ int risp_serve_classical_shaded(const uint16_t *raw, float divisor, int demosaic
 int risp_raw_defect(const void *raw, int bits, int stride, uint16_t *out, int threshold, int slope, const uint32_t *defects,
                     const uint16_t *gains, int cell_log2, int GH, int GW, int black_level, int N, int H, int W, void *stream);
 
+/* 3A statistics of the sensor frame (risp_stats.hip): the statistics block of a hardware ISP - per-zone colour sums for
+ * auto-white-balance, histograms for auto-exposure, a focus measure for autofocus -, taken on the linear samples the route
+ * demosaics.  Counts and sums of integers, fixed to the bit and without a summation order (tests/stats_reference.py restates
+ * them in numpy int64).
+ * s(y,x) = max(S(y,x) - black_level, 0), S the decoded sample of the frame as stored - uint16, or RAW10 / RAW12 as above.
+ * Coordinates are those of the frame as stored, whatever cfa says; the plane of a pixel is c = 2 * (y & 1) + (x & 1).
+ * A specification is (zone_h, zone_w, bins, hist_shift, lo, hi).  ZH = ceil(H / zone_h), ZW = ceil(W / zone_w); pixel (y,x)
+ * belongs to zone (y / zone_h, x / zone_w); the last row and column of zones may be partial.  For each image, zone and plane:
+ *     count  the number of the zone's samples of that plane with lo <= s <= hi
+ *     sum    the sum of those samples
+ *     sharp  the sum of |2 s(y,x) - s(y,x-2) - s(y,x+2)| over the zone's pixels of that plane with 2 <= x < W - 2, whatever lo
+ *            and hi are: a pixel without both neighbours inside the frame adds nothing (no reflection); a neighbour may lie
+ *            in the next zone
+ * and for each image and plane   hist[min(s >> hist_shift, bins - 1)] += 1   over every sample of the frame.
+ *
+ * risp_raw_stats: frames -> zones (N,ZH,ZW,4,3) int64 holding [sum, count, sharp] and hist (N,4,bins) int32, both contiguous
+ * and both overwritten: they are zeroed on the stream (one memset where hist lies right behind zones, else two), then ONE launch
+ * reads bits / 8 bytes per pixel.  The values pass 2^32 on real frames (131072 samples of 65535 already do), which is why zones
+ * is 64-bit; a workgroup's partials are 32-bit and bounded by its tile (risp_stats.hip).  raw, bits and stride as in
+ * risp_raw_shade: uint16 rows (2-byte aligned, wider loads when raw and stride are 8-byte aligned) or packed rows from any byte,
+ * decoded on the way.  Rules (anything else is refused before anything is issued, the message names the value): no NULL,
+ * N >= 1, H even, W >= 4 and W % 4 == 0, the stride rules of the format, black_level 0 .. 65535, zone_h even and >= 2,
+ * zone_w >= 4 and zone_w % 4 == 0, ZH * ZW <= 65536, bins 1 .. 1024, hist_shift 0 .. 16, 0 <= lo <= hi <= 65535,
+ * H * W / 4 < 2^31, zones 8-byte and hist 4-byte aligned.  Not covered: statistics gathered inside another launch, vertical or
+ * IIR focus filters, statistics behind the demosaic, per-zone histograms. */
+int risp_raw_stats(const void *raw, int bits, int stride, int black_level, long long *zones, int *hist, int zone_h, int zone_w,
+                   int bins, int hist_shift, int lo, int hi, int N, int H, int W, void *stream);
+
 /* A scaled, cropped output at the end of the serving path (risp_resize.hip): the scaler / crop block behind an ISP's colour
  * pipeline.  Packed 8-bit images are resampled separably, antialiased on reduction, with an integer tap table per axis - the
  * design of Pillow's ImagingResample, made reproducible to the bit: Q14 weights, every row of weights sums to exactly 16384, and

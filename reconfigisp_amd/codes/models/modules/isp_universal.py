@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, wants_grad
+from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -48,6 +48,7 @@ class _FixedPipeline(nn.Module):
         self.last_serve_resize = None           # with out_size / out_window: 'pass' (risp_bgr8_resize behind the route); None without the keywords
         self.last_serve_shade = None            # with lens_shading: 'fused' (the serving launch shaded in its load) | 'pass' (risp_raw_shade did, decoding packed frames too); None without the keyword
         self.last_serve_defect = None           # with defect_correction: 'fused' (one risp_raw_defect launch corrected and shaded) | 'pass' (risp_raw_defect corrected; risp_raw_shade follows where lens_shading is given); None without the keyword
+        self.last_serve_stats = None            # with statistics: 'pass' (risp_raw_stats filled the RawStatistics from what the route reads); None without the keyword
         self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
 
     def _apply(self, fn, *args, **kwargs):
@@ -100,8 +101,8 @@ class _FixedPipeline(nn.Module):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
-              resample='triangle', raw_format='u16', raw_width=None, lens_shading=None, defect_correction=None, fast_median=False,
-              fast_denoise_scene=False):
+              resample='triangle', raw_format='u16', statistics=None, raw_width=None, lens_shading=None, defect_correction=None,
+              fast_median=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -177,17 +178,26 @@ class _FixedPipeline(nn.Module):
         and one ``risp_bgr8_resize`` launch writes ``out``: ``last_serve_resize`` is 'pass', None without the keywords.  With
         ``out_format='nv12'`` (N,3*OH/2,OW), OH and OW even; ``last_serve_store`` is then 'resize' (that launch stored NV12,
         where ``pipeline_fusion.resize_store`` says 'fused') or 'pass' (``risp_bgr8_to_nv12`` followed it).  ``out_format``,
-        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``raw_width``, ``lens_shading``,
-        ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are keyword-only (``pipeline_fusion.serve``)."""
+        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``raw_width``,
+        ``lens_shading``, ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are keyword-only
+        (``pipeline_fusion.serve``).
+
+        ``statistics=st`` (a ``functional.RawStatistics``, built once by ``functional.raw_statistics``) also fills ``st.zones``
+        and ``st.hist`` with the 3A statistics of the samples the route demosaics - zone sums and counts, the focus measure,
+        histograms; include/risp.h has the integer definition.  ``st`` is checked before anything is launched, then
+        ``risp_raw_stats`` reads what the route is about to read: the pre-pass's frames with ``defect_correction`` and / or
+        ``lens_shading`` (the shade launch then runs: ``last_serve_shade`` 'pass'), otherwise the input as given.  The image
+        bytes and the route are those of the call without the keyword.  ``last_serve_stats`` is 'pass', None without it."""
         with torch.no_grad():
             # (the resize keywords are refused before the stage parameters are made: that is a launch)
             resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
+            stats_plan(raw_u16, raw_format, raw_width, (3,), statistics)
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                                     out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size,
                                                     out_window=out_window, resample=resample, raw_format=raw_format,
-                                                    raw_width=raw_width, lens_shading=lens_shading,
+                                                    statistics=statistics, raw_width=raw_width, lens_shading=lens_shading,
                                                     defect_correction=defect_correction, fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
@@ -209,11 +219,17 @@ class _FixedPipeline(nn.Module):
                     self.last_serve_load = 'pass'
                 if lens_shading is not None:
                     self.last_serve_shade = 'pass'
+            self.last_serve_stats = None
+            if statistics is not None:
+                self.last_serve_stats = 'pass'
+                if lens_shading is not None:
+                    self.last_serve_shade = 'pass'
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
-                    resample='triangle', raw_format='u16', raw_width=None, defect_correction=None, lens_shading=None):
+                    resample='triangle', raw_format='u16', statistics=None, raw_width=None, defect_correction=None,
+                    lens_shading=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
         ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
@@ -228,13 +244,15 @@ class _FixedPipeline(nn.Module):
         frame is corrected once in front of the tiles and of the shading (``last_serve_defect`` as there), packed frames in
         that same launch.  ``out_size``, ``out_window`` and ``resample`` as in ``serve``: the frames are blended at the sensor's
         size into a cached image and one ``risp_bgr8_resize`` launch writes (OH,OW,3) or (N,OH,OW,3) - NV12 likewise -;
-        ``last_serve_resize`` and ``last_serve_store`` as there."""
+        ``last_serve_resize`` and ``last_serve_store`` as there.  ``statistics`` as in ``serve``: the 3A statistics of the whole
+        frames, (H,W) being one image, taken once in front of the tiles (``last_serve_stats`` 'pass')."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
                               reverse_channels, out, black_level, cfa, out_format, yuv_matrix, out_size=out_size,
-                              out_window=out_window, resample=resample, raw_format=raw_format, raw_width=raw_width,
-                              defect_correction=defect_correction, lens_shading=lens_shading)
+                              out_window=out_window, resample=resample, raw_format=raw_format, statistics=statistics,
+                              raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
             self.last_serve_route = 'tiled'
+            self.last_serve_stats = None if statistics is None else 'pass'
             self.last_serve_load = serve_load('tiled', raw_format)
             self.last_serve_shade = None if lens_shading is None else serve_shade('tiled', raw_format)
             self.last_serve_defect = None if defect_correction is None else (

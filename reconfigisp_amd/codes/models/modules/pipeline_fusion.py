@@ -675,10 +675,29 @@ def _resized(img, plan, resample, out):
     return F.bgr8_to_nv12(bgr, coef, 'bgr', out)
 
 
+def stats_plan(raw, raw_format, raw_width, dims, statistics):
+    """``F.stats_check`` of ``statistics`` from the frames as given - uint16 or packed, of ``dims`` dimensions, one image for an
+    (H,W) frame -, nothing for None: what ``serve_frame`` and the modules' ``serve`` check before their first launch"""
+    if statistics is None:
+        return None
+    if not isinstance(statistics, F.RawStatistics):
+        raise ValueError('statistics must be a RawStatistics (functional.raw_statistics builds one), got %s'
+                         % (type(statistics).__name__,))
+    if raw_format != 'u16':
+        w = _packed_plan(raw, raw_format, raw_width, dims)[1]
+    elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint16 or raw.dim() not in dims:
+        raise ValueError('expected %s uint16 frames, got %s %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
+                                                                   getattr(raw, 'dtype', type(raw)), tuple(getattr(raw, 'shape', ()))))
+    else:
+        w = raw.shape[-1]
+    F._need_gpu(raw, 'raw')
+    return F.stats_check(statistics, 1 if raw.dim() == 2 else raw.shape[0], raw.shape[-2], w, raw.device)
+
+
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          out_size=None, out_window=None, resample='triangle', raw_format='u16', raw_width=None, lens_shading=None,
-          defect_correction=None, fast_median=False, fast_denoise_scene=False):
+          out_size=None, out_window=None, resample='triangle', raw_format='u16', statistics=None, raw_width=None,
+          lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -795,7 +814,18 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     outside the image, an unknown kernel, more than 32 taps on an axis, odd OH / OW with NV12 and a wrong ``out`` are refused
     before anything is launched.  With both None the call is today's call, launch for launch, and ``resample`` is not read.
 
-    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
+    ``statistics=st`` (an ``F.RawStatistics`` built once for these N, H, W: ``F.raw_statistics``) also fills ``st.zones`` and
+    ``st.hist`` with the 3A statistics of the samples the route demosaics - per zone and Bayer plane of the frame as stored the
+    sum and the count of the samples in lo .. hi and the horizontal focus measure, per image and plane a histogram
+    (include/risp.h has the integer definition; ``F.stats_planes(cfa)`` names the planes).  ``st`` is checked before anything is
+    launched; then ``risp_raw_stats`` - a memset and one launch - reads what the route is about to read: with
+    ``defect_correction`` and / or ``lens_shading`` the cached corrected uint16 frames (black level 0 behind a shading),
+    otherwise the input as given, packed or not, with ``black_level``.  With ``lens_shading`` the shade launch runs: no fused
+    shading load is taken, as under ``defect_correction``.  Everything else about the route is chosen exactly as without the
+    keyword and the image bytes are the same.  H even, W % 4 == 0.  With ``out`` given a warm call allocates nothing and never
+    waits for the device; a captured call zeroes ``st`` on every replay.  None is today's call, launch for launch.
+
+    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -827,28 +857,32 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     defect = defect_correction
     if defect is not None:
         F.defect_check(defect, h, w, raw_u16.device)        # refused before anything is launched
+    stats = statistics
+    if stats is not None:
+        F.stats_check(stats, n, h, w, raw_u16.device)       # refused before anything is launched
     if out_size is not None or out_window is not None:
         plan = _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, (n,),
                             raw_u16.device)                 # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
                                    _resize_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
-                                   fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect)
+                                   fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect,
+                                   stats=stats)
         return _resized(img, plan, resample, out), route
     coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
     if coef is not None:
         if out is not None:
             F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade, defect)
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade, defect, stats)
         return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
     return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
                       fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade,
-                      defect=defect)
+                      defect=defect, stats=stats)
 
 
 def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
                fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False, shade=None,
-               defect=None):
+               defect=None, stats=None):
     """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
     NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
     With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
@@ -860,7 +894,10 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
     from the uint16 or the packed frames.
     With ``defect`` = (threshold, slope, defects): the route is once more the one uint16 frames from the allocator take and
     every route runs on ``frames()``, the cached uint16 stack ``risp_raw_defect`` fills from the uint16 or the packed frames -
-    shaded too with ``shade``, by that launch or by ``risp_raw_shade`` behind it (``defect_shade``); no fused load is taken"""
+    shaded too with ``shade``, by that launch or by ``risp_raw_shade`` behind it (``defect_shade``); no fused load is taken.
+    With ``stats`` (a checked ``F.RawStatistics``): ``risp_raw_stats`` reads what the route is about to read - behind a pre-pass
+    its cached frames, which are then made first and no fused shading load is taken, otherwise the input as given, packed or
+    not, with ``black_level``; the route is chosen as without it"""
     device = raw_u16.device
     if defect is not None:
         (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
@@ -888,6 +925,19 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
 
         def frames():
             return F.raw_unpack(packed[0], packed[1], w, _packed_u16((n, h, w), device))
+    if stats is not None:
+        if defect is not None or shade is not None:
+            # the pre-pass runs now and the statistics read its frames; nothing behind it sees a shading (no fused shading load)
+            ready = frames()
+            shade = None
+
+            def frames():
+                return ready
+            F.raw_stats(ready, stats, black_level, 16, w)
+        elif packed is not None:
+            F.raw_stats(packed[0], stats, black_level, packed[1], w)
+        else:
+            F.raw_stats(raw_u16, stats, black_level, 16, w)
     code = F.cfa_code(cfa)
     # where a route without the NV12 store writes its packed image
     dst = (lambda: out) if coef is None else (lambda: _nv12_bgr((n, h, w, 3), device))
@@ -987,8 +1037,8 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
                 out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None,
-                out_window=None, resample='triangle', raw_format='u16', raw_width=None, defect_correction=None,
-                lens_shading=None):
+                out_window=None, resample='triangle', raw_format='u16', statistics=None, raw_width=None,
+                defect_correction=None, lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -1018,12 +1068,20 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     ``risp_bgr8_resize`` launch behind the last frame writes ``out``: (OH,OW,3) or (N,OH,OW,3), with ``out_format='nv12'``
     (3*OH/2,OW) or (N,3*OH/2,OW) - stored by that launch where ``resize_store('nv12')`` says 'fused', by ``risp_bgr8_to_nv12``
     behind it otherwise.  Their refusals come before anything is launched.  With both None nothing changes.
+    ``statistics=st`` (keyword-only, as in ``serve``; an ``F.RawStatistics`` for N frames, N = 1 for an (H,W) frame) fills ``st``
+    with the 3A statistics of the whole frames the tiles are cut from: ``risp_raw_stats`` runs once, on the frames of the
+    pre-pass where ``defect_correction`` or ``lens_shading`` is given (black level 0 behind a shading), otherwise on the input
+    as given, packed or not, with ``black_level``.  ``st`` is checked before anything is launched; the image is unchanged.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
     plan = resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample, out_format, yuv_matrix,
                        reverse_channels, out)               # refused before anything is launched
+    if statistics is not None:                              # refused before anything is launched
+        stats_plan(raw_u16, raw_format, raw_width, (2, 3), statistics)
+        if black_level != int(black_level) or not 0 <= black_level < white_level:
+            raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
     if lens_shading is not None or defect_correction is not None:
         if raw_format != 'u16':
             bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
@@ -1050,6 +1108,11 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
         if lens_shading is not None:
             white_level, black_level = white_level - black_level, 0
         raw_format = 'u16'
+        if statistics is not None:                          # the statistics of the pre-pass's frames
+            F.raw_stats(raw_u16, statistics, int(black_level), 16)
+    elif statistics is not None:                            # of the input as given, packed or not
+        F.raw_stats(raw_u16.contiguous(), statistics, int(black_level), F.raw_format_bits(raw_format) or 16,
+                    raw_width if raw_format != 'u16' else None)
     if raw_format != 'u16':
         bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
         F._need_gpu(raw_u16, 'raw')

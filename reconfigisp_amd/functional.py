@@ -1355,6 +1355,131 @@ def raw_defect(frames, defect, bits=16, width=None, shading=None, black_level=0,
     return out
 
 
+def _stats_spec(zone, bins, hist_shift, lo, hi):
+    """the specification of the 3A statistics, checked on the host -> (zone_h, zone_w, bins, hist_shift, lo, hi) as ints"""
+    try:
+        zone_h, zone_w = zone
+    except (TypeError, ValueError):
+        raise ValueError('a statistics zone is (zone_h, zone_w) in pixels, got %r' % (zone,)) from None
+    zh = _small_int(zone_h, 2, 1 << 30)
+    if zh is None or zh % 2:
+        raise ValueError('zone_h %r: an even integer, at least 2 (a Bayer row pair lies in one zone)' % (zone_h,))
+    zw = _small_int(zone_w, 4, 1 << 30)
+    if zw is None or zw % 4:
+        raise ValueError('zone_w %r: a multiple of 4, at least 4' % (zone_w,))
+    nb = _small_int(bins, 1, 1024)
+    if nb is None:
+        raise ValueError('bins %r: an integer in 1 .. 1024' % (bins,))
+    shift = _small_int(hist_shift, 0, 16)
+    if shift is None:
+        raise ValueError('hist_shift %r: an integer in 0 .. 16' % (hist_shift,))
+    low, high = _small_int(lo, 0, 65535), _small_int(hi, 0, 65535)
+    if low is None or high is None or low > high:
+        raise ValueError('lo %r, hi %r: integers with 0 <= lo <= hi <= 65535' % (lo, hi))
+    return zh, zw, nb, shift, low, high
+
+
+def _stats_shape(n, h, w, zh, zw):
+    """the frames a statistics block is built for -> (ZH, ZW); N >= 1, H even, W >= 4 and a multiple of 4, at most 65536 zones"""
+    if _small_int(n, 1, 1 << 30) is None:
+        raise ValueError('statistics of %r frames: N >= 1' % (n,))
+    if _small_int(h, 2, 1 << 30) is None or h % 2:
+        raise ValueError('statistics of frames %r high: H must be even' % (h,))
+    if _small_int(w, 4, 1 << 30) is None or w % 4:
+        raise ValueError('statistics of frames %r wide: W must be a multiple of 4, at least 4' % (w,))
+    gh, gw = -(-int(h) // zh), -(-int(w) // zw)
+    if gh * gw > 65536:
+        raise ValueError('%d x %d zones of %d x %d pixels on a %d x %d frame: more than 65536' % (gh, gw, zh, zw, h, w))
+    return gh, gw
+
+
+class RawStatistics:
+    """The 3A statistics of (N,H,W) sensor frames and the buffers that take them: ``zone`` = (zone_h, zone_w) pixels per zone
+    (even, a multiple of 4), ``bins`` histogram bins of ``1 << hist_shift`` codes (the last one takes everything above),
+    ``lo`` .. ``hi`` the samples that enter ``sum`` and ``count``.  ``.zones``: (N,ZH,ZW,4,3) ``torch.int64`` holding
+    [sum, count, sharp] per zone and plane 2 * (y & 1) + (x & 1) of the frame as stored (``stats_planes`` names the planes of a
+    ``cfa``); ``.hist``: (N,4,bins) ``torch.int32``.  Both are views of one allocation, the histogram right behind the zones, so
+    that ``risp_raw_stats`` zeroes them with one memset.  Built once by the caller (``raw_statistics``) and overwritten by
+    every call that takes it (include/risp.h has the definition to the bit)."""
+
+    def __init__(self, n, h, w, zone=(16, 16), bins=256, hist_shift=0, lo=0, hi=65535, device=None):
+        self.zone_h, self.zone_w, self.bins, self.hist_shift, self.lo, self.hi = _stats_spec(zone, bins, hist_shift, lo, hi)
+        self.grid = _stats_shape(n, h, w, self.zone_h, self.zone_w)
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        self._checked = None                    # what stats_check validated last
+        words, counts = self.n * self.grid[0] * self.grid[1] * 12, self.n * 4 * self.bins
+        buf = torch.zeros(words + (counts + 1) // 2, dtype=torch.int64, device='cuda' if device is None else device)
+        self.zones = buf[:words].view(self.n, self.grid[0], self.grid[1], 4, 3)
+        self.hist = buf[words:].view(torch.int32)[:counts].view(self.n, 4, self.bins)
+
+    def __repr__(self):
+        return 'RawStatistics(%d, %d, %d, zone=(%d, %d), bins=%d, hist_shift=%d, lo=%d, hi=%d)' % (
+            self.n, self.h, self.w, self.zone_h, self.zone_w, self.bins, self.hist_shift, self.lo, self.hi)
+
+
+def raw_statistics(n, h, w, zone=(16, 16), bins=256, hist_shift=0, lo=0, hi=65535, device=None):
+    """A ``RawStatistics`` for (N,H,W) frames on ``device`` (None: the current HIP device): built once, it owns ``.zones`` and
+    ``.hist``, which ``raw_stats`` and ``serve(statistics=)`` overwrite.  Everything the definition refuses is refused here."""
+    return RawStatistics(n, h, w, zone, bins, hist_shift, lo, hi, device)
+
+
+def stats_check(st, n, h, w, device=None):
+    """A ``RawStatistics`` for N frames of H x W on ``device``, checked on the host before anything is launched ->
+    (zone_h, zone_w, bins, hist_shift, lo, hi).  The specification is checked again (its fields can be assigned), then the
+    outputs: ``.zones`` contiguous (N,ZH,ZW,4,3) int64 and ``.hist`` contiguous (N,4,bins) int32, both on ``device``.  Nothing
+    on the device is read: the host never waits."""
+    if not isinstance(st, RawStatistics):
+        raise ValueError('statistics must be a RawStatistics (functional.raw_statistics builds one), got %s' % (type(st).__name__,))
+    # (a served call comes here three times and is bound by its host side: the integers are validated once per value)
+    key = (st.zone_h, st.zone_w, st.bins, st.hist_shift, st.lo, st.hi, n, h, w)
+    if st._checked is None or st._checked[0] != key:
+        spec = _stats_spec((st.zone_h, st.zone_w), st.bins, st.hist_shift, st.lo, st.hi)
+        st._checked = (key, spec, _stats_shape(n, h, w, spec[0], spec[1]))
+    _, spec, (gh, gw) = st._checked
+    bins = spec[2]
+    for name, t, shape, dtype in (('zones', st.zones, (int(n), gh, gw, 4, 3), torch.int64),
+                                  ('hist', st.hist, (int(n), 4, bins), torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError('statistics.%s for %d frames of %d x %d must be a contiguous %s %s tensor, got %s %s'
+                             % (name, n, h, w, shape, str(dtype).replace('torch.', ''), getattr(t, 'dtype', type(t)),
+                                tuple(getattr(t, 'shape', ()))))
+        if device is not None and t.device != torch.device(device):
+            raise ValueError('statistics.%s lives on %s, the frames on %s' % (name, t.device, device))
+    return spec
+
+
+def stats_planes(cfa):
+    """The names of the four planes of ``.zones`` and ``.hist`` for a sensor of phase ``cfa``, in plane order
+    2 * (y & 1) + (x & 1) of the frame as stored: 'r', 'gr' (green of the red rows), 'gb', 'b'."""
+    code = cfa_code(cfa)
+    return tuple(('r', 'gr', 'gb', 'b')[c ^ code] for c in range(4))
+
+
+def raw_stats(frames, st, black_level=0, bits=16, width=None):
+    """The 3A statistics of sensor frames in ONE launch behind the zeroing (``risp_raw_stats``): (N,H,W) or (H,W)
+    ``torch.uint16`` frames on the device (``bits=16``), or (N,H,stride) / (H,stride) ``torch.uint8`` MIPI-packed RAW10 / RAW12
+    (``bits`` 10 / 12, ``width`` as in ``raw_unpack``).  Fills ``st`` (a ``RawStatistics`` built for these N, H, W; N is 1 for a
+    single frame) from the samples max(s - black_level, 0) and returns it: per zone and plane the sum and the count of the
+    samples in lo .. hi and the focus measure sum |2 s(y,x) - s(y,x-2) - s(y,x+2)|, per image and plane the histogram
+    (include/risp.h has the definition to the bit).  Integers throughout: the result is exact and has no summation order.
+    H even, W % 4 == 0.  Nothing is allocated and the host does not wait."""
+    _need_gpu(frames, 'frames')
+    if bits == 16:
+        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
+        if width is not None and width != frames.shape[-1]:
+            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
+        (n, h, w), stride = ((1,) + tuple(frames.shape) if frames.dim() == 2 else tuple(frames.shape)), 2 * frames.shape[-1]
+    else:
+        n, h, w, stride = _packed_frames(frames[None] if frames.dim() == 2 else frames, bits, width, 'frames')
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    zh, zw, nb, shift, lo, hi = stats_check(st, n, h, w, frames.device)
+    L.call('risp_raw_stats', _p(frames), int(bits), stride, int(black_level), _p(st.zones), _p(st.hist), zh, zw, nb, shift, lo, hi,
+           n, h, w, _stream())
+    return st
+
+
 def serve_classical_shaded(raw_u16, shading, divisor, demosaic, ops, params, reverse_channels=False, matrix=None, out=None,
                            black_level=0, cfa='rggb'):
     """``serve_classical_u8`` / ``serve_classical_nv12`` with the lens-shading correction inside the load, still ONE launch
