@@ -1053,6 +1053,64 @@ int risp_bgr8_resize(const uint8_t *img, uint8_t *out, const int32_t *xstart, co
                      const int16_t *yweight, int ty, int tile_rows, int span, const int32_t *coef, int rgb_in, int N, int H, int W,
                      int OH, int OW, void *stream);
 
+/* A geometry-corrected output of the serving path (risp_warp.hip): the LDC / GDC / dewarp block of an ISP - lens-distortion
+ * correction, rotation and flips, keystone, the per-frame shift and rotation of electronic stabilisation.  Packed 8-bit images
+ * are resampled through a mesh of source coordinates; an integer function, fixed to the bit (tests/warp_reference.py restates
+ * all of it in numpy int64; functional.warp_mesh / warp_homography / warp_radial build meshes on the host).
+ *
+ * Source: img, packed 8-bit (N,H,W,3); every channel is treated alike, so the channel order does not matter.  Output (N,WH,WW,3).
+ *
+ * Mesh: (MH,MW,2) int32, contiguous, with cell_log2 = k, 2 <= k <= 8, cell = 1 << k.  Node (i,j) sits at output pixel
+ * (i << k, j << k); mesh[i][j][0] is the source y of that pixel, mesh[i][j][1] its source x, in Q8: 256 is one pixel, coordinate 0
+ * the centre of source pixel 0, signed, possibly outside the image.  MH == ((WH-1) >> k) + 2 and MW == ((WW-1) >> k) + 2
+ * exactly - the rule of the shading map: the node below and right of the last pixel exists, so no read is conditional.  One
+ * mesh serves every image of the call.
+ *
+ * Per-pixel coordinate: signed 64-bit arithmetic.  For output pixel (y,x): i = y >> k, fy = y & (cell-1), j = x >> k,
+ * fx = x & (cell-1); for component c with S = H for c = 0 and S = W for c = 1
+ *     top = (cell - fx) * M[i][j][c]   + fx * M[i][j+1][c]
+ *     bot = (cell - fx) * M[i+1][j][c] + fx * M[i+1][j+1][c]
+ *     u_c = ((cell - fy) * top + fy * bot + (1 << (2k-1))) >> 2k          >> the arithmetic shift (floor)
+ *     u_c = clamp(u_c, 0, (S-1) << 8)                                      the replicate border
+ * Every int32 mesh is a defined input; the sums stay below 2^48.  The clamp comes after the interpolation: a node outside the
+ * image - the extra node of a flip - enters unclamped.
+ *
+ * kernel 0, bilinear: y0 = uy >> 8, ty = uy & 255, y1 = min(y0+1, H-1), and x0, tx, x1 likewise with W; per channel
+ *     out = ((256-ty) * ((256-tx)*p[y0][x0] + tx*p[y0][x1]) + ty * ((256-tx)*p[y1][x0] + tx*p[y1][x1]) + 32768) >> 16
+ * exact, every sum below 2^24, no clamp needed.
+ *
+ * kernel 1, bicubic: Catmull-Rom (a = -1/2) with Q11 weights from integers only.  For the phase f in 0 .. 255
+ *     n0 = -f^3 + 512 f^2 - 65536 f      n1 = 3 f^3 - 1280 f^2 + 2^25
+ *     n2 = -3 f^3 + 1024 f^2 + 65536 f   n3 = f^3 - 256 f^2                (they sum to 2^25; each |n| < 2^31)
+ *     q_t = (n_t + 8192) >> 14,  then q[first index of the largest q] += 2048 - (q0+q1+q2+q3)
+ * so every row sums to 2048; row 0 is (0, 2048, 0, 0), row 128 (-128, 1152, 1152, -128).  Taps are rows y0-1 .. y0+2 and
+ * columns x0-1 .. x0+2, every index clamped into the image:
+ *     h_r = sum_c q[tx][c] * p[row r][col c];   v = sum_r q[ty][r] * h_r;   out = clamp((v + (1 << 21)) >> 22, 0, 255)
+ * with no intermediate rounding; |v| + 2^21 <= 1 370 357 760 + 2^21 < 2^31 (Q12 would overflow, Q11 does not).
+ *
+ * Consequences (tests/test_warp_reference_cpu.py): the identity mesh returns img; the mesh of (H-1-y, W-1-x) returns img flipped
+ * on both axes; the mesh of (x, y) with size (W,H) the transpose; an affine map's per-pixel coordinate lies within 1 Q8 unit of
+ * 256 times the exact value (1/2 from rounding the nodes, 1/2 from the final rounding).
+ *
+ * risp_bgr8_warp: one launch, no host synchronisation, capturable.  kernel 0 / 1 as above.  A workgroup owns
+ * RISP_WARP_TILE_W x RISP_WARP_TILE_H output pixels: it evaluates their coordinates, reduces them to the tile's source
+ * bounding box - taps and border clamp included - and, with stage = 1, loads that box into LDS with aligned dword loads and
+ * samples from there where the box fits RISP_WARP_LDS_BYTES (beside 5136 bytes of weights and output tile); a tile whose box
+ * does not fit - a strong reduction, a twisted cell, a meaningless mesh - samples global memory, decided per tile inside the
+ * launch.  stage = 0 makes every tile sample global memory; both forms are the same integer function.  The bicubic weights are
+ * computed in the kernel.  No alignment is asked of img or out - a packed row starts at any byte -, and no byte outside img,
+ * mesh or out is read or written whatever the mesh holds, the last partial dword of img included.  Rules (anything else is
+ * refused before the launch, the message names the value): no NULL pointer, 1 <= N <= 65535, H, W, WH, WW in 1 .. 2^23 (a Q8
+ * coordinate fits int32), 2 <= cell_log2 <= 8, MH and MW exactly as defined, kernel and stage in {0, 1}, out not overlapping
+ * img, at most 65535 row tiles, mesh 8-byte aligned.  Not covered: a fill colour outside the image, antialiasing of reductions
+ * beyond about 2:1 (resize behind the warp: out_size), chroma-aware warping, a per-image mesh, meshes that are not bilinear
+ * patches. */
+#define RISP_WARP_TILE_W 64
+#define RISP_WARP_TILE_H 16
+#define RISP_WARP_LDS_BYTES 65536
+int risp_bgr8_warp(const uint8_t *img, uint8_t *out, const int32_t *mesh, int cell_log2, int MH, int MW, int kernel, int stage,
+                   int N, int H, int W, int WH, int WW, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

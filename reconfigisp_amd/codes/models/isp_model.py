@@ -125,8 +125,8 @@ class IspModel(BaseModel):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
-              resample='triangle', raw_format='u16', statistics=None, raw_width=None, lens_shading=None, defect_correction=None,
-              fast_median=False, fast_denoise_scene=False):
+              resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, lens_shading=None,
+              defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
         describe the sensor; ``fast_scene=True`` opts gray-world / white-world / Reinhard pipelines in to the scene route,
         whose bytes agree with the float64 reference under its tie rule - white-world-only pipelines byte for byte;
@@ -147,24 +147,27 @@ class IspModel(BaseModel):
         ``out_size=(OH, OW)``, ``out_window=(y0, x0, h, w)`` and ``resample`` deliver a scaled, cropped image, the bytes of
         ``functional.bgr8_resize`` of the same call without them - NV12 from the resized codes;
         ``statistics=st`` (a ``functional.RawStatistics``) also fills ``st`` with the 3A statistics - zone sums, histograms, the
-        focus measure - of the samples the route demosaics, the image unchanged)."""
+        focus measure - of the samples the route demosaics, the image unchanged;
+        ``warp=(mesh, cell, (WH, WW), kernel)`` delivers a geometry-corrected image (N,WH,WW,3) through a mesh of Q8 source
+        coordinates - lens distortion, rotation, flips, keystone, stabilisation -, the bytes of ``functional.bgr8_warp`` of the
+        same call without it, in front of the resize and the NV12 conversion where those are asked for)."""
         with torch.no_grad():
             return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                         out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size, out_window=out_window,
-                                        resample=resample, raw_format=raw_format, statistics=statistics, raw_width=raw_width,
+                                        resample=resample, raw_format=raw_format, statistics=statistics, warp=warp, raw_width=raw_width,
                                         lens_shading=lens_shading, defect_correction=defect_correction, fast_median=fast_median,
                                         fast_denoise_scene=fast_denoise_scene)
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
-                    resample='triangle', raw_format='u16', statistics=None, raw_width=None, defect_correction=None,
+                    resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, defect_correction=None,
                     lens_shading=None):
         """(H,W) or (N,H,W) uint16 sensor frames on the device -> (H,W,3) or (N,H,W,3) uint8 through overlapped tiles (the
         pipeline's ``serve_frame``): the bytes ``test_split.py`` writes, without an fp32 frame at either end; ``black_level``
         and ``cfa`` describe the sensor; ``out_format='nv12'``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``,
-        ``raw_format``, ``statistics``, ``raw_width``, ``defect_correction`` and ``lens_shading`` as in ``serve``."""
+        ``raw_format``, ``statistics``, ``warp``, ``raw_width``, ``defect_correction`` and ``lens_shading`` as in ``serve``."""
         with torch.no_grad():
             return self.netG_attr.serve_frame(raw_u16, white_level, patch_size, patch_stride, tile_batch, reverse_channels, out,
                                               black_level, cfa, out_format, yuv_matrix, out_size=out_size, out_window=out_window,
-                                              resample=resample, raw_format=raw_format, statistics=statistics,
+                                              resample=resample, raw_format=raw_format, statistics=statistics, warp=warp,
                                               raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)

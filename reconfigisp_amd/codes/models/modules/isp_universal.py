@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, wants_grad
+from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, wants_grad, warp_plan
 
 
 class _FixedPipeline(nn.Module):
@@ -48,6 +48,7 @@ class _FixedPipeline(nn.Module):
         self.last_serve_resize = None           # with out_size / out_window: 'pass' (risp_bgr8_resize behind the route); None without the keywords
         self.last_serve_shade = None            # with lens_shading: 'fused' (the serving launch shaded in its load) | 'pass' (risp_raw_shade did, decoding packed frames too); None without the keyword
         self.last_serve_defect = None           # with defect_correction: 'fused' (one risp_raw_defect launch corrected and shaded) | 'pass' (risp_raw_defect corrected; risp_raw_shade follows where lens_shading is given); None without the keyword
+        self.last_serve_warp = None             # with warp: 'pass' (risp_bgr8_warp behind the route); None without the keyword
         self.last_serve_stats = None            # with statistics: 'pass' (risp_raw_stats filled the RawStatistics from what the route reads); None without the keyword
         self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
 
@@ -101,8 +102,8 @@ class _FixedPipeline(nn.Module):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
-              resample='triangle', raw_format='u16', statistics=None, raw_width=None, lens_shading=None, defect_correction=None,
-              fast_median=False, fast_denoise_scene=False):
+              resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, lens_shading=None,
+              defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -178,7 +179,7 @@ class _FixedPipeline(nn.Module):
         and one ``risp_bgr8_resize`` launch writes ``out``: ``last_serve_resize`` is 'pass', None without the keywords.  With
         ``out_format='nv12'`` (N,3*OH/2,OW), OH and OW even; ``last_serve_store`` is then 'resize' (that launch stored NV12,
         where ``pipeline_fusion.resize_store`` says 'fused') or 'pass' (``risp_bgr8_to_nv12`` followed it).  ``out_format``,
-        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``raw_width``,
+        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``warp``, ``raw_width``,
         ``lens_shading``, ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are keyword-only
         (``pipeline_fusion.serve``).
 
@@ -187,20 +188,36 @@ class _FixedPipeline(nn.Module):
         histograms; include/risp.h has the integer definition.  ``st`` is checked before anything is launched, then
         ``risp_raw_stats`` reads what the route is about to read: the pre-pass's frames with ``defect_correction`` and / or
         ``lens_shading`` (the shade launch then runs: ``last_serve_shade`` 'pass'), otherwise the input as given.  The image
-        bytes and the route are those of the call without the keyword.  ``last_serve_stats`` is 'pass', None without it."""
+        bytes and the route are those of the call without the keyword.  ``last_serve_stats`` is 'pass', None without it.
+
+        ``warp=(mesh, cell, (WH, WW), kernel)`` delivers a geometry-corrected image (N,WH,WW,3): lens distortion, rotation,
+        flips, keystone, stabilisation through an (MH,MW,2) int32 mesh of Q8 source coordinates with 'bilinear' or 'bicubic'
+        taps (``functional.warp_check``; ``functional.warp_mesh`` / ``warp_homography`` / ``warp_radial`` build meshes;
+        include/risp.h has the integer definition).  The route, chosen as without the keyword, serves packed BGR into a cached
+        image and one ``risp_bgr8_warp`` launch writes the warped image - into ``out``, or in front of the resize
+        (``out_size`` / ``out_window`` then apply to the warped image) and of the NV12 conversion (WH, WW even;
+        ``last_serve_store`` 'pass' or as under a resize): the bytes of ``functional.bgr8_warp`` of the same call without the
+        keyword.  Statistics are unchanged.  ``last_serve_warp`` is 'pass', None without it."""
         with torch.no_grad():
-            # (the resize keywords are refused before the stage parameters are made: that is a launch)
-            resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
+            # (the warp and resize keywords are refused before the stage parameters are made: that is a launch)
+            if warp_plan(raw_u16, raw_format, raw_width, (3,), warp, out_size, out_window, resample, out_format, yuv_matrix,
+                         reverse_channels, out) is None:
+                resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
             stats_plan(raw_u16, raw_format, raw_width, (3,), statistics)
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                                     out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size,
                                                     out_window=out_window, resample=resample, raw_format=raw_format,
-                                                    statistics=statistics, raw_width=raw_width, lens_shading=lens_shading,
+                                                    statistics=statistics, warp=warp, raw_width=raw_width, lens_shading=lens_shading,
                                                     defect_correction=defect_correction, fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
+            self.last_serve_warp = None
+            if warp is not None:
+                self.last_serve_warp = 'pass'
+                if out_format != 'bgr8':
+                    self.last_serve_store = 'pass'      # the route served BGR for the warp launch
             self.last_serve_resize = None
             if out_size is not None or out_window is not None:
                 self.last_serve_resize = 'pass'
@@ -228,7 +245,7 @@ class _FixedPipeline(nn.Module):
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
-                    resample='triangle', raw_format='u16', statistics=None, raw_width=None, defect_correction=None,
+                    resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, defect_correction=None,
                     lens_shading=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
@@ -245,12 +262,15 @@ class _FixedPipeline(nn.Module):
         that same launch.  ``out_size``, ``out_window`` and ``resample`` as in ``serve``: the frames are blended at the sensor's
         size into a cached image and one ``risp_bgr8_resize`` launch writes (OH,OW,3) or (N,OH,OW,3) - NV12 likewise -;
         ``last_serve_resize`` and ``last_serve_store`` as there.  ``statistics`` as in ``serve``: the 3A statistics of the whole
-        frames, (H,W) being one image, taken once in front of the tiles (``last_serve_stats`` 'pass')."""
+        frames, (H,W) being one image, taken once in front of the tiles (``last_serve_stats`` 'pass').  ``warp`` as in
+        ``serve``: the frames are blended at the sensor's size into a cached image and one ``risp_bgr8_warp`` launch behind the
+        last frame writes (WH,WW,3) or (N,WH,WW,3), in front of the resize and the NV12 conversion where those are asked for
+        (``last_serve_warp`` 'pass')."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
                               reverse_channels, out, black_level, cfa, out_format, yuv_matrix, out_size=out_size,
                               out_window=out_window, resample=resample, raw_format=raw_format, statistics=statistics,
-                              raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
+                              warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
             self.last_serve_route = 'tiled'
             self.last_serve_stats = None if statistics is None else 'pass'
             self.last_serve_load = serve_load('tiled', raw_format)
@@ -258,6 +278,7 @@ class _FixedPipeline(nn.Module):
             self.last_serve_defect = None if defect_correction is None else (
                 defect_shade(raw_format) if lens_shading is not None else 'pass')
             self.last_serve_store = None if out_format == 'bgr8' else 'pass'
+            self.last_serve_warp = None if warp is None else 'pass'
             self.last_serve_resize = None
             if out_size is not None or out_window is not None:
                 self.last_serve_resize = 'pass'

@@ -675,6 +675,73 @@ def _resized(img, plan, resample, out):
     return F.bgr8_to_nv12(bgr, coef, 'bgr', out)
 
 
+# warp kernels whose launch stages the source box of a tile in LDS (risp_bgr8_warp with stage = 1) instead of sampling global
+# memory from every tile (stage = 0).  A kernel is listed only if stage = 1 beats stage = 0 by more than the larger spread of the
+# two legs in every measured row of that kernel in profiles/serve_warp.txt (two sizes x identity, a 2-degree rotation and a radial
+# correction) - the rule of _FUSED_LOAD, _FUSED_SHADE, _DEFECT_SHADE_FUSED and _RESIZE_NV12_FUSED.  The verdict line
+# of that file is this table.  Measured: staging LOSES in all twelve rows - 3000 x 4000 bilinear 284-292 us against 58-68 us, bicubic
+# 336-344 against 180-215; 64 x 256 x 256 97-99 against 23-25 and 115-118 against 66-78, spreads under 8 us: a launch that asks for 64 KB
+# of LDS keeps two workgroups on a CU, and a tile's chain of loads, barriers, taps and stores has nothing to hide behind.  So the
+# table is empty and serve gathers.  Both forms are the same integer function and stay reachable through
+# functional.bgr8_warp(stage=).
+_WARP_STAGED = frozenset()
+
+
+def warp_stage(kernel):
+    """How the warp launch of ``serve`` / ``serve_frame`` (and ``functional.bgr8_warp`` with ``stage=None``) reads its source:
+    'lds' - a workgroup stages its tile's source box in LDS where it fits - or 'gather' - every tile samples global memory.  A
+    pure function of the kernel's name ('bilinear' | 'bicubic'); the bytes are the same either way."""
+    if kernel not in F.WARP_KERNELS:
+        raise ValueError('unknown warp kernel %r: one of %s' % (kernel, ', '.join(F.WARP_KERNELS)))
+    return 'lds' if kernel in _WARP_STAGED else 'gather'
+
+
+def _warp_bgr(shape, device):
+    """the packed sensor-size image a call with ``warp`` serves into, kept per (shape, device, stream); neither the resize's
+    nor the NV12 route's image: the launches behind the warp read those at the warp's size, which may be the sensor's"""
+    return F._scene_buffer(device, 'warp_bgr', shape, torch.uint8)
+
+
+def _warp_plan(warp, h, w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, lead, device):
+    """a call with ``warp``, checked on the host before anything is launched: (the checked warp, the resize plan of the warped
+    image or None, the twelve integers of an NV12 store without a resize or None); ``lead`` is the shape in front of the
+    image's own dimensions"""
+    wp = F.warp_check(warp, h, w, device, out_format == 'nv12')
+    wh, ww = wp[2]
+    if out_size is not None or out_window is not None:
+        return wp, _resize_plan(out_size, out_window, resample, wh, ww, out_format, yuv_matrix, reverse_channels, out, lead, device), None
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, wh, ww)
+    if out is not None:
+        F._u8_out(out, tuple(lead) + ((wh, ww, 3) if coef is None else (wh + wh // 2, ww)), device, 1)
+    return wp, None, coef
+
+
+def warp_plan(raw, raw_format, raw_width, dims, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out):
+    """``_warp_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keyword: what
+    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
+    if warp is None:
+        return None
+    if not isinstance(raw, torch.Tensor) or raw.dim() not in dims:
+        raise ValueError('expected %s frames, got %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
+                                                        tuple(getattr(raw, 'shape', ()))))
+    w = raw.shape[-1] if raw_format == 'u16' else _packed_plan(raw, raw_format, raw_width, dims)[1]
+    return _warp_plan(warp, raw.shape[-2], w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out,
+                      tuple(raw.shape[:-2]), raw.device)
+
+
+def _warped(img, plan, warp, resample, out):
+    """the end of a call with ``warp``: the served packed image -> ONE ``risp_bgr8_warp`` launch (``warp_stage`` picks its
+    form) into ``out``, into the resize's source image where ``out_size`` / ``out_window`` follow, or into the NV12
+    conversion's source image"""
+    wp, rplan, coef = plan
+    shape = tuple(img.shape[:-3]) + (wp[2][0], wp[2][1], 3)
+    if rplan is not None:
+        return _resized(F.bgr8_warp(img, warp, out=_resize_bgr(shape, img.device)), rplan, resample, out)
+    if coef is not None:
+        return F.bgr8_to_nv12(F.bgr8_warp(img, warp, out=_nv12_bgr(shape, img.device)), coef, 'bgr', out)
+    return F.bgr8_warp(img, warp, out=out)
+
+
 def stats_plan(raw, raw_format, raw_width, dims, statistics):
     """``F.stats_check`` of ``statistics`` from the frames as given - uint16 or packed, of ``dims`` dimensions, one image for an
     (H,W) frame -, nothing for None: what ``serve_frame`` and the modules' ``serve`` check before their first launch"""
@@ -696,7 +763,7 @@ def stats_plan(raw, raw_format, raw_width, dims, statistics):
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          out_size=None, out_window=None, resample='triangle', raw_format='u16', statistics=None, raw_width=None,
+          out_size=None, out_window=None, resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None,
           lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
@@ -825,7 +892,22 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     keyword and the image bytes are the same.  H even, W % 4 == 0.  With ``out`` given a warm call allocates nothing and never
     waits for the device; a captured call zeroes ``st`` on every replay.  None is today's call, launch for launch.
 
-    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
+    ``warp=(mesh, cell, (WH, WW), kernel)`` delivers a geometry-corrected image (N,WH,WW,3) - lens distortion, rotation, flips,
+    keystone, stabilisation: output pixel (y,x) is sampled at the Q8 source coordinate interpolated from the (MH,MW,2) int32
+    ``mesh`` of ``cell``-pixel cells, with 'bilinear' or 'bicubic' taps and a replicate border (``F.warp_check``;
+    ``F.warp_mesh`` / ``F.warp_homography`` / ``F.warp_radial`` build meshes; include/risp.h has the integer definition).  The
+    route is chosen exactly as without the keyword, and so is every ``fast_*``, load, shade, defect and statistics choice -
+    statistics describe the sensor frame and do not change; it serves packed BGR at the sensor's size (``reverse_channels``
+    honoured there) into an image of its own kept per shape, device and stream, and ONE ``risp_bgr8_warp`` launch
+    (``warp_stage(kernel)`` picks its form) writes the warped image into ``out``, into the resize's source image when
+    ``out_size`` / ``out_window`` are given - they and ``resample`` then mean what they mean above, applied to the warped image
+    of WH x WW -, or into the NV12 conversion's source image with ``out_format='nv12'`` (the routes that own a fused NV12 store
+    serve BGR too; WH and WW even, OH and OW too when resizing).  Byte for byte
+    ``nv12?(F.bgr8_resize?(F.bgr8_warp(serve(.. without warp, the resize keywords and out_format ..), warp), ..))``.  The warp
+    and ``out`` are checked before anything is launched; with ``out`` given a warm call allocates nothing and never waits.
+    None is today's call, launch for launch.
+
+    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``warp``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -860,6 +942,14 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     stats = statistics
     if stats is not None:
         F.stats_check(stats, n, h, w, raw_u16.device)       # refused before anything is launched
+    if warp is not None:
+        plan = _warp_plan(warp, h, w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, (n,),
+                          raw_u16.device)                   # refused before anything is launched
+        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
+                                   _warp_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
+                                   fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect,
+                                   stats=stats)
+        return _warped(img, plan, warp, resample, out), route
     if out_size is not None or out_window is not None:
         plan = _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, (n,),
                             raw_u16.device)                 # refused before anything is launched
@@ -1037,7 +1127,7 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
                 out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None,
-                out_window=None, resample='triangle', raw_format='u16', statistics=None, raw_width=None,
+                out_window=None, resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None,
                 defect_correction=None, lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
@@ -1072,12 +1162,19 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     with the 3A statistics of the whole frames the tiles are cut from: ``risp_raw_stats`` runs once, on the frames of the
     pre-pass where ``defect_correction`` or ``lens_shading`` is given (black level 0 behind a shading), otherwise on the input
     as given, packed or not, with ``black_level``.  ``st`` is checked before anything is launched; the image is unchanged.
+    ``warp=(mesh, cell, (WH, WW), kernel)`` (keyword-only, as in ``serve``) delivers a geometry-corrected image: every frame is
+    blended into a packed sensor-size image of the warp's own (``reverse_channels`` honoured there) and ONE ``risp_bgr8_warp``
+    launch behind the last frame writes (WH,WW,3) or (N,WH,WW,3) into ``out`` - or into the source image of the resize launch
+    (``out_size`` / ``out_window``, then applied to the warped image) or of the NV12 conversion that follows it.  Its refusals
+    come before anything is launched; statistics are unchanged.  None changes nothing.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
-    plan = resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample, out_format, yuv_matrix,
-                       reverse_channels, out)               # refused before anything is launched
+    wplan = warp_plan(raw_u16, raw_format, raw_width, (2, 3), warp, out_size, out_window, resample, out_format, yuv_matrix,
+                      reverse_channels, out)                # refused before anything is launched
+    plan = None if wplan is not None else resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample,
+                                                      out_format, yuv_matrix, reverse_channels, out)    # likewise
     if statistics is not None:                              # refused before anything is launched
         stats_plan(raw_u16, raw_format, raw_width, (2, 3), statistics)
         if black_level != int(black_level) or not 0 <= black_level < white_level:
@@ -1132,8 +1229,11 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     size, stride = _pair(patch_size), _pair(patch_stride)
     origins, sel = frame_geometry(H, W, size, stride, cfa, frames.device)
     count, tile_batch = origins.shape[0], int(tile_batch)
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W) if plan is None else None
-    if plan is not None:
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W) if plan is None and wplan is None else None
+    if wplan is not None:
+        # every frame is served at the sensor's size into the warp's cached image; the warp launch behind the loop reads it
+        final, out = out, _warp_bgr((H, W, 3) if single else (n, H, W, 3), frames.device)
+    elif plan is not None:
         # every frame is served at the sensor's size into the cached image; the resize launch behind the loop writes `out`
         final, out = out, _resize_bgr((H, W, 3) if single else (n, H, W, 3), frames.device)
     elif coef is None:
@@ -1159,6 +1259,8 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
             else:
                 F.tile_blend_u8(stack, origins, (H, W), stride, False, bgr, code)
                 F.bgr8_to_nv12(bgr, coef, 'bgr', out if single else out[k])
+    if wplan is not None:
+        return _warped(out, wplan, warp, resample, final)
     if plan is not None:
         return _resized(out, plan, resample, final)
     return out

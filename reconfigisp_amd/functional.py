@@ -990,6 +990,200 @@ def bgr8_resize(img_u8, out_size=None, out_window=None, resample='triangle', nv1
     return out
 
 
+# ---- a geometry-corrected output: the mesh warp (risp_warp.hip; include/risp.h has the definition to the bit)
+WARP_KERNELS = ('bilinear', 'bicubic')
+WARP_TILE_W = 64                        # RISP_WARP_TILE_W: output columns of a workgroup
+WARP_TILE_H = 16                        # RISP_WARP_TILE_H: output rows of a workgroup
+WARP_LDS_BYTES = 65536                  # RISP_WARP_LDS_BYTES: what a tile's staged source box may take, weights and tile included
+_WARP_CELLS = (4, 8, 16, 32, 64, 128, 256)
+_WARP_MAX = 1 << 23                     # sizes: a Q8 coordinate fits int32
+
+
+def warp_cubic_table():
+    """The Catmull-Rom weights of the 'bicubic' warp: (256,4) numpy int16, Q11, row f for the phase f / 256, from the integer
+    formula of include/risp.h - every row sums to exactly 2048.  The kernel computes the same rows itself; this serves the
+    reference's cross-check and the documents."""
+    import numpy as np
+    f = np.arange(256, dtype=np.int64)
+    n = np.stack([-f ** 3 + 512 * f ** 2 - 65536 * f, 3 * f ** 3 - 1280 * f ** 2 + (1 << 25),
+                  -3 * f ** 3 + 1024 * f ** 2 + 65536 * f, f ** 3 - 256 * f ** 2], axis=1)
+    q = (n + 8192) >> 14
+    q[np.arange(256), q.argmax(axis=1)] += 2048 - q.sum(axis=1)         # argmax: the first index of the largest
+    return q.astype(np.int16)
+
+
+def _warp_size(size, what='size'):
+    try:
+        wh, ww = (_small_int(v, 1, _WARP_MAX) for v in size)
+    except (TypeError, ValueError):
+        wh = ww = None
+    if wh is None or ww is None:
+        raise ValueError('warp %s %r: (WH, WW) as integers in 1 .. 2^23' % (what, size))
+    return wh, ww
+
+
+def _warp_cell(cell):
+    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in _WARP_CELLS:
+        raise ValueError('warp cell %r: a power of two from 4 to 256' % (cell,))
+    return cell.bit_length() - 1
+
+
+def warp_check(warp, H, W, device=None, nv12=False):
+    """A warp ``(mesh, cell, (WH, WW), kernel)`` for H x W images, checked on the host before anything is launched ->
+    (mesh, k, (WH, WW), kernel) with cell = 1 << k.  ``cell``: a power of two from 4 to 256; WH, WW: integers >= 1 (at most
+    2^23, as H and W; at most 65535 row tiles), even with ``nv12``; ``kernel``: a name of ``WARP_KERNELS``; ``mesh``: a
+    contiguous (MH,MW,2) ``torch.int32`` tensor, 8-byte aligned, MH == (WH-1) // cell + 2 and MW == (WW-1) // cell + 2 exactly,
+    on ``device`` when one is given - node (i,j) holds the Q8 source (y, x) of output pixel (i * cell, j * cell)
+    (include/risp.h has the definition).  Every int32 value is legal, so the mesh is never read here and the host never waits."""
+    try:
+        mesh, cell, size, kernel = warp
+    except (TypeError, ValueError):
+        raise ValueError('a warp is (mesh, cell, (WH, WW), kernel): an (MH,MW,2) int32 tensor, the cell size in pixels, the output '
+                         "size and 'bilinear' or 'bicubic'") from None
+    k = _warp_cell(cell)
+    wh, ww = _warp_size(size)
+    if _small_int(H, 1, _WARP_MAX) is None or _small_int(W, 1, _WARP_MAX) is None:
+        raise ValueError('warp of %r x %r images: H and W in 1 .. 2^23' % (H, W))
+    if (wh + WARP_TILE_H - 1) // WARP_TILE_H > 65535:
+        raise ValueError('warp size %r: %d output rows in tiles of %d are more than 65535 row tiles' % (size, wh, WARP_TILE_H))
+    if nv12 and (wh % 2 or ww % 2):
+        raise ValueError('a %d x %d warp output has no 4:2:0 form: WH and WW must be even' % (wh, ww))
+    if kernel not in WARP_KERNELS:
+        raise ValueError('unknown warp kernel %r: one of %s' % (kernel, ', '.join(WARP_KERNELS)))
+    if not isinstance(mesh, torch.Tensor) or mesh.dtype != torch.int32:
+        raise ValueError('a warp mesh must be an int32 tensor (Q8 coordinates), got %s' % (getattr(mesh, 'dtype', type(mesh)),))
+    mh, mw = ((wh - 1) >> k) + 2, ((ww - 1) >> k) + 2
+    if tuple(mesh.shape) != (mh, mw, 2) or not mesh.is_contiguous():
+        raise ValueError('the warp mesh of a %d x %d output with cell %d must be contiguous (%d,%d,2): (WH-1) // cell + 2 by '
+                         '(WW-1) // cell + 2 nodes of (y, x); got %s' % (wh, ww, cell, mh, mw, tuple(mesh.shape)))
+    if device is not None and mesh.device != device:
+        raise ValueError('the warp mesh lives on %s, the images on %s' % (mesh.device, device))
+    if mesh.data_ptr() % 8:
+        raise ValueError('the warp mesh must be 8-byte aligned')
+    return mesh, k, (wh, ww), kernel
+
+
+def bgr8_warp(img_u8, warp, out=None, stage=None):
+    """Packed 8-bit images through a mesh warp in ONE launch (``risp_bgr8_warp``): (N,H,W,3) or (H,W,3) ``torch.uint8`` on the
+    device -> (N,WH,WW,3) or (WH,WW,3), ``warp = (mesh, cell, (WH, WW), kernel)`` as ``warp_check`` takes it - the mesh on the
+    images' device; one mesh serves every image.  Output pixel (y,x) takes the source coordinate interpolated bilinearly from
+    the four nodes of its cell, clamped into the image (replicate border), and the 'bilinear' or 'bicubic' (Catmull-Rom, Q11)
+    taps there: an integer function, include/risp.h fixes every bit.  ``stage``: 'lds' / 1 - a workgroup stages the source box
+    of its tile in LDS where it fits - or 'gather' / 0 - every tile samples global memory -, the same bytes either way; None
+    takes what ``pipeline_fusion.warp_stage(kernel)`` says.  No alignment is asked of the images or of ``out``; ``out`` must not
+    share memory with the images.  With ``out`` given a call on contiguous images allocates nothing and the host never waits;
+    images that are not contiguous are copied first, which allocates."""
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
+        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
+                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
+    h, w = img_u8.shape[-3], img_u8.shape[-2]
+    mesh, k, (wh, ww), kernel = warp_check(warp, h, w, img_u8.device)
+    if stage is None:
+        from .codes.models.modules.pipeline_fusion import warp_stage
+        stage = warp_stage(kernel)
+    if isinstance(stage, bool) or stage not in (0, 1, 'gather', 'lds'):
+        raise ValueError("warp stage %r: 'lds' / 1, 'gather' / 0 or None" % (stage,))
+    _need_gpu(img_u8, 'img')
+    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
+    if n > 65535:
+        raise ValueError('%d images in one call: at most 65535' % n)
+    img_u8 = img_u8.contiguous()
+    out = _u8_out(out, tuple(img_u8.shape[:-3]) + (wh, ww, 3), img_u8.device, 1)
+    if (out.data_ptr() < img_u8.data_ptr() + img_u8.numel() and img_u8.data_ptr() < out.data_ptr() + out.numel()):
+        raise ValueError('out shares memory with the images: a tile reads pixels other tiles would have overwritten')
+    L.call('risp_bgr8_warp', _p(img_u8), _p(out), _p(mesh), k, mesh.shape[0], mesh.shape[1], WARP_KERNELS.index(kernel),
+           int(stage in (1, 'lds')), n, h, w, wh, ww, _stream())
+    return out
+
+
+def warp_mesh(fn, size, cell):
+    """Host builder of a warp mesh: ``fn(y, x) -> (sy, sx)`` gives the source pixel coordinates (floats; 0 is the centre of
+    source pixel 0) of output pixel coordinates, and is called ONCE on the node coordinates - float64 numpy arrays of shapes
+    (MH,1) and (1,MW) holding i * cell and j * cell, the row and column behind the last pixel included; what it returns is
+    broadcast to (MH,MW).  -> the (MH,MW,2) ``torch.int32`` mesh of ``size = (WH, WW)`` on the host (move it to the device once):
+    floor(v * 256 + 0.5), saturated to int32.  A value that is not a number is refused.  Where ``fn`` uses IEEE basic operations
+    only, every machine builds the same integers."""
+    import numpy as np
+    k = _warp_cell(cell)
+    wh, ww = _warp_size(size)
+    mh, mw = ((wh - 1) >> k) + 2, ((ww - 1) >> k) + 2
+    y = (np.arange(mh, dtype=np.float64) * cell)[:, None]
+    x = (np.arange(mw, dtype=np.float64) * cell)[None, :]
+    got = fn(y, x)
+    try:
+        sy, sx = got
+    except (TypeError, ValueError):
+        raise ValueError('warp_mesh: fn(y, x) must return (sy, sx), got %s' % (type(got).__name__,)) from None
+    nodes = np.empty((mh, mw, 2), dtype=np.float64)
+    try:
+        nodes[..., 0] = np.asarray(sy, dtype=np.float64)
+        nodes[..., 1] = np.asarray(sx, dtype=np.float64)
+    except ValueError:
+        raise ValueError('warp_mesh: fn returned shapes %s and %s, which do not broadcast to the (%d,%d) nodes'
+                         % (np.shape(sy), np.shape(sx), mh, mw)) from None
+    if np.isnan(nodes).any():
+        raise ValueError('warp_mesh: fn returned values that are not numbers at %d nodes' % int(np.isnan(nodes).sum()))
+    q = np.floor(nodes * 256.0 + 0.5)
+    q = np.minimum(np.maximum(q, -2147483648.0), 2147483647.0)
+    return torch.from_numpy(q.astype(np.int64).astype(np.int32))
+
+
+def warp_homography(matrix3x3, size, cell):
+    """Host builder: the mesh of a projective map.  ``matrix3x3`` takes an OUTPUT pixel to its SOURCE pixel,
+    (sx * d, sy * d, d) = M (x, y, 1) - x first, as OpenCV's ``warpPerspective`` with WARP_INVERSE_MAP.  Identity, flips,
+    90-degree turns, rotation, zoom, shift (affine maps: exact to within 1 Q8 unit per pixel) and keystone (interpolated
+    bilinearly inside a cell: take smaller cells for a stronger one).  A node whose denominator d is not positive is refused.
+    -> (MH,MW,2) ``torch.int32`` on the host, as ``warp_mesh``."""
+    import numpy as np
+    try:
+        m = np.asarray(matrix3x3.detach().cpu().numpy() if isinstance(matrix3x3, torch.Tensor) else matrix3x3, dtype=np.float64)
+    except (TypeError, ValueError):
+        m = np.zeros(0)
+    if m.shape != (3, 3) or not np.isfinite(m).all():
+        raise ValueError('warp_homography: a finite 3 x 3 matrix, got %r' % (matrix3x3,))
+
+    def fn(y, x):
+        d = m[2, 0] * x + m[2, 1] * y + m[2, 2]
+        if not (d > 0.0).all():
+            raise ValueError('warp_homography: the denominator is %g at node %s: it must be positive at every node'
+                             % (d.min(), tuple(int(v) for v in np.unravel_index(d.argmin(), d.shape))))
+        return (m[1, 0] * x + m[1, 1] * y + m[1, 2]) / d, (m[0, 0] * x + m[0, 1] * y + m[0, 2]) / d
+    return warp_mesh(fn, size, cell)
+
+
+def warp_radial_source(H, W, size, k1, k2=0.0, centre=None, zoom=1.0):
+    """``fn(y, x) -> (sy, sx)`` of ``warp_radial``: the Brown radial model on float64 arrays of output pixel coordinates."""
+    wh, ww = _warp_size(size)
+    if _small_int(H, 1, _WARP_MAX) is None or _small_int(W, 1, _WARP_MAX) is None:
+        raise ValueError('warp_radial of %r x %r images: H and W in 1 .. 2^23' % (H, W))
+    k1, k2, zoom = float(k1), float(k2), float(zoom)
+    if not (k1 == k1 and k2 == k2 and zoom > 0.0 and abs(k1) < float('inf') and abs(k2) < float('inf') and zoom < float('inf')):
+        raise ValueError('warp_radial: finite k1, k2 and a finite zoom > 0, got %r, %r, %r' % (k1, k2, zoom))
+    try:
+        cy, cx = ((H - 1) / 2.0, (W - 1) / 2.0) if centre is None else (float(centre[0]), float(centre[1]))
+    except (TypeError, ValueError, IndexError):
+        raise ValueError('warp_radial: centre %r: (cy, cx) in source pixels' % (centre,)) from None
+    quarter = (float(H) * H + float(W) * W) / 4.0          # the square of half the source diagonal
+
+    def fn(y, x):
+        # the output frame mapped onto the source frame, pixel centres on pixel centres of the scaled grid
+        dy, dx = (y + 0.5) * (H / wh) - 0.5 - cy, (x + 0.5) * (W / ww) - 0.5 - cx
+        r2 = (dy * dy + dx * dx) / quarter
+        s = zoom * (1.0 + k1 * r2 + k2 * (r2 * r2))
+        return cy + dy * s, cx + dx * s
+    return fn
+
+
+def warp_radial(H, W, size, cell, k1, k2=0.0, centre=None, zoom=1.0):
+    """Host builder: the mesh that corrects a radial lens distortion of H x W images (the Brown model, as DNG's
+    ``WarpRectilinear`` without its tangential terms): source = centre + (p - centre) * zoom * (1 + k1 r^2 + k2 r^4), p the
+    output pixel mapped onto the source frame ((y + 0.5) * H / WH - 0.5), r = |p - centre| over half the source diagonal,
+    ``centre`` (cy, cx) in source pixels (default: the middle).  k1 < 0 corrects a pincushion, k1 > 0 a barrel distortion;
+    ``zoom`` < 1 magnifies.  Only + - * / on float64 enter.  The model is interpolated bilinearly inside a cell: the error falls
+    with the square of the cell (DESIGN.md 4.6 has figures).  -> (MH,MW,2) ``torch.int32`` on the host, as ``warp_mesh``."""
+    return warp_mesh(warp_radial_source(H, W, size, k1, k2, centre, zoom), size, cell)
+
+
 def serve_nv12(raw_u16, divisor, ops, params, bilateral=None, matrix='bt601_full', out=None, black_level=0, cfa='rggb'):
     """``serve_u8`` with the NV12 store (``risp_serve_nv12``, ONE launch): the same arguments with ``matrix``
     (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte
