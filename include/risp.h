@@ -76,6 +76,7 @@ int risp_wb_quadratic_bwd(const float *x, const float *p, const float *gy, float
 /* Per-image per-channel statistics of an (N,C,H,W) tensor (NC = N*C planes):
  * stats[plane*4+{0,1,2}] = {min, sum, max}; arg[plane*2+{0,1}] = first (row-major) index of
  * the min / max (may be NULL).  Used by SRCNNRes (srcnn_res_arch.py:36-40) and gray-world.
+ * Any HW > 0: planes of HW % 4 == 0 pixels through 16-byte loads, others through element loads.
  * scratch: risp_channel_stats_scratch_floats(NC,HW) floats.  Deterministic (no atomics). */
 size_t risp_channel_stats_scratch_floats(int NC, int HW);
 int risp_channel_stats(const float *x, float *stats, int32_t *arg, float *scratch, int NC, int HW,
@@ -432,6 +433,10 @@ int risp_group_sum(const float *stack, float *out, int G, int N, int C, int HW, 
  * (N,cout,H,W).  scratch: scratch_floats >= risp_conv_wgrad_scratch_floats(cin, cout, ksize) floats, checked (per-workgroup partial sums:
  * 768 slices of the pixel tiles, dealt over the 32 x 32 blocks of (cout, cin), k * k slots each - k for the thin layers whose filter column
  * is packed into the matrix -, added in index order by a finishing launch - no atomics, the same bits on every run).
+ * Limits: cin and cout 1 .. 64 and ksize 1, 3, 5 or 9, but ksize 9 only with cin <= 31 - the tiles of 32 input channels and more
+ * (32 x 129 + 32 x 385 floats = 65 792 bytes) are past the 64 KiB of LDS a workgroup may ask for, whatever cout ("tile too large
+ * for LDS").  The bias gradient is not part of this entry: convnets.conv_wgrad takes it from risp_plane_sums, which holds
+ * N * cout <= 65535.  Refusals return before any launch and write nothing (tests/test_gpu_wgrad_space.py).
  * Only the proxy fine-tuning path (darts_ft_model.py:206-246) needs weight gradients. */
 size_t risp_conv_wgrad_scratch_floats(int cin, int cout, int ksize);
 int risp_conv2d_wgrad(const risp_conv_desc *d, const float *gy, float *dw, float *scratch, size_t scratch_floats, void *stream);

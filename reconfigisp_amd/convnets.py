@@ -759,7 +759,9 @@ def conv_wgrad(x, gy, cin, cout, k, n, h, w, load=LOAD_PLAIN, cin_img=0, cvals=N
     partial sums added in index order - the same bits on every run).  ``load`` LOAD_CONSTCH (SRCNNRes' first layer, srcnn_res_arch.py:
     41-46: ``cin_img`` image channels followed by planes that hold the per-image constants ``cvals``): the gradient of a constant plane's
     taps is cvals^T @ (rectangle sums of gy) - risp_rect_sums, the sums its backward-data pass needs anyway - and only the image channels
-    go through the matrix kernel (cin_img * k <= 32: one chain per filter ROW with (channel, column) pairs as the matrix columns)."""
+    go through the matrix kernel (cin_img * k <= 32: one chain per filter ROW with (channel, column) pairs as the matrix columns).
+    Limits (refused on the host, include/risp.h): cin, cout <= 64, k in 1 / 3 / 5 / 9, a 9x9 layer only with cin <= 31 (the tiles of 32
+    channels and more do not fit the LDS), and n * cout <= 65535 for the bias sums (risp_plane_sums)."""
     gy = _dev(gy, 'grad')
     if load == LOAD_CONSTCH and cin_img * k <= 32 and cvals is not None and h >= k // 2 and k // 2 <= w <= 8192:   # (risp_rect_sums: W <= 8192)
         dw_img, db = conv_wgrad(x, gy, cin_img, cout, k, n, h, w)

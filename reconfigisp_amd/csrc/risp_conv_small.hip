@@ -319,10 +319,12 @@ __global__ __launch_bounds__(256) void rect_sums_kernel(const float *__restrict_
         float t = 0.f, edge[2 * (RK_MAX / 2)];             // edge[k-1]: sum of the first k columns, edge[P+k-1]: last k
 #pragma unroll
         for (int k = 0; k < 2 * (RK_MAX / 2); ++k) edge[k] = 0.f;
+        const bool none = dy <= -H || dy >= H;             // H == P: every row dropped - exactly 0, not the rounding left of col - rows
         for (int x = lane; x < W; x += 64) {
             float v = col[x];
             for (int k = 0; k < -dy; ++k) v -= gp[(size_t)k * W + x];
             for (int k = 0; k < dy; ++k) v -= gp[(size_t)(H - 1 - k) * W + x];
+            if (none) v = 0.f;
             t += v;
             for (int k = 1; k <= P; ++k) {
                 if (x < k) edge[k - 1] += v;

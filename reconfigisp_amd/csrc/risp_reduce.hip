@@ -33,11 +33,27 @@ __device__ __forceinline__ void mm_wave(MinMax &a) {
     }
 }
 
-// partial record: 5 words {min, max, sum, argmin, argmax}
-__global__ __launch_bounds__(256) void stats_partial_kernel(const float *__restrict__ x, float *__restrict__ part,
-                                                            int hw4, int nblk) {
+// partial record: 5 words {min, max, sum, argmin, argmax}.  The lanes of a wave by shuffles, the four waves of the workgroup through LDS
+__device__ __forceinline__ void stats_record(MinMax a, float *__restrict__ o) {
     __shared__ float s_f[3][4];
     __shared__ int s_i[2][4];
+    mm_wave(a);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_f[0][wave] = a.mn; s_f[1][wave] = a.mx; s_f[2][wave] = a.sum;
+        s_i[0][wave] = a.imn; s_i[1][wave] = a.imx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        MinMax t = {s_f[0][0], s_f[1][0], s_f[2][0], s_i[0][0], s_i[1][0]};
+        for (int w = 1; w < 4; ++w) mm_merge(t, s_f[0][w], s_i[0][w], s_f[1][w], s_i[1][w], s_f[2][w]);
+        o[0] = t.mn; o[1] = t.mx; o[2] = t.sum;
+        o[3] = __int_as_float(t.imn); o[4] = __int_as_float(t.imx);
+    }
+}
+
+__global__ __launch_bounds__(256) void stats_partial_kernel(const float *__restrict__ x, float *__restrict__ part,
+                                                            int hw4, int nblk) {
     const int plane = blockIdx.y;
     const float4 *xb = reinterpret_cast<const float4 *>(x) + (size_t)plane * hw4;
     MinMax a = {INFINITY, -INFINITY, 0.f, 0x7fffffff, 0x7fffffff};
@@ -57,20 +73,21 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float *__restr
         take4(v0, i); take4(v1, i + step); take4(v2, i + 2 * step); take4(v3, i + 3 * step);
     }
     for (; i < hw4; i += step) take4(xb[i], i);
-    mm_wave(a);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_f[0][wave] = a.mn; s_f[1][wave] = a.mx; s_f[2][wave] = a.sum;
-        s_i[0][wave] = a.imn; s_i[1][wave] = a.imx;
+    stats_record(a, part + ((size_t)plane * nblk + blockIdx.x) * 5);
+}
+
+// the same record from element loads: planes whose size is no multiple of 4 do not start on 16-byte boundaries (a 9 x 17 image)
+__global__ __launch_bounds__(256) void stats_partial_scalar_kernel(const float *__restrict__ x, float *__restrict__ part,
+                                                                   int hw, int nblk) {
+    const int plane = blockIdx.y;
+    const float *xb = x + (size_t)plane * hw;
+    MinMax a = {INFINITY, -INFINITY, 0.f, 0x7fffffff, 0x7fffffff};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
+        const float v = xb[i];
+        mm_take(a, v, i);
+        a.sum += v;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        MinMax t = {s_f[0][0], s_f[1][0], s_f[2][0], s_i[0][0], s_i[1][0]};
-        for (int w = 1; w < 4; ++w) mm_merge(t, s_f[0][w], s_i[0][w], s_f[1][w], s_i[1][w], s_f[2][w]);
-        float *o = part + ((size_t)plane * nblk + blockIdx.x) * 5;
-        o[0] = t.mn; o[1] = t.mx; o[2] = t.sum;
-        o[3] = __int_as_float(t.imn); o[4] = __int_as_float(t.imx);
-    }
+    stats_record(a, part + ((size_t)plane * nblk + blockIdx.x) * 5);
 }
 
 __global__ __launch_bounds__(64) void stats_final_kernel(const float *__restrict__ part, float *__restrict__ stats,
@@ -351,10 +368,13 @@ extern "C" {
 size_t risp_channel_stats_scratch_floats(int NC, int HW) { return (size_t)NC * stat_blocks(HW) * 5; }
 
 int risp_channel_stats(const float *x, float *stats, int32_t *arg, float *scratch, int NC, int HW, void *stream) {
-    RISP_CHECK_ARG(x && stats && scratch && NC > 0 && NC <= 65535 && HW > 0 && HW % 4 == 0,
+    RISP_CHECK_ARG(x && stats && scratch && NC > 0 && NC <= 65535 && HW > 0,
                    "risp_channel_stats: bad arguments (NC=%d HW=%d)", NC, HW);
     const int nb = stat_blocks(HW);
-    hipLaunchKernelGGL(stats_partial_kernel, dim3(nb, NC), dim3(256), 0, (hipStream_t)stream, x, scratch, HW / 4, nb);
+    if (HW % 4 == 0)
+        hipLaunchKernelGGL(stats_partial_kernel, dim3(nb, NC), dim3(256), 0, (hipStream_t)stream, x, scratch, HW / 4, nb);
+    else
+        hipLaunchKernelGGL(stats_partial_scalar_kernel, dim3(nb, NC), dim3(256), 0, (hipStream_t)stream, x, scratch, HW, nb);
     hipLaunchKernelGGL(stats_final_kernel, dim3(NC), dim3(64), 0, (hipStream_t)stream, scratch, stats, arg, nb);
     RISP_LAUNCH_CHECK("risp_channel_stats");
     return 0;

@@ -156,6 +156,26 @@ def test_channel_stats_first_occurrence(F):
     assert arg[0, 0, 0].item() == 3 * 24 + 5 and arg[1, 2, 1].item() == 0
 
 
+@pytest.mark.parametrize('hw', [(9, 17), (1, 1), (3, 2), (97, 131)])
+def test_channel_stats_of_planes_that_are_no_multiple_of_4(F, hw):
+    """H W % 4 != 0 (planes that do not start on 16-byte boundaries): the element-load form - the same statistics, ties to the first index;
+    97 x 131 pixels are more than one workgroup pass"""
+    h, w = hw
+    x = rnd(2, 3, h, w, seed=17)
+    if h * w > 8:
+        x[0, 0, h // 3, w // 2] = x[0, 0, h - 1, 1] = -1.0
+        x[1, 2, 0, 0] = x[1, 2, h - 1, w - 1] = 2.0
+    stats, arg = F.channel_stats(x.cuda())
+    flat = x.view(2, 3, -1)
+    assert torch.equal(stats[..., 0].cpu(), flat.min(dim=2)[0])
+    assert torch.equal(stats[..., 2].cpu(), flat.max(dim=2)[0])
+    assert_close(stats[..., 1], flat.double().sum(dim=2), rtol=1e-5)
+    if h * w > 8:
+        assert arg[0, 0, 0].item() == (h // 3) * w + w // 2 and arg[1, 2, 1].item() == 0
+    else:                                                     # no ties
+        assert torch.equal(arg[..., 0].cpu().long(), flat.argmin(dim=2)) and torch.equal(arg[..., 1].cpu().long(), flat.argmax(dim=2))
+
+
 def test_mix_fwd_bwd(F):
     outs = [rnd(2, 3, 8, 8, seed=20 + k) for k in range(5)]
     w = torch.tensor([0.1, 0.0, 0.4, 0.3, 0.2])
