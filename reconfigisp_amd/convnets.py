@@ -16,7 +16,7 @@ import os
 import torch
 
 from . import lib as L
-from .functional import _dev, _p, _stream, channel_stats
+from .functional import _dev, _need_gpu, _p, _stream, channel_stats
 
 LOAD_PLAIN, LOAD_UNSHUFFLE2, LOAD_CONSTCH = 0, 1, 2
 EPI_RELU, EPI_ADD, EPI_MASK, EPI_SHUFFLE2, EPI_NOBIAS, EPI_CASEBIAS = 1, 2, 4, 8, 16, 32
@@ -677,8 +677,14 @@ def conv(x, pc, n, h, w, transpose=False, load=LOAD_PLAIN, cin_img=0, cvals=None
     """One fused convolution launch at resolution (h,w); returns the output tensor.  ``infer``: no backward pass will read this
     layer's activations (an inference launch: its result must not depend on the batch a tile travels in).  ``group`` = (G, flags):
     ``pc`` holds the packs of G same-geometry layers stacked along dimension 0 and the launch covers G * n images
-    (``_group_fields``).  The kernel is chosen by ``route``."""
+    (``_group_fields``).  The kernel is chosen by ``route``.  ``add`` and EPI_ADD go together: a residual handed over without the flag
+    is refused (the route would be chosen for a residual that no kernel then adds)."""
     cin, cout = (pc.cout, pc.cin) if transpose else (pc.cin, pc.cout)
+    for t, what in ((x, 'x'), (cvals, 'cvals'), (add, 'add'), (mask, 'mask'), (out, 'out')):
+        if t is not None:
+            _need_gpu(t, what)
+    if add is not None and not (epi & EPI_ADD):
+        raise ValueError('conv: add= without EPI_ADD in the epilogue (%d)' % epi)
     if transpose:
         epi |= EPI_NOBIAS
     if group is not None and pc.k == 3:
@@ -690,11 +696,7 @@ def conv(x, pc, n, h, w, transpose=False, load=LOAD_PLAIN, cin_img=0, cvals=None
     aligned = (x.data_ptr() | out.data_ptr() | (add.data_ptr() if add is not None else 0) |
                (mask.data_ptr() if mask is not None else 0)) % 16 == 0
     have = _have(pc, transpose)
-    if add is not None:
-        epi_r = epi | EPI_ADD
-    else:
-        epi_r = epi
-    entry = route(pc.k, cin, cout, h, w, transpose, load, epi_r, add_c, infer, aligned, have)
+    entry = route(pc.k, cin, cout, h, w, transpose, load, epi, add_c, infer, aligned, have)
     if entry == 'risp_conv2d_toep_first_exact' and nn_ * cout * h * w >= (1 << 32):
         entry = 'risp_conv2d_toep_first'
     sfx = '_bwd' if transpose else '_fwd'

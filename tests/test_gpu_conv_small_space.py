@@ -25,28 +25,11 @@ import torch
 import conv_small_reference as R
 from conftest import assert_close
 from conv_small_reference import ADD, NOBIAS, SHUFFLE2, NARROW3, SMALL, SPLIT, TAPOUT, TOEP
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
-NAN, GUARD, BAND = float('nan'), 12345.0, 64
 REPORT = os.environ.get('RISP_BUDGET_REPORT') == '1'
-
-
-class Guarded:
-    """a device buffer between two bands of BAND sentinel floats (256 bytes: the view stays 16-byte aligned), NaN inside"""
-
-    def __init__(self, *shape):
-        numel = int(np.prod(shape))
-        self.raw = torch.full((numel + 2 * BAND,), GUARD, device='cuda')
-        self.t = self.raw[BAND: BAND + numel].view(*shape)
-        self.t.fill_(NAN)
-        assert self.t.data_ptr() % 16 == 0
-
-    def bands_intact(self):
-        return (self.raw[:BAND] == GUARD).all().item() and (self.raw[-BAND:] == GUARD).all().item()
-
-    def untouched(self):
-        return self.bands_intact() and torch.isnan(self.t).all().item()
 
 
 @pytest.fixture
