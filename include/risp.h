@@ -981,6 +981,40 @@ int risp_serve_classical_shaded(const uint16_t *raw, float divisor, int demosaic
 int risp_raw_defect(const void *raw, int bits, int stride, uint16_t *out, int threshold, int slope, const uint32_t *defects,
                     const uint16_t *gains, int cell_log2, int GH, int GW, int black_level, int N, int H, int W, void *stream);
 
+/* Temporal noise reduction (TNR / 3DNR) into the serving path (risp_temporal.hip, risp_temporal.h): the recursive raw-domain filter
+ * of a video ISP, behind defect correction and lens shading and in front of the demosaic.  The one serving block with state across
+ * calls.  An integer function of the current frame and the state, fixed to the bit (tests/temporal_reference.py restates it in
+ * numpy int64).
+ * c is the current frame and p the state - the previous filtered frame -, both (H,W) uint16 in the sample domain the route
+ * demosaics: raw codes with pedestal black_level, or shaded samples with black level 0 behind a shading.  The window is the full
+ * 5 x 5 around (y,x), all colours - symmetric, so cfa does not enter.  An index outside the frame reflects without repeating the
+ * edge (-1 -> 1, -2 -> 2, H -> H-2, H+1 -> H-3), as in the defect correction.  H >= 3, W >= 4, W % 4 == 0.
+ *     A  = sum over the window of (c - p)                      signed, |A| <= 25 * 65535
+ *     B  = sum over the window of p
+ *     Bs = max(B - 25 * black_level, 0)
+ *     lo = 25 * threshold + ((Bs * slope) >> 8)
+ *     e  = min(max(|A| - lo, 0), 65535)
+ *     k  = min(strength + ((e * ramp) >> 8), 256)
+ *     out(y,x) = (p(y,x) * (256 - k) + c(y,x) * k + 128) >> 8
+ * strength: 0 .. 256, Q8, the share of the new frame where nothing moves - 256 is the identity, 0 freezes; threshold: 0 .. 65535,
+ * in codes of mean difference; slope: 0 .. 255, Q8, the part of the threshold that grows with the signal; ramp: 0 .. 65535, Q8 per
+ * code of summed excess.  Every intermediate fits unsigned 32 bits: Bs * slope < 4.2e8, e * ramp <= 65535^2, and the blend stays
+ * below 2^24 + 128.  With k == 256, out == c exactly.  The new state is out.  Neighbours are always the previous state's and the
+ * current frame's: a launch never reads a state value that it wrote itself.
+ *
+ * risp_raw_temporal: cur, state, out (N,H,W) uint16 contiguous.  ONE launch reads cur and state and writes out (6 bytes per pixel),
+ * then ONE device-to-device copy of out into state follows on the same stream (4 more): the state cannot be written in place -
+ * other workgroups still read its halo - and two buffers alternated by the host would bake one direction into a captured graph.
+ * prime != 0: state is not read, out = cur, and the copy makes state = cur (two copies, no launch).  cur and state 2-byte aligned
+ * (wider loads when both are 8-byte aligned), out 8-byte aligned.  out may overlap neither cur nor state.  Rules (anything else
+ * is refused before anything is issued, the message names the value): no NULL, N >= 1, H >= 3, W >= 4 and W % 4 == 0,
+ * strength 0 .. 256, threshold 0 .. 65535, slope 0 .. 255, ramp 0 .. 65535, black_level 0 .. 65535, the alignments, no overlap of
+ * out.  Not covered: motion compensation, a per-plane or per-gain noise model, the filter fused into the defect or shade launch or
+ * into a route's own launch, a state updated without the copy, a separate luma / chroma strength, a fix for the recursion stalling
+ * at strength < 128 from rounding ((p * (256 - k) + c * k + 128) >> 8 == p once |c - p| * k < 128). */
+int risp_raw_temporal(const uint16_t *cur, uint16_t *state, uint16_t *out, int prime, int strength, int threshold, int slope,
+                      int ramp, int black_level, int N, int H, int W, void *stream);
+
 /* 3A statistics of the sensor frame (risp_stats.hip): the statistics block of a hardware ISP - per-zone colour sums for
  * auto-white-balance, histograms for auto-exposure, a focus measure for autofocus -, taken on the linear samples the route
  * demosaics.  Counts and sums of integers, fixed to the bit and without a summation order (tests/stats_reference.py restates

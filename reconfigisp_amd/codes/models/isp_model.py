@@ -125,8 +125,8 @@ class IspModel(BaseModel):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
-              resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, lens_shading=None,
-              defect_correction=None, fast_median=False, fast_denoise_scene=False):
+              resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
+              lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
         describe the sensor; ``fast_scene=True`` opts gray-world / white-world / Reinhard pipelines in to the scene route,
         whose bytes agree with the float64 reference under its tie rule - white-world-only pipelines byte for byte;
@@ -144,6 +144,9 @@ class IspModel(BaseModel):
         returns the bytes of the same call on ``functional.raw_shade`` of the frames;
         ``defect_correction=(threshold, slope, defects)`` replaces hot, dead and listed pixels from their same-colour neighbours
         in front of that and returns the bytes of the same call on ``functional.raw_defect`` of the frames;
+        ``temporal_denoise=(state, strength, threshold, slope, ramp)`` blends the frames over ``state.frames`` (a
+        ``functional.TemporalState``), the previous filtered frames, behind those two and in front of everything else, returns the
+        bytes of the same call on ``functional.raw_temporal`` of the frames and advances the state;
         ``out_size=(OH, OW)``, ``out_window=(y0, x0, h, w)`` and ``resample`` deliver a scaled, cropped image, the bytes of
         ``functional.bgr8_resize`` of the same call without them - NV12 from the resized codes;
         ``statistics=st`` (a ``functional.RawStatistics``) also fills ``st`` with the 3A statistics - zone sums, histograms, the
@@ -154,20 +157,21 @@ class IspModel(BaseModel):
         with torch.no_grad():
             return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                         out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size, out_window=out_window,
-                                        resample=resample, raw_format=raw_format, statistics=statistics, warp=warp, raw_width=raw_width,
+                                        resample=resample, raw_format=raw_format, temporal_denoise=temporal_denoise, statistics=statistics,
+                                        warp=warp, raw_width=raw_width,
                                         lens_shading=lens_shading, defect_correction=defect_correction, fast_median=fast_median,
                                         fast_denoise_scene=fast_denoise_scene)
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
-                    resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, defect_correction=None,
-                    lens_shading=None):
+                    resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
+                    defect_correction=None, lens_shading=None):
         """(H,W) or (N,H,W) uint16 sensor frames on the device -> (H,W,3) or (N,H,W,3) uint8 through overlapped tiles (the
         pipeline's ``serve_frame``): the bytes ``test_split.py`` writes, without an fp32 frame at either end; ``black_level``
         and ``cfa`` describe the sensor; ``out_format='nv12'``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``,
-        ``raw_format``, ``statistics``, ``warp``, ``raw_width``, ``defect_correction`` and ``lens_shading`` as in ``serve``."""
+        ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``defect_correction`` and ``lens_shading`` as in ``serve``."""
         with torch.no_grad():
             return self.netG_attr.serve_frame(raw_u16, white_level, patch_size, patch_stride, tile_batch, reverse_channels, out,
                                               black_level, cfa, out_format, yuv_matrix, out_size=out_size, out_window=out_window,
-                                              resample=resample, raw_format=raw_format, statistics=statistics, warp=warp,
-                                              raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
+                                              resample=resample, raw_format=raw_format, temporal_denoise=temporal_denoise,
+                                              statistics=statistics, warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, wants_grad, warp_plan
+from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, temporal_plan, wants_grad, warp_plan
 
 
 class _FixedPipeline(nn.Module):
@@ -49,6 +49,7 @@ class _FixedPipeline(nn.Module):
         self.last_serve_shade = None            # with lens_shading: 'fused' (the serving launch shaded in its load) | 'pass' (risp_raw_shade did, decoding packed frames too); None without the keyword
         self.last_serve_defect = None           # with defect_correction: 'fused' (one risp_raw_defect launch corrected and shaded) | 'pass' (risp_raw_defect corrected; risp_raw_shade follows where lens_shading is given); None without the keyword
         self.last_serve_warp = None             # with warp: 'pass' (risp_bgr8_warp behind the route); None without the keyword
+        self.last_serve_temporal = None         # with temporal_denoise: 'pass' (risp_raw_temporal filtered the frames in front of the route and advanced the state); None without the keyword
         self.last_serve_stats = None            # with statistics: 'pass' (risp_raw_stats filled the RawStatistics from what the route reads); None without the keyword
         self.last_serve_load = None             # with raw_format='raw10' / 'raw12': 'fused' (the serving launch decoded the packed bytes) | 'pass' (the unpack launch did); None for 'u16'
 
@@ -102,8 +103,8 @@ class _FixedPipeline(nn.Module):
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
               fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
-              resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, lens_shading=None,
-              defect_correction=None, fast_median=False, fast_denoise_scene=False):
+              resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
+              lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
         ``tensor2bgr(self(raw / white_level))`` image by image (RGB order with ``reverse_channels``).  One launch where
         ``pipeline_fusion.serve_route`` says 'fused' (and the learned bilateral window allows it) or 'classical' (a classical
@@ -172,6 +173,16 @@ class _FixedPipeline(nn.Module):
         ``pipeline_fusion.defect_shade`` tells: 'fused' (that one launch shaded as well) or 'pass' (it corrected alone;
         ``risp_raw_shade`` follows where a shading is given); None without the keyword.
 
+        ``temporal_denoise=(state, strength, threshold, slope, ramp)`` filters the frames over time behind those pre-passes and
+        in front of the statistics and the route: each sample is blended over ``state.frames`` (a ``functional.TemporalState``,
+        built once by ``functional.temporal_state``) with a Q8 share that starts at ``strength`` and climbs to 256 where the
+        5 x 5 neighbourhood moved (``functional.temporal_check``; include/risp.h has the integer definition) - the bytes of the
+        same call without the keyword on ``functional.raw_temporal`` of the pre-pass's frames, on the route that call takes, and
+        the state advanced to those frames.  One ``risp_raw_temporal`` launch and one copy; packed frames without a pre-pass are
+        unpacked first (``last_serve_load`` is then 'pass', ``last_serve_shade`` 'pass' with a shading).  An unprimed state is
+        primed by the call - refused while the stream is capturing; a primed call with ``out`` captures, and every replay
+        advances the state.  ``last_serve_temporal`` is 'pass', None without the keyword.
+
         ``out_size=(OH, OW)`` and ``out_window=(y0, x0, h, w)`` deliver a scaled, cropped image (N,OH,OW,3): the window of the
         image as returned (default: all of it) resampled to ``out_size`` (default: the window's size, a crop) with ``resample``
         'box', 'triangle' or 'bicubic' - the bytes of ``functional.bgr8_resize`` of the same call without the keywords, on the
@@ -179,7 +190,7 @@ class _FixedPipeline(nn.Module):
         and one ``risp_bgr8_resize`` launch writes ``out``: ``last_serve_resize`` is 'pass', None without the keywords.  With
         ``out_format='nv12'`` (N,3*OH/2,OW), OH and OW even; ``last_serve_store`` is then 'resize' (that launch stored NV12,
         where ``pipeline_fusion.resize_store`` says 'fused') or 'pass' (``risp_bgr8_to_nv12`` followed it).  ``out_format``,
-        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``warp``, ``raw_width``,
+        ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``,
         ``lens_shading``, ``defect_correction``, ``fast_median`` and ``fast_denoise_scene`` are keyword-only
         (``pipeline_fusion.serve``).
 
@@ -204,12 +215,13 @@ class _FixedPipeline(nn.Module):
                          reverse_channels, out) is None:
                 resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
             stats_plan(raw_u16, raw_format, raw_width, (3,), statistics)
+            temporal_plan(raw_u16, raw_format, raw_width, (3,), temporal_denoise)
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
                                                     black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                                     out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size,
                                                     out_window=out_window, resample=resample, raw_format=raw_format,
-                                                    statistics=statistics, warp=warp, raw_width=raw_width, lens_shading=lens_shading,
+                                                    temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width, lens_shading=lens_shading,
                                                     defect_correction=defect_correction, fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
             self.last_serve_store = None if out_format == 'bgr8' else (
                 'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
@@ -241,12 +253,19 @@ class _FixedPipeline(nn.Module):
                 self.last_serve_stats = 'pass'
                 if lens_shading is not None:
                     self.last_serve_shade = 'pass'
+            self.last_serve_temporal = None
+            if temporal_denoise is not None:
+                self.last_serve_temporal = 'pass'
+                if self.last_serve_load is not None:
+                    self.last_serve_load = 'pass'
+                if lens_shading is not None:
+                    self.last_serve_shade = 'pass'
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
                     black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
-                    resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None, defect_correction=None,
-                    lens_shading=None):
+                    resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
+                    defect_correction=None, lens_shading=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
         uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8, the bytes ``test_split.py`` writes for
         ``raw / white_level`` with ``patch_size`` / ``patch_stride`` (an int or a pair; H, W, sizes and strides even).  One
@@ -259,7 +278,9 @@ class _FixedPipeline(nn.Module):
         (``last_serve_load`` 'pass').  ``lens_shading`` as in ``serve``: the whole frame is shaded once in front of the tiles
         (``last_serve_shade`` 'pass'), packed frames in that same launch.  ``defect_correction`` as in ``serve``: the whole
         frame is corrected once in front of the tiles and of the shading (``last_serve_defect`` as there), packed frames in
-        that same launch.  ``out_size``, ``out_window`` and ``resample`` as in ``serve``: the frames are blended at the sensor's
+        that same launch.  ``temporal_denoise`` as in ``serve``: the whole frame is filtered once over its state, (H,W) being one
+        image, behind those pre-passes and in front of the statistics and the tiles (``last_serve_temporal`` 'pass').
+        ``out_size``, ``out_window`` and ``resample`` as in ``serve``: the frames are blended at the sensor's
         size into a cached image and one ``risp_bgr8_resize`` launch writes (OH,OW,3) or (N,OH,OW,3) - NV12 likewise -;
         ``last_serve_resize`` and ``last_serve_store`` as there.  ``statistics`` as in ``serve``: the 3A statistics of the whole
         frames, (H,W) being one image, taken once in front of the tiles (``last_serve_stats`` 'pass').  ``warp`` as in
@@ -269,10 +290,11 @@ class _FixedPipeline(nn.Module):
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
                               reverse_channels, out, black_level, cfa, out_format, yuv_matrix, out_size=out_size,
-                              out_window=out_window, resample=resample, raw_format=raw_format, statistics=statistics,
-                              warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
+                              out_window=out_window, resample=resample, raw_format=raw_format,
+                              temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
             self.last_serve_route = 'tiled'
             self.last_serve_stats = None if statistics is None else 'pass'
+            self.last_serve_temporal = None if temporal_denoise is None else 'pass'
             self.last_serve_load = serve_load('tiled', raw_format)
             self.last_serve_shade = None if lens_shading is None else serve_shade('tiled', raw_format)
             self.last_serve_defect = None if defect_correction is None else (

@@ -608,6 +608,29 @@ def _corrected(frames, defect, bits, w, raw_format, shade):
                        _shaded_u16(shape, device))
 
 
+def _temporal_u16(shape, device):
+    """the uint16 frames the temporal noise reduction writes, kept per (shape, device, stream); none of the pre-passes' buffers:
+    the launch reads theirs, and its output may alias neither its input nor the state"""
+    return F._scene_buffer(device, 'temporal_u16', shape, torch.uint16)
+
+
+def temporal_plan(raw, raw_format, raw_width, dims, temporal_denoise):
+    """``F.temporal_check`` of ``temporal_denoise`` from the frames as given - uint16 or packed, of ``dims`` dimensions, one image
+    for an (H,W) frame -, nothing for None: what ``serve_frame`` and the modules' ``serve`` check before their first launch"""
+    if temporal_denoise is None:
+        return None
+    if raw_format != 'u16':
+        w = _packed_plan(raw, raw_format, raw_width, dims)[1]
+    elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint16 or raw.dim() not in dims:
+        raise ValueError('expected %s uint16 frames, got %s %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
+                                                                   getattr(raw, 'dtype', type(raw)), tuple(getattr(raw, 'shape', ()))))
+    else:
+        w = raw.shape[-1]
+    checked = F.temporal_check(temporal_denoise, 1 if raw.dim() == 2 else raw.shape[0], raw.shape[-2], w, raw.device)
+    F._temporal_prime(checked[0], torch.cuda.is_current_stream_capturing())     # an unprimed state under capture is refused here
+    return checked
+
+
 # output formats a resized call stores from the resize launch itself (risp_bgr8_resize with the matrix) instead of resizing to
 # packed BGR and converting that with risp_bgr8_to_nv12.  'nv12' is listed only if the fused store beats the two launches by
 # more than the larger spread of the two legs in every measured row of profiles/serve_resize.txt (two sizes, triangle and
@@ -763,8 +786,8 @@ def stats_plan(raw, raw_format, raw_width, dims, statistics):
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
           fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
-          out_size=None, out_window=None, resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None,
-          lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
+          out_size=None, out_window=None, resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None,
+          warp=None, raw_width=None, lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
     ``tensor2bgr`` of what ``fused_forward`` gives for ``raw / white_level``, on every route: ``'fused'``
     (``risp_serve_u8[_cfa]``, one launch), ``'classical'`` (``risp_serve_classical_u8``, one launch: ``serve_route``, H even
@@ -869,6 +892,22 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     live in a buffer of their own per shape, device and stream.  H >= 3, W % 4 == 0.  With ``out`` given a warm call allocates
     nothing and never waits for the device.  None is the call without the keyword.
 
+    ``temporal_denoise=(state, strength, threshold, slope, ramp)`` filters the frames over time, the one block with state across
+    calls: each sample is blended over ``state.frames`` - the previous filtered frames, an ``F.TemporalState`` built once for
+    these N, H, W (``F.temporal_state``) - with a Q8 share that starts at ``strength`` and climbs to 256 where the 5 x 5
+    neighbourhood says that something moved (``F.temporal_check``; include/risp.h has the integer definition).  It runs behind
+    ``defect_correction`` and ``lens_shading`` (fused into one launch where ``defect_shade`` says so, exactly as without the
+    keyword) and in front of ``statistics`` and the route: ``risp_raw_temporal`` - one launch and one device-to-device copy that
+    advances the state - reads the pre-pass's frames, or the uint16 input as given, or what ``risp_raw_unpack`` makes of packed
+    input, and writes uint16 frames kept per shape, device and stream.  The bytes returned are those of the same call without the
+    keyword on ``F.raw_temporal(pre(frames), (a state of equal content, ...), black_level')``, ``pre`` being today's pre-pass or
+    the unpack and ``black_level'`` 0 behind a shading, and afterwards ``state.frames`` holds those filtered frames.  Behind
+    it nothing sees packed bytes or a shading: no fused packed or shading load is taken, and the route is chosen exactly as
+    without the keyword - the one uint16 frames from the allocator take.  A state whose ``.primed`` is False is primed by the
+    call: the frames pass and become the state.  That is refused while the stream is capturing; with ``out`` given and a
+    primed state a warm call allocates nothing and never waits, so it captures, and the captured copy makes every replay advance
+    the state.  H >= 3, W % 4 == 0.  None is the call without the keyword.
+
     ``out_size=(OH, OW)`` and ``out_window=(y0, x0, h, w)`` deliver a scaled, cropped image: the window of the image as returned
     (default: all of it) resampled to ``out_size`` (default: the window's size, a crop) with ``resample`` 'box', 'triangle' or
     'bicubic' (``F.resize_check``; include/risp.h has the integer definition).  The route is chosen exactly as without the
@@ -907,7 +946,7 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     and ``out`` are checked before anything is launched; with ``out`` given a warm call allocates nothing and never waits.
     None is today's call, launch for launch.
 
-    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``statistics``, ``warp``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
+    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -939,6 +978,10 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     defect = defect_correction
     if defect is not None:
         F.defect_check(defect, h, w, raw_u16.device)        # refused before anything is launched
+    temporal = temporal_denoise
+    if temporal is not None:                                # refused before anything is launched, an unprimed state under capture too
+        temporal = F.temporal_check(temporal, n, h, w, raw_u16.device)
+        F._temporal_prime(temporal[0], torch.cuda.is_current_stream_capturing())
     stats = statistics
     if stats is not None:
         F.stats_check(stats, n, h, w, raw_u16.device)       # refused before anything is launched
@@ -948,7 +991,7 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
                                    _warp_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                    fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect,
-                                   stats=stats)
+                                   stats=stats, temporal=temporal)
         return _warped(img, plan, warp, resample, out), route
     if out_size is not None or out_window is not None:
         plan = _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, (n,),
@@ -956,23 +999,24 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
                                    _resize_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
                                    fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect,
-                                   stats=stats)
+                                   stats=stats, temporal=temporal)
         return _resized(img, plan, resample, out), route
     coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
     if coef is not None:
         if out is not None:
             F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
         img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade, defect, stats)
+                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade, defect, stats,
+                                temporal)
         return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
     return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
                       fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade,
-                      defect=defect, stats=stats)
+                      defect=defect, stats=stats, temporal=temporal)
 
 
 def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
                fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False, shade=None,
-               defect=None, stats=None):
+               defect=None, stats=None, temporal=None):
     """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
     NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
     With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
@@ -987,7 +1031,11 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
     shaded too with ``shade``, by that launch or by ``risp_raw_shade`` behind it (``defect_shade``); no fused load is taken.
     With ``stats`` (a checked ``F.RawStatistics``): ``risp_raw_stats`` reads what the route is about to read - behind a pre-pass
     its cached frames, which are then made first and no fused shading load is taken, otherwise the input as given, packed or
-    not, with ``black_level``; the route is chosen as without it"""
+    not, with ``black_level``; the route is chosen as without it.
+    With ``temporal`` (a checked ``F.temporal_check`` tuple): ``risp_raw_temporal`` runs now, on ``frames()`` as the lines above
+    make them - the pre-pass's frames, the uint16 input, or the unpacked frames -, with ``black_level`` (0 behind a shading), into
+    a cached uint16 stack of its own, and advances the state; every route and the statistics run on that stack, the route being
+    the one uint16 frames from the allocator take, and nothing behind it sees packed bytes or a shading"""
     device = raw_u16.device
     if defect is not None:
         (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
@@ -1015,8 +1063,15 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
 
         def frames():
             return F.raw_unpack(packed[0], packed[1], w, _packed_u16((n, h, w), device))
+    if temporal is not None:
+        # the filter runs now, once: it advances the state.  Behind it nothing sees packed bytes or a shading
+        filtered = F.raw_temporal(frames(), temporal, black_level, _temporal_u16((n, h, w), device))
+        packed, shade, aligned = None, None, True
+
+        def frames():
+            return filtered
     if stats is not None:
-        if defect is not None or shade is not None:
+        if temporal is not None or defect is not None or shade is not None:
             # the pre-pass runs now and the statistics read its frames; nothing behind it sees a shading (no fused shading load)
             ready = frames()
             shade = None
@@ -1127,8 +1182,8 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
                 out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None,
-                out_window=None, resample='triangle', raw_format='u16', statistics=None, warp=None, raw_width=None,
-                defect_correction=None, lens_shading=None):
+                out_window=None, resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None,
+                raw_width=None, defect_correction=None, lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
     (N,H,W) uint16 mosaic on the device -> (H,W,3) or (N,H,W,3) uint8.  Per frame ONE ``raw_crops`` launch cuts the
     (T,1,h,w) tile stack out of the mosaic (``util_path_restore.frame_tile_sel``: pedestal in integers, divisor
@@ -1153,6 +1208,10 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     everything else: ``risp_raw_defect`` writes uint16 frames kept per shape, device and stream - from packed frames too, in
     place of the unpack launch; with ``lens_shading`` it shades in the same launch where ``defect_shade`` says 'fused', and
     ``risp_raw_shade`` follows otherwise.
+    ``temporal_denoise=(state, strength, threshold, slope, ramp)`` (keyword-only, as in ``serve``; an ``F.TemporalState`` for N
+    frames, N = 1 for an (H,W) frame) filters the whole frame once in front of the tiles and of the statistics, behind the
+    pre-passes above: ``risp_raw_temporal`` - one launch and the copy that advances the state - writes uint16 frames kept per
+    shape, device and stream; packed frames without a pre-pass are unpacked first.  Checked before anything is launched.
     ``out_size``, ``out_window`` and ``resample`` (keyword-only, as in ``serve``) deliver a scaled, cropped image: every frame
     is blended into a packed sensor-size image kept per shape, device and stream (``reverse_channels`` honoured there) and ONE
     ``risp_bgr8_resize`` launch behind the last frame writes ``out``: (OH,OW,3) or (N,OH,OW,3), with ``out_format='nv12'``
@@ -1179,7 +1238,11 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
         stats_plan(raw_u16, raw_format, raw_width, (2, 3), statistics)
         if black_level != int(black_level) or not 0 <= black_level < white_level:
             raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-    if lens_shading is not None or defect_correction is not None:
+    temporal = temporal_plan(raw_u16, raw_format, raw_width, (2, 3), temporal_denoise)     # refused before anything is launched
+    if temporal is not None and (black_level != int(black_level) or not 0 <= black_level < white_level):
+        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
+    prepass = lens_shading is not None or defect_correction is not None
+    if prepass:
         if raw_format != 'u16':
             bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
         else:
@@ -1205,11 +1268,20 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
         if lens_shading is not None:
             white_level, black_level = white_level - black_level, 0
         raw_format = 'u16'
-        if statistics is not None:                          # the statistics of the pre-pass's frames
+    if temporal is not None:                                # behind the pre-pass, in front of the statistics and the tiles
+        if raw_format != 'u16':
+            bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
+            F._need_gpu(raw_u16, 'raw')
+            raw_u16 = F.raw_unpack(raw_u16.contiguous(), bits, w, _packed_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
+            raw_format = 'u16'
+        F._need_gpu(raw_u16, 'raw')
+        raw_u16 = F.raw_temporal(raw_u16.contiguous(), temporal, int(black_level), _temporal_u16(tuple(raw_u16.shape), raw_u16.device))
+    if statistics is not None:
+        if prepass or temporal is not None:                 # the statistics of the pre-pass's or the filter's frames
             F.raw_stats(raw_u16, statistics, int(black_level), 16)
-    elif statistics is not None:                            # of the input as given, packed or not
-        F.raw_stats(raw_u16.contiguous(), statistics, int(black_level), F.raw_format_bits(raw_format) or 16,
-                    raw_width if raw_format != 'u16' else None)
+        else:                                               # of the input as given, packed or not
+            F.raw_stats(raw_u16.contiguous(), statistics, int(black_level), F.raw_format_bits(raw_format) or 16,
+                        raw_width if raw_format != 'u16' else None)
     if raw_format != 'u16':
         bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
         F._need_gpu(raw_u16, 'raw')

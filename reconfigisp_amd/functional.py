@@ -1549,6 +1549,127 @@ def raw_defect(frames, defect, bits=16, width=None, shading=None, black_level=0,
     return out
 
 
+class TemporalState:
+    """The state of the temporal noise reduction for (N,H,W) frames: ``.frames``, (N,H,W) ``torch.uint16``, contiguous and 8-byte
+    aligned - the previous filtered frames, which every call that takes the state reads and then overwrites with what it returns -
+    and ``.primed``, a host bool that starts False: the first call copies its frames into the state instead of filtering.
+    ``.reset()`` clears the flag (a scene cut, a new stream).  Built once by the caller (``temporal_state``); one state belongs to
+    one sequence (include/risp.h has the definition to the bit)."""
+
+    def __init__(self, n, h, w, device=None):
+        if _small_int(n, 1, 1 << 30) is None:
+            raise ValueError('a temporal state of %r frames: N >= 1' % (n,))
+        if _small_int(h, 3, 1 << 30) is None or _small_int(w, 4, 1 << 30) is None or w % 4:
+            raise ValueError('a temporal state of %r x %r frames: H >= 3, W >= 4 and a multiple of 4' % (h, w))
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        self.frames = torch.zeros((self.n, self.h, self.w), dtype=torch.uint16, device='cuda' if device is None else device)
+        self.primed = False
+
+    def reset(self):
+        self.primed = False
+
+    def __repr__(self):
+        return 'TemporalState(%d, %d, %d, primed=%s)' % (self.n, self.h, self.w, self.primed)
+
+
+def temporal_state(n, h, w, device=None):
+    """A ``TemporalState`` for (N,H,W) frames on ``device`` (None: the current HIP device), N = 1 for an (H,W) frame: built once,
+    it owns ``.frames``, which ``raw_temporal`` and ``serve(temporal_denoise=)`` read and advance, and ``.primed``."""
+    return TemporalState(n, h, w, device)
+
+
+def temporal_check(td, n, h, w, device=None):
+    """A temporal noise reduction ``(state, strength, threshold, slope, ramp)`` for N frames of H x W on ``device``, checked on
+    the host before anything is launched -> (state, strength, threshold, slope, ramp) with the numbers as ints.  ``state``: a
+    ``TemporalState`` whose ``.frames`` are contiguous (N,H,W) ``torch.uint16`` on the device, 8-byte aligned; ``strength``: an
+    integer 0 .. 256, Q8, the share of the new frame where nothing moves (256 passes the frames, 0 freezes); ``threshold``: an
+    integer 0 .. 65535 in codes of mean difference over the 5 x 5 window; ``slope``: an integer 0 .. 255, Q8, the part of the
+    threshold that grows with the signal; ``ramp``: an integer 0 .. 65535, Q8 per code of summed excess.  H >= 3, W >= 4,
+    W % 4 == 0.  Nothing on the device is read: the host never waits (include/risp.h has the definition to the bit)."""
+    try:
+        state, strength, threshold, slope, ramp = td
+    except (TypeError, ValueError):
+        raise ValueError('a temporal noise reduction is (state, strength, threshold, slope, ramp): a TemporalState, a Q8 share '
+                         '0 .. 256, codes 0 .. 65535, a Q8 slope 0 .. 255, a Q8 ramp 0 .. 65535') from None
+    if not isinstance(state, TemporalState):
+        raise ValueError('the temporal state must be a TemporalState (functional.temporal_state builds one), got %s'
+                         % (type(state).__name__,))
+    stg = _small_int(strength, 0, 256)
+    if stg is None:
+        raise ValueError('temporal strength %r: an integer in 0 .. 256 (Q8)' % (strength,))
+    thr = _small_int(threshold, 0, 65535)
+    if thr is None:
+        raise ValueError('temporal threshold %r: an integer in 0 .. 65535 (codes of mean difference)' % (threshold,))
+    slp = _small_int(slope, 0, 255)
+    if slp is None:
+        raise ValueError('temporal slope %r: an integer in 0 .. 255 (Q8)' % (slope,))
+    rmp = _small_int(ramp, 0, 65535)
+    if rmp is None:
+        raise ValueError('temporal ramp %r: an integer in 0 .. 65535 (Q8 per code)' % (ramp,))
+    if int(h) < 3 or int(w) < 4 or int(w) % 4:
+        raise ValueError('temporal noise reduction on %d x %d frames: H >= 3, W >= 4 and a multiple of 4' % (h, w))
+    t = state.frames
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.uint16 or tuple(t.shape) != (int(n), int(h), int(w))
+            or not t.is_contiguous()):
+        raise ValueError('the temporal state of %d frames of %d x %d must hold contiguous (%d,%d,%d) uint16 frames, got %s %s'
+                         % (n, h, w, n, h, w, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+    _need_gpu(t, 'temporal state')
+    if device is not None and t.device != torch.device(device):
+        raise ValueError('the temporal state lives on %s, the frames on %s' % (t.device, device))
+    if t.data_ptr() % 8:
+        raise ValueError('the temporal state must be 8-byte aligned')
+    return state, stg, thr, slp, rmp
+
+
+def _temporal_prime(state, capturing):
+    """whether the call in hand primes ``state``; an unprimed state while the stream is capturing is refused"""
+    if state.primed:
+        return 0
+    if capturing:
+        raise RuntimeError('the temporal state is not primed and the stream is capturing: the graph would replay the priming '
+                           'form forever.  Prime with one eager call, then capture')
+    return 1
+
+
+def raw_temporal(frames, td, black_level=0, out=None):
+    """Temporal noise reduction of sensor frames in ONE launch and one copy (``risp_raw_temporal``): (N,H,W) or (H,W)
+    ``torch.uint16`` frames on the device and ``td`` = (state, strength, threshold, slope, ramp) (``temporal_check``; N = 1 for
+    an (H,W) frame) -> (N,H,W) or (H,W) ``torch.uint16``, the filtered frames, and ``state.frames`` advanced to them by a
+    device-to-device copy on the same stream.  Per pixel the frame is blended over the state with a Q8 share k that starts at
+    ``strength`` and climbs to 256 as the summed difference of the 5 x 5 window passes
+    25 * threshold + (slope * max(sum of the state - 25 * black_level, 0) >> 8), by ``ramp`` / 256 per code; borders reflect;
+    neighbours are the previous state's and the current frame's (include/risp.h has the definition to the bit).
+    ``black_level`` is the pedestal of the samples: 0 behind a shading.  A state whose ``.primed`` is False is primed: the
+    frames come back as they are and become the state; that is refused while the stream is capturing - prime with one eager
+    call, then capture, and every replay advances the state.  Packed frames are not taken: they come through ``raw_unpack`` or a
+    pre-pass first.  H >= 3, W % 4 == 0.  ``out`` (contiguous, 8-byte aligned) must share memory with neither the frames nor
+    the state - the launch reads rows other threads write; with it nothing is allocated and the host does not wait."""
+    _need_gpu(frames, 'frames')
+    if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+        raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
+    single = frames.dim() == 2
+    n, h, w = (1,) + tuple(frames.shape) if single else tuple(frames.shape)
+    state, stg, thr, slp, rmp = temporal_check(td, n, h, w, frames.device)
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    shape = (h, w) if single else (n, h, w)
+    if out is None:
+        out = torch.empty(shape, device=frames.device, dtype=torch.uint16)
+    elif (out.dtype != torch.uint16 or out.device != frames.device or tuple(out.shape) != shape or not out.is_contiguous()
+            or out.data_ptr() % 8):
+        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
+                         % (shape, frames.device, out.dtype, tuple(out.shape)))
+    else:
+        for t, what in ((frames, 'the frames'), (state.frames, 'the temporal state')):
+            if out.data_ptr() < t.data_ptr() + t.numel() * 2 and t.data_ptr() < out.data_ptr() + out.numel() * 2:
+                raise ValueError('out shares memory with %s: the filter reads neighbours other threads would have overwritten' % what)
+    prime = _temporal_prime(state, torch.cuda.is_current_stream_capturing())
+    L.call('risp_raw_temporal', _p(frames), _p(state.frames), _p(out), prime, stg, thr, slp, rmp, int(black_level), n, h, w,
+           _stream())
+    state.primed = True
+    return out
+
+
 def _stats_spec(zone, bins, hist_shift, lo, hi):
     """the specification of the 3A statistics, checked on the host -> (zone_h, zone_w, bins, hist_shift, lo, hi) as ints"""
     try:

@@ -200,6 +200,7 @@ SIGNATURES = {
     'risp_serve_classical_shaded': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _f, _i, C.POINTER(_i), _f, _i, _i, _i, _i, _i, _i, _i, _i,
                                          _s]),
     'risp_raw_defect': (_i, [_f, _i, _i, _f, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_raw_temporal': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bgr8_resize': (_i, [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _s]),
     'risp_raw_stats': (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bgr8_warp': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
