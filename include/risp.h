@@ -82,7 +82,8 @@ size_t risp_channel_stats_scratch_floats(int NC, int HW);
 int risp_channel_stats(const float *x, float *stats, int32_t *arg, float *scratch, int NC, int HW,
                        void *stream);
 /* backward of the statistics, in place on gx (NC planes): gx += g_mean[plane]/HW everywhere,
- * gx[argmin] += g_min[plane], gx[argmax] += g_max[plane]; any of the three may be NULL. */
+ * gx[argmin] += g_min[plane], gx[argmax] += g_max[plane]; any of the three may be NULL.  Any HW > 0, as the forward:
+ * 16-byte accesses when HW % 4 == 0 and gx is 16-byte aligned, element accesses otherwise. */
 int risp_stats_bwd(float *gx, const float *g_min, const float *g_mean, const float *g_max,
                    const int32_t *arg, int NC, int HW, void *stream);
 /* the same with the three gradients as column ranges of a row-major (N, row_stride) matrix - plane n * C + c reads

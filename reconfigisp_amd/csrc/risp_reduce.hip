@@ -175,6 +175,26 @@ __global__ __launch_bounds__(256) void stats_bwd_kernel(float *__restrict__ gx, 
     }
 }
 
+// the same update from element loads and stores: planes whose size is no multiple of 4 do not start on 16-byte boundaries (a
+// 9 x 17 image); per element the same three additions in the same order as above
+__global__ __launch_bounds__(256) void stats_bwd_scalar_kernel(float *__restrict__ gx, const float *__restrict__ g_min,
+                                                               const float *__restrict__ g_mean,
+                                                               const float *__restrict__ g_max,
+                                                               const int32_t *__restrict__ arg, int hw, float inv_hw, int C,
+                                                               int gstride) {
+    const int plane = blockIdx.y, gi = (plane / C) * gstride + plane % C;
+    float *gb = gx + (size_t)plane * hw;
+    const float add = g_mean ? g_mean[gi] * inv_hw : 0.f;
+    const int imn = (g_min && arg) ? arg[plane * 2] : -1, imx = (g_max && arg) ? arg[plane * 2 + 1] : -1;
+    const float vmn = g_min ? g_min[gi] : 0.f, vmx = g_max ? g_max[gi] : 0.f;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
+        float t = gb[i] + add;
+        if (i == imn) t += vmn;
+        if (i == imx) t += vmx;
+        gb[i] = t;
+    }
+}
+
 // ---- SRCNNRes broadcast-plane values (srcnn_res_arch.py:36-43): [min(3) | mean(3) | max(3) | params(P)]
 __global__ void srcnn_cvals_kernel(const float *__restrict__ stats, const float *__restrict__ pv,
                                    float *__restrict__ cvals, int N, int P, float inv_hw) {
@@ -417,12 +437,17 @@ int risp_histc(const float *x, float *hist, int NC, int HW, int bins, void *stre
 
 static int stats_bwd_launch(const char *name, float *gx, const float *g_min, const float *g_mean, const float *g_max,
                             const int32_t *arg, int NC, int HW, int C, int gstride, void *stream) {
-    RISP_CHECK_ARG(gx && NC > 0 && NC <= 65535 && HW > 0 && HW % 4 == 0, "%s: bad arguments", name);
+    RISP_CHECK_ARG(gx && NC > 0 && NC <= 65535 && HW > 0, "%s: bad arguments", name);
     RISP_CHECK_ARG(arg || (!g_min && !g_max), "%s: arg indices required for min/max gradients", name);
-    int bx = (HW / 4 + 255) / 256;
+    const bool vec = HW % 4 == 0 && reinterpret_cast<uintptr_t>(gx) % 16 == 0;
+    int bx = ((vec ? HW / 4 : HW) + 255) / 256;
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(stats_bwd_kernel, dim3(bx, NC), dim3(256), 0, (hipStream_t)stream, gx, g_min, g_mean, g_max,
-                       arg, HW / 4, 1.0f / (float)HW, C, gstride);
+    if (vec)
+        hipLaunchKernelGGL(stats_bwd_kernel, dim3(bx, NC), dim3(256), 0, (hipStream_t)stream, gx, g_min, g_mean, g_max,
+                           arg, HW / 4, 1.0f / (float)HW, C, gstride);
+    else
+        hipLaunchKernelGGL(stats_bwd_scalar_kernel, dim3(bx, NC), dim3(256), 0, (hipStream_t)stream, gx, g_min, g_mean,
+                           g_max, arg, HW, 1.0f / (float)HW, C, gstride);
     RISP_LAUNCH_CHECK(name);
     return 0;
 }
