@@ -105,6 +105,7 @@ def test_head_kernels_against_float64(shape):
                _p(a), _p(g_up), _p(out), n, h, w, _stream())
     rx, rup = torch.autograd.grad(ref, (x, up), gy)
     # a hidden pre-activation within fp32 rounding of 0 may take the other side of the ReLU: leave its 3x3 footprint out
+    # (the kernel rows of tests/test_gpu_demosaicnet_space.py draw inputs without such a unit and compare every pixel)
     pre = torch.nn.functional.conv2d(torch.cat([R.masked_mosaic(x.detach()), up.detach()], 1), fd['post.weight'], fd['post.bias'],
                                      padding=1)
     near = (pre.abs() < 2e-6 * pre.abs().max()).any(dim=1, keepdim=True).double()
