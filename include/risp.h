@@ -1151,6 +1151,43 @@ int risp_bgr8_resize(const uint8_t *img, uint8_t *out, const int32_t *xstart, co
 int risp_bgr8_warp(const uint8_t *img, uint8_t *out, const int32_t *mesh, int cell_log2, int MH, int MW, int kernel, int stage,
                    int N, int H, int W, int WH, int WW, void *stream);
 
+/* Output sharpening of the serving path (risp_sharpen.hip): the edge-enhancement (EE) block between the scaler and the YUV
+ * output of an ISP - an unsharp mask of luma with coring and a limit.  An integer function of packed 8-bit images, fixed to the
+ * bit (tests/sharpen_reference.py restates all of it in numpy int64).
+ *
+ * Source: img, packed 8-bit (N,H,W,3), B,G,R per pixel or R,G,B with rgb_in != 0.  Parameters: radius 1 or 2, amount
+ * 0 .. RISP_SHARPEN_MAX_AMOUNT (Q8: 256 is a gain of 1.0), threshold 0 .. 255 and limit 0 .. 255 (codes).  All arithmetic is
+ * unsigned or signed 32-bit and nothing can overflow: 65280 * 4095 + 32768 < 2^32.
+ *
+ *     luma      L = (77 R + 150 G + 29 B + 128) >> 8                    0 .. 255; the weights do not depend on any YUV matrix
+ *     blur      S = sum over the (2 radius + 1)^2 window of w * L        Q8, no intermediate rounding
+ *               radius 2: w = [1 4 6 4 1] (x) [1 4 6 4 1]; radius 1: w = 16 * ([1 2 1] (x) [1 2 1]); both sum to 256
+ *               window indices are clamped to 0 .. H-1 and 0 .. W-1 (replicate border, the warp's rule): every size from
+ *               1 x 1 is defined
+ *     detail    D = 256 L - S                                            signed, exact, |D| <= 65280
+ *     coring    A = max(|D| - 256 threshold, 0)                          soft: the threshold is subtracted, not only compared
+ *     gain      E = min((A * amount + 32768) >> 16, limit)               the limit follows the gain
+ *     output    c' = min(max(c + sign(D) * E, 0), 255)                   the same E for B, G and R
+ *
+ * The enhancement is of luma only: chroma differences are kept until a channel clips.  With amount == 0 or limit == 0 the
+ * image passes unchanged (still one launch).
+ *
+ * risp_bgr8_sharpen: one launch for all N images, no host synchronisation, capturable.  With coef == NULL out is (N,H,W,3)
+ * packed bytes in the channel order of img; with coef (twelve integers as in risp_bgr8_to_nv12, validated alike; H and W even)
+ * out is NV12 (N,3H/2,W) of the sharpened codes, byte for byte
+ * risp_bgr8_to_nv12(risp_bgr8_sharpen(.., NULL, ..), coef, rgb_in).  A workgroup owns RISP_SHARPEN_TILE_W x
+ * RISP_SHARPEN_TILE_H pixels and stages their source box, widened by the radius and clamped into the image, in LDS.  No
+ * alignment is asked of img or out - a packed row starts at any byte -, and no byte outside the two images is read or written
+ * for any H, W >= 1, the last partial dword of img included.  Rules (anything else is refused before the launch, the message
+ * names the value): no NULL img or out, 1 <= N <= 65535, H and W in 1 .. 2^24, at most 65535 row tiles, the parameter ranges
+ * above, out not overlapping img.  Not covered: overshoot control by local extremes, separate gains for dark and bright halos,
+ * a noise-adaptive threshold, sharpening fused into the resize or warp launch, chroma noise reduction. */
+#define RISP_SHARPEN_TILE_W 64
+#define RISP_SHARPEN_TILE_H 16
+#define RISP_SHARPEN_MAX_AMOUNT 4095
+int risp_bgr8_sharpen(const uint8_t *img, uint8_t *out, const int32_t *coef /* 12 integers or NULL */, int rgb_in, int radius,
+                      int amount, int threshold, int limit, int N, int H, int W, void *stream);
+
 /* Scene-adaptive stages on the serving path (risp_serve_scene.hip): gray-world, white-world and Reinhard need one
  * whole-image quantity in front of them - three sums, three maxima, one sum of logarithms.  The mosaic is read twice
  * instead of fp32 planes being written: a statistics launch, a finish launch, the serving launch (2 S + 1 launches for S

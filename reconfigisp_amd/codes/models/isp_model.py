@@ -124,7 +124,7 @@ class IspModel(BaseModel):
         return self.output, self.netG.intermediate_results
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
+              fast_denoise=False, fast_cond=False, *, sharpen=None, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
               resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
               lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """(N,H,W) uint16 frames on the device -> (N,H,W,3) uint8 (the pipeline's ``serve``; ``black_level`` and ``cfa``
@@ -153,25 +153,29 @@ class IspModel(BaseModel):
         focus measure - of the samples the route demosaics, the image unchanged;
         ``warp=(mesh, cell, (WH, WW), kernel)`` delivers a geometry-corrected image (N,WH,WW,3) through a mesh of Q8 source
         coordinates - lens distortion, rotation, flips, keystone, stabilisation -, the bytes of ``functional.bgr8_warp`` of the
-        same call without it, in front of the resize and the NV12 conversion where those are asked for)."""
+        same call without it, in front of the resize and the NV12 conversion where those are asked for;
+        ``sharpen=(amount, threshold, limit, radius)`` sharpens the image as returned - an unsharp mask of luma with coring and
+        a limit, behind the warp and the resize and in front of the NV12 conversion -, the bytes of ``functional.bgr8_sharpen``
+        of the same call without it)."""
         with torch.no_grad():
             return self.netG_attr.serve(raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene, fast_denoise, fast_cond,
-                                        out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size, out_window=out_window,
+                                        sharpen=sharpen, out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size, out_window=out_window,
                                         resample=resample, raw_format=raw_format, temporal_denoise=temporal_denoise, statistics=statistics,
                                         warp=warp, raw_width=raw_width,
                                         lens_shading=lens_shading, defect_correction=defect_correction, fast_median=fast_median,
                                         fast_denoise_scene=fast_denoise_scene)
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
-                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
+                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', sharpen=None, *, out_size=None, out_window=None,
                     resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
                     defect_correction=None, lens_shading=None):
         """(H,W) or (N,H,W) uint16 sensor frames on the device -> (H,W,3) or (N,H,W,3) uint8 through overlapped tiles (the
         pipeline's ``serve_frame``): the bytes ``test_split.py`` writes, without an fp32 frame at either end; ``black_level``
         and ``cfa`` describe the sensor; ``out_format='nv12'``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``,
-        ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``defect_correction`` and ``lens_shading`` as in ``serve``."""
+        ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``defect_correction`` and ``lens_shading`` as in ``serve``;
+        ``sharpen`` as there too - it stands in front of the ``*`` here, but is meant to be passed by name."""
         with torch.no_grad():
             return self.netG_attr.serve_frame(raw_u16, white_level, patch_size, patch_stride, tile_batch, reverse_channels, out,
-                                              black_level, cfa, out_format, yuv_matrix, out_size=out_size, out_window=out_window,
+                                              black_level, cfa, out_format, yuv_matrix, sharpen, out_size=out_size, out_window=out_window,
                                               resample=resample, raw_format=raw_format, temporal_denoise=temporal_denoise,
                                               statistics=statistics, warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, temporal_plan, wants_grad, warp_plan
+from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, sharpen_plan, sharpen_store, temporal_plan, wants_grad, warp_plan
 
 
 class _FixedPipeline(nn.Module):
@@ -48,6 +48,7 @@ class _FixedPipeline(nn.Module):
         self.last_serve_resize = None           # with out_size / out_window: 'pass' (risp_bgr8_resize behind the route); None without the keywords
         self.last_serve_shade = None            # with lens_shading: 'fused' (the serving launch shaded in its load) | 'pass' (risp_raw_shade did, decoding packed frames too); None without the keyword
         self.last_serve_defect = None           # with defect_correction: 'fused' (one risp_raw_defect launch corrected and shaded) | 'pass' (risp_raw_defect corrected; risp_raw_shade follows where lens_shading is given); None without the keyword
+        self.last_serve_sharpen = None          # with sharpen: 'pass' (risp_bgr8_sharpen behind the route, the warp and the resize); None without the keyword
         self.last_serve_warp = None             # with warp: 'pass' (risp_bgr8_warp behind the route); None without the keyword
         self.last_serve_temporal = None         # with temporal_denoise: 'pass' (risp_raw_temporal filtered the frames in front of the route and advanced the state); None without the keyword
         self.last_serve_stats = None            # with statistics: 'pass' (risp_raw_stats filled the RawStatistics from what the route reads); None without the keyword
@@ -102,7 +103,7 @@ class _FixedPipeline(nn.Module):
         return x
 
     def serve(self, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb', fast_scene=False,
-              fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
+              fast_denoise=False, fast_cond=False, *, sharpen=None, out_format='bgr8', yuv_matrix='bt601_full', out_size=None, out_window=None,
               resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
               lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
         """The pipeline as an ISP: (N,H,W) uint16 RGGB frames on the device -> (N,H,W,3) uint8, the bytes of
@@ -208,17 +209,30 @@ class _FixedPipeline(nn.Module):
         image and one ``risp_bgr8_warp`` launch writes the warped image - into ``out``, or in front of the resize
         (``out_size`` / ``out_window`` then apply to the warped image) and of the NV12 conversion (WH, WW even;
         ``last_serve_store`` 'pass' or as under a resize): the bytes of ``functional.bgr8_warp`` of the same call without the
-        keyword.  Statistics are unchanged.  ``last_serve_warp`` is 'pass', None without it."""
+        keyword.  Statistics are unchanged.  ``last_serve_warp`` is 'pass', None without it.
+
+        ``sharpen=(amount, threshold, limit, radius)`` (keyword-only) sharpens the image as returned, behind ``warp`` and
+        ``out_size`` / ``out_window`` and in front of the NV12 conversion: an unsharp mask of the 8-bit luma - binomial blur of
+        ``radius`` 1 or 2, soft coring by ``threshold`` codes, the gain ``amount`` / 256 (0 .. 4095), at most ``limit`` codes -
+        added to B, G and R alike (``functional.sharpen_check``; include/risp.h has the integer definition).  The stage in front
+        of it stores packed BGR into a cached image and one ``risp_bgr8_sharpen`` launch writes ``out``: the bytes of
+        ``functional.bgr8_sharpen`` of the same call without the keyword, ``reverse_channels`` honoured.  With
+        ``out_format='nv12'`` ``last_serve_store`` is 'sharpen' (that launch stored NV12, where
+        ``pipeline_fusion.sharpen_store`` says 'fused') or 'pass' (``risp_bgr8_to_nv12`` followed it).  Statistics, the temporal
+        state and every other ``last_serve_*`` are unchanged.  ``last_serve_sharpen`` is 'pass', None without it."""
         with torch.no_grad():
-            # (the warp and resize keywords are refused before the stage parameters are made: that is a launch)
-            if warp_plan(raw_u16, raw_format, raw_width, (3,), warp, out_size, out_window, resample, out_format, yuv_matrix,
-                         reverse_channels, out) is None:
+            # (the sharpen, warp and resize keywords are refused before the stage parameters are made: that is a launch)
+            if sharpen is not None:                     # (it plans the warp and the resize in front of it too)
+                sharpen_plan(raw_u16, raw_format, raw_width, (3,), sharpen, warp, out_size, out_window, resample, out_format,
+                             yuv_matrix, reverse_channels, out)
+            elif warp_plan(raw_u16, raw_format, raw_width, (3,), warp, out_size, out_window, resample, out_format, yuv_matrix,
+                           reverse_channels, out) is None:
                 resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
             stats_plan(raw_u16, raw_format, raw_width, (3,), statistics)
             temporal_plan(raw_u16, raw_format, raw_width, (3,), temporal_denoise)
             pars = self._stage_params(raw_u16.size(0))
             out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond,
+                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond, sharpen=sharpen,
                                                     out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size,
                                                     out_window=out_window, resample=resample, raw_format=raw_format,
                                                     temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width, lens_shading=lens_shading,
@@ -235,6 +249,11 @@ class _FixedPipeline(nn.Module):
                 self.last_serve_resize = 'pass'
                 if out_format != 'bgr8':
                     self.last_serve_store = 'resize' if resize_store(out_format) == 'fused' else 'pass'
+            self.last_serve_sharpen = None
+            if sharpen is not None:
+                self.last_serve_sharpen = 'pass'
+                if out_format != 'bgr8':                # the stages in front of the sharpen launch stored BGR
+                    self.last_serve_store = 'sharpen' if sharpen_store(out_format) == 'fused' else 'pass'
             self.last_serve_load = serve_load(self.last_serve_route, raw_format)
             self.last_serve_shade = None
             if lens_shading is not None:
@@ -263,7 +282,7 @@ class _FixedPipeline(nn.Module):
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
-                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None, out_window=None,
+                    black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', sharpen=None, *, out_size=None, out_window=None,
                     resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None, raw_width=None,
                     defect_correction=None, lens_shading=None):
         """A full sensor frame through the pipeline in overlapped tiles (``pipeline_fusion.serve_frame``): (H,W) or (N,H,W)
@@ -286,10 +305,12 @@ class _FixedPipeline(nn.Module):
         frames, (H,W) being one image, taken once in front of the tiles (``last_serve_stats`` 'pass').  ``warp`` as in
         ``serve``: the frames are blended at the sensor's size into a cached image and one ``risp_bgr8_warp`` launch behind the
         last frame writes (WH,WW,3) or (N,WH,WW,3), in front of the resize and the NV12 conversion where those are asked for
-        (``last_serve_warp`` 'pass')."""
+        (``last_serve_warp`` 'pass').  ``sharpen`` as in ``serve`` (it stands in front of the ``*`` here, but is meant to be
+        passed by name): one ``risp_bgr8_sharpen`` launch behind the last frame, the warp and the resize sharpens the image as
+        returned, in front of the NV12 conversion (``last_serve_sharpen`` 'pass', ``last_serve_store`` as there)."""
         with torch.no_grad():
             out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
-                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix, out_size=out_size,
+                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix, sharpen, out_size=out_size,
                               out_window=out_window, resample=resample, raw_format=raw_format,
                               temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
             self.last_serve_route = 'tiled'
@@ -306,6 +327,11 @@ class _FixedPipeline(nn.Module):
                 self.last_serve_resize = 'pass'
                 if out_format != 'bgr8':
                     self.last_serve_store = 'resize' if resize_store(out_format) == 'fused' else 'pass'
+            self.last_serve_sharpen = None
+            if sharpen is not None:
+                self.last_serve_sharpen = 'pass'
+                if out_format != 'bgr8':
+                    self.last_serve_store = 'sharpen' if sharpen_store(out_format) == 'fused' else 'pass'
         return out
 
     @property

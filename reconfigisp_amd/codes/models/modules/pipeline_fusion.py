@@ -765,6 +765,93 @@ def _warped(img, plan, warp, resample, out):
     return F.bgr8_warp(img, warp, out=out)
 
 
+# output formats a sharpened call stores from the sharpen launch itself (risp_bgr8_sharpen with the matrix) instead of sharpening
+# to packed BGR and converting that with risp_bgr8_to_nv12.  'nv12' is listed only if the fused store beats the two launches by
+# more than the larger spread of the two legs in every measured row of profiles/serve_sharpen.txt (three sizes, both radii;
+# DESIGN.md 4.6) - the rule of _FUSED_LOAD, _FUSED_SHADE, _DEFECT_SHADE_FUSED and _RESIZE_NV12_FUSED.  The verdict line of that
+# file is this table.  Measured: the fused store wins all six rows - 64 x 256 x 256 15.3 / 16.5 us (radius 1 / 2) against 21.9 / 23.0,
+# 3000 x 4000 38.1 / 40.7 against 47.8 / 51.2, 1080 x 1920 9.8 / 9.9 against 16.3 / 16.3, spreads of at most 0.7 us: the NV12 store
+# reads the sharpened tile from LDS, where the BGR store reads it too, and writes half the bytes, while the conversion launch reads
+# the whole image again.  Both forms are the same integer function and stay reachable through functional.bgr8_sharpen.
+_SHARPEN_NV12_FUSED = frozenset({'nv12'})
+
+
+def sharpen_store(out_format):
+    """Who stores the image of a call with ``sharpen``: None for ``out_format='bgr8'`` (the sharpen launch stores packed bytes);
+    for 'nv12' 'fused' - ``risp_bgr8_sharpen`` stores NV12 itself - or 'pass' - it stores packed BGR into a cached image and
+    ``risp_bgr8_to_nv12`` follows.  A pure function of its argument: what ``serve`` / ``serve_frame`` do, and
+    ``last_serve_store`` reports 'sharpen' for 'fused' and 'pass' for 'pass'."""
+    if out_format == 'bgr8':
+        return None
+    if out_format != 'nv12':
+        raise ValueError("unknown out_format %r: 'bgr8' or 'nv12'" % (out_format,))
+    return 'fused' if out_format in _SHARPEN_NV12_FUSED else 'pass'
+
+
+def _sharpen_bgr(shape, device):
+    """the packed image a call with ``sharpen`` puts in front of the sharpen launch, kept per (shape, device, stream); not the
+    warp's, the resize's or the NV12 route's image, whose shapes can coincide with it: the stages around the launch use those"""
+    return F._scene_buffer(device, 'sharpen_bgr', shape, torch.uint8)
+
+
+def _sharpen_plan(sharpen, h, w, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, lead, device):
+    """a call with ``sharpen``, checked on the host before anything is launched: (the checked tuple, the warp's plan or None,
+    the resize's plan where no warp is given or None, the twelve integers of an NV12 store or None, the size of the image as
+    returned).  The stages in front of the launch are planned for packed BGR; ``lead`` is the shape in front of the image's own
+    dimensions"""
+    F.sharpen_check(sharpen, out_format == 'nv12')
+    wplan = rplan = None
+    fh, fw = h, w
+    if warp is not None:
+        wplan = _warp_plan(warp, h, w, out_size, out_window, resample, 'bgr8', yuv_matrix, False, None, lead, device)
+        fh, fw = wplan[0][2] if wplan[1] is None else wplan[1][0]
+    elif out_size is not None or out_window is not None:
+        rplan = _resize_plan(out_size, out_window, resample, h, w, 'bgr8', yuv_matrix, False, None, lead, device)
+        fh, fw = rplan[0]
+    sp = F.sharpen_check(sharpen, out_format == 'nv12', fh, fw)
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, fh, fw)
+    if out is not None:
+        F._u8_out(out, tuple(lead) + ((fh, fw, 3) if coef is None else (fh + fh // 2, fw)), device, 1)
+    return sp, wplan, rplan, coef, (fh, fw)
+
+
+def sharpen_plan(raw, raw_format, raw_width, dims, sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix,
+                 reverse_channels, out):
+    """``_sharpen_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keyword: what
+    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
+    if sharpen is None:
+        return None
+    F.sharpen_check(sharpen, out_format == 'nv12')
+    if not isinstance(raw, torch.Tensor) or raw.dim() not in dims:
+        raise ValueError('expected %s frames, got %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
+                                                        tuple(getattr(raw, 'shape', ()))))
+    w = raw.shape[-1] if raw_format == 'u16' else _packed_plan(raw, raw_format, raw_width, dims)[1]
+    return _sharpen_plan(sharpen, raw.shape[-2], w, warp, out_size, out_window, resample, out_format, yuv_matrix,
+                         reverse_channels, out, tuple(raw.shape[:-2]), raw.device)
+
+
+def _sharpen_source(warp, out_size, out_window):
+    """the cached image the route of a call with ``sharpen`` serves into: that of the first stage behind the route"""
+    return _warp_bgr if warp is not None else (_resize_bgr if out_size is not None or out_window is not None else _sharpen_bgr)
+
+
+def _sharpened(img, plan, warp, resample, reverse_channels, out):
+    """the end of a call with ``sharpen``: the served packed image -> the warp and / or the resize launch where asked for, into
+    ``_sharpen_bgr`` -> ONE ``risp_bgr8_sharpen`` launch into ``out``; with NV12 that launch stores NV12 itself where
+    ``sharpen_store`` says so, otherwise it writes the NV12 conversion's source image and ``risp_bgr8_to_nv12`` follows"""
+    sp, wplan, rplan, coef, (fh, fw) = plan
+    shape = tuple(img.shape[:-3]) + (fh, fw, 3)
+    if wplan is not None:
+        img = _warped(img, wplan, warp, resample, _sharpen_bgr(shape, img.device))
+    elif rplan is not None:
+        img = _resized(img, rplan, resample, _sharpen_bgr(shape, img.device))
+    if coef is None:
+        return F.bgr8_sharpen(img, sp, None, 'rgb' if reverse_channels else 'bgr', out)
+    if sharpen_store('nv12') == 'fused':
+        return F.bgr8_sharpen(img, sp, coef, 'bgr', out)
+    return F.bgr8_to_nv12(F.bgr8_sharpen(img, sp, out=_nv12_bgr(shape, img.device)), coef, 'bgr', out)
+
+
 def stats_plan(raw, raw_format, raw_width, dims, statistics):
     """``F.stats_check`` of ``statistics`` from the frames as given - uint16 or packed, of ``dims`` dimensions, one image for an
     (H,W) frame -, nothing for None: what ``serve_frame`` and the modules' ``serve`` check before their first launch"""
@@ -785,7 +872,7 @@ def stats_plan(raw, raw_format, raw_width, dims, statistics):
 
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
-          fast_scene=False, fast_denoise=False, fast_cond=False, *, out_format='bgr8', yuv_matrix='bt601_full',
+          fast_scene=False, fast_denoise=False, fast_cond=False, *, sharpen=None, out_format='bgr8', yuv_matrix='bt601_full',
           out_size=None, out_window=None, resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None,
           warp=None, raw_width=None, lens_shading=None, defect_correction=None, fast_median=False, fast_denoise_scene=False):
     """The pipeline as an ISP: (N,H,W) uint16 frames on the device -> ((N,H,W,3) uint8, route taken).  The bytes are
@@ -946,7 +1033,20 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     and ``out`` are checked before anything is launched; with ``out`` given a warm call allocates nothing and never waits.
     None is today's call, launch for launch.
 
-    ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
+    ``sharpen=(amount, threshold, limit, radius)`` sharpens the image as returned - the edge-enhancement block between the
+    scaler and the YUV output: an unsharp mask of the 8-bit luma with a binomial blur of ``radius`` 1 or 2, the detail cored
+    softly by ``threshold`` codes, multiplied by ``amount`` / 256 (0 .. 4095), bounded by ``limit`` codes and added to B, G and R
+    alike (``F.sharpen_check``; include/risp.h has the integer definition).  The route is chosen exactly as without the keyword,
+    and so is every other choice; statistics and the temporal state do not change.  Whatever stage precedes the sharpening - the
+    route, the warp launch or the resize launch - stores packed BGR (``reverse_channels`` honoured there; the routes that own a
+    fused NV12 store serve BGR too) into an image of its own kept per shape, device and stream, and ONE ``risp_bgr8_sharpen``
+    launch, told the channel order, writes ``out``; with ``out_format='nv12'`` it stores NV12 itself where
+    ``sharpen_store('nv12')`` says 'fused' and writes the conversion's source image for ``risp_bgr8_to_nv12`` otherwise.  Byte
+    for byte ``nv12?(F.bgr8_sharpen(F.bgr8_resize?(F.bgr8_warp?(serve(.. without these keywords ..)))))``.  The tuple, odd sizes
+    with NV12 and ``out`` are refused before anything is launched; with ``out`` given a warm call allocates nothing and never
+    waits.  None is today's call, launch for launch.
+
+    ``sharpen``, ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
     packed = None
@@ -985,6 +1085,14 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     stats = statistics
     if stats is not None:
         F.stats_check(stats, n, h, w, raw_u16.device)       # refused before anything is launched
+    if sharpen is not None:
+        plan = _sharpen_plan(sharpen, h, w, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out,
+                             (n,), raw_u16.device)          # refused before anything is launched
+        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
+                                   _sharpen_source(warp, out_size, out_window)((n, h, w, 3), raw_u16.device), black_level, cfa,
+                                   fast_scene, fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median,
+                                   shade=shade, defect=defect, stats=stats, temporal=temporal)
+        return _sharpened(img, plan, warp, resample, reverse_channels, out), route
     if warp is not None:
         plan = _warp_plan(warp, h, w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, (n,),
                           raw_u16.device)                   # refused before anything is launched
@@ -1181,7 +1289,7 @@ def frame_geometry(H, W, size, stride, cfa, device):
 
 
 def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False,
-                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', *, out_size=None,
+                out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full', sharpen=None, *, out_size=None,
                 out_window=None, resample='triangle', raw_format='u16', temporal_denoise=None, statistics=None, warp=None,
                 raw_width=None, defect_correction=None, lens_shading=None):
     """A full sensor frame through the pipeline in overlapped tiles, the serving form of ``test_split.run_frame``: (H,W) or
@@ -1226,13 +1334,20 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     launch behind the last frame writes (WH,WW,3) or (N,WH,WW,3) into ``out`` - or into the source image of the resize launch
     (``out_size`` / ``out_window``, then applied to the warped image) or of the NV12 conversion that follows it.  Its refusals
     come before anything is launched; statistics are unchanged.  None changes nothing.
+    ``sharpen=(amount, threshold, limit, radius)`` (as in ``serve``; it stands in front of the ``*`` but is meant to be passed by
+    name) sharpens the image as returned: every frame is blended at the sensor's size into a cached packed image, the warp and
+    the resize launch follow where asked for, and ONE ``risp_bgr8_sharpen`` launch behind them writes ``out`` - or, with
+    ``out_format='nv12'``, NV12 itself or the source image of ``risp_bgr8_to_nv12`` (``sharpen_store``).  Its refusals come before
+    anything is launched; statistics and the temporal state are unchanged.  None changes nothing.
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
     from ...data.gpu_input import raw_crops
-    wplan = warp_plan(raw_u16, raw_format, raw_width, (2, 3), warp, out_size, out_window, resample, out_format, yuv_matrix,
-                      reverse_channels, out)                # refused before anything is launched
-    plan = None if wplan is not None else resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample,
+    splan = sharpen_plan(raw_u16, raw_format, raw_width, (2, 3), sharpen, warp, out_size, out_window, resample, out_format,
+                         yuv_matrix, reverse_channels, out) # refused before anything is launched; it plans the warp and the resize too
+    wplan = None if splan is not None else warp_plan(raw_u16, raw_format, raw_width, (2, 3), warp, out_size, out_window, resample,
+                                                     out_format, yuv_matrix, reverse_channels, out)     # likewise
+    plan = None if wplan is not None or splan is not None else resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample,
                                                       out_format, yuv_matrix, reverse_channels, out)    # likewise
     if statistics is not None:                              # refused before anything is launched
         stats_plan(raw_u16, raw_format, raw_width, (2, 3), statistics)
@@ -1301,8 +1416,11 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     size, stride = _pair(patch_size), _pair(patch_stride)
     origins, sel = frame_geometry(H, W, size, stride, cfa, frames.device)
     count, tile_batch = origins.shape[0], int(tile_batch)
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W) if plan is None and wplan is None else None
-    if wplan is not None:
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W) if plan is None and wplan is None and splan is None else None
+    if splan is not None:
+        # every frame is served at the sensor's size into the cached image of the first launch behind the loop
+        final, out = out, _sharpen_source(warp, out_size, out_window)((H, W, 3) if single else (n, H, W, 3), frames.device)
+    elif wplan is not None:
         # every frame is served at the sensor's size into the warp's cached image; the warp launch behind the loop reads it
         final, out = out, _warp_bgr((H, W, 3) if single else (n, H, W, 3), frames.device)
     elif plan is not None:
@@ -1331,6 +1449,8 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
             else:
                 F.tile_blend_u8(stack, origins, (H, W), stride, False, bgr, code)
                 F.bgr8_to_nv12(bgr, coef, 'bgr', out if single else out[k])
+    if splan is not None:
+        return _sharpened(out, splan, warp, resample, reverse_channels, final)
     if wplan is not None:
         return _warped(out, wplan, warp, resample, final)
     if plan is not None:

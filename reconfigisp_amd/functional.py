@@ -1184,6 +1184,77 @@ def warp_radial(H, W, size, cell, k1, k2=0.0, centre=None, zoom=1.0):
     return warp_mesh(warp_radial_source(H, W, size, k1, k2, centre, zoom), size, cell)
 
 
+# ---- output sharpening: the luma edge enhancement (risp_sharpen.hip; include/risp.h has the definition to the bit)
+SHARPEN_RADII = (1, 2)
+SHARPEN_MAX_AMOUNT = 4095               # RISP_SHARPEN_MAX_AMOUNT: Q8, 256 is a gain of 1.0
+SHARPEN_TILE_H = 16                     # RISP_SHARPEN_TILE_H: rows of a workgroup
+_SHARPEN_MAX = 1 << 24                  # sizes
+
+
+def sharpen_check(sharpen, nv12=False, H=None, W=None):
+    """A sharpening ``(amount, threshold, limit, radius)``, checked on the host before anything is launched -> the four as
+    ints.  ``amount``: 0 .. 4095, the Q8 gain on the detail (256 is 1.0); ``threshold``: 0 .. 255 codes of detail cored away
+    (soft: subtracted); ``limit``: 0 .. 255, the largest step in codes; ``radius``: one of ``SHARPEN_RADII``, the binomial
+    blur's (3 x 3 or 5 x 5).  Integers only - a bool or a float is refused.  With ``H`` / ``W`` given: 1 .. 2^24, at most
+    65535 row tiles, and even with ``nv12``.  Nothing is read from the device and the host never waits."""
+    try:
+        amount, threshold, limit, radius = sharpen
+    except (TypeError, ValueError):
+        raise ValueError('a sharpening is (amount, threshold, limit, radius): four integers - the Q8 gain 0 .. 4095, the coring '
+                         'threshold 0 .. 255, the limit 0 .. 255 and the radius 1 or 2; got %r' % (sharpen,)) from None
+    for name, v, hi in (('amount', amount, SHARPEN_MAX_AMOUNT), ('threshold', threshold, 255), ('limit', limit, 255)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError('sharpen %s %r: an integer (not a bool, not a float) in 0 .. %d' % (name, v, hi))
+        if not 0 <= v <= hi:
+            raise ValueError('sharpen %s %r: outside 0 .. %d' % (name, v, hi))
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise ValueError('sharpen radius %r: an integer (not a bool, not a float), one of %s' % (radius, SHARPEN_RADII))
+    if radius not in SHARPEN_RADII:
+        raise ValueError('sharpen radius %r: one of %s' % (radius, SHARPEN_RADII))
+    for name, v in (('H', H), ('W', W)):
+        if v is None:
+            continue
+        if _small_int(v, 1, _SHARPEN_MAX) is None:
+            raise ValueError('sharpening of images with %s = %r: 1 .. 2^24' % (name, v))
+        if nv12 and v % 2:
+            raise ValueError('sharpening into NV12 with %s = %d: a frame with an odd size has no 4:2:0 form, H and W must be even'
+                             % (name, v))
+    if H is not None and (H + SHARPEN_TILE_H - 1) // SHARPEN_TILE_H > 65535:
+        raise ValueError('sharpening of images with H = %d: more than 65535 row tiles of %d rows' % (H, SHARPEN_TILE_H))
+    return amount, threshold, limit, radius
+
+
+def bgr8_sharpen(img_u8, sharpen, nv12=None, channels='bgr', out=None):
+    """Packed 8-bit images sharpened in ONE launch (``risp_bgr8_sharpen``): (N,H,W,3) or (H,W,3) ``torch.uint8`` on the device ->
+    the same shape, ``sharpen = (amount, threshold, limit, radius)`` as ``sharpen_check`` takes it.  An unsharp mask of the 8-bit
+    luma ``(77 R + 150 G + 29 B + 128) >> 8`` - ``channels`` 'bgr' or 'rgb' names the order - with a binomial blur of the radius
+    (replicate border), the detail cored softly by ``threshold``, multiplied by ``amount`` / 256, bounded by ``limit`` and added
+    to B, G and R alike, clamped: an integer function, include/risp.h fixes every bit.  With ``nv12`` (a matrix as
+    ``nv12_matrix`` takes it) the same launch stores (N,3H/2,W) or (3H/2,W) YUV 4:2:0 of the sharpened codes instead, byte for
+    byte ``bgr8_to_nv12`` of the packed result (H, W even).  No alignment is asked of the images or of ``out``; ``out`` must not
+    share memory with the images.  With ``out`` given a call on contiguous images allocates nothing and the host never waits;
+    images that are not contiguous are copied first, which allocates."""
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
+        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
+                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
+    if channels not in ('bgr', 'rgb'):
+        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    coef = None if nv12 is None else nv12_matrix(nv12)
+    h, w = img_u8.shape[-3], img_u8.shape[-2]
+    amount, threshold, limit, radius = sharpen_check(sharpen, coef is not None, h, w)
+    _need_gpu(img_u8, 'img')
+    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
+    if n > 65535:
+        raise ValueError('%d images in one call: at most 65535' % n)
+    img_u8 = img_u8.contiguous()
+    out = _u8_out(out, tuple(img_u8.shape[:-3]) + ((h, w, 3) if coef is None else (h + h // 2, w)), img_u8.device, 1)
+    if (out.data_ptr() < img_u8.data_ptr() + img_u8.numel() and img_u8.data_ptr() < out.data_ptr() + out.numel()):
+        raise ValueError('out shares memory with the images: a tile reads pixels other tiles would have overwritten')
+    L.call('risp_bgr8_sharpen', _p(img_u8), _p(out), None if coef is None else (C.c_int * 12)(*coef), int(channels == 'rgb'),
+           radius, amount, threshold, limit, n, h, w, _stream())
+    return out
+
+
 def serve_nv12(raw_u16, divisor, ops, params, bilateral=None, matrix='bt601_full', out=None, black_level=0, cfa='rggb'):
     """``serve_u8`` with the NV12 store (``risp_serve_nv12``, ONE launch): the same arguments with ``matrix``
     (``nv12_matrix``) in place of ``reverse_channels`` -> (N,3H/2,W) ``torch.uint8``, byte for byte

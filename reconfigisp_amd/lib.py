@@ -204,6 +204,7 @@ SIGNATURES = {
     'risp_bgr8_resize': (_i, [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _s]),
     'risp_raw_stats': (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bgr8_warp': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_bgr8_sharpen': (_i, [_f, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_scene_groups': (_i, [_i, _i]),
     'risp_serve_scene_stats': (_i, [_f, _fl, _i, _i, C.POINTER(_i), _pp, _i, _f, _i, _i, _i, _i, _i, _s]),
     'risp_serve_scene_finish': (_i, [_i, _f, _f, _f, _f, _i, _i, _i, _s]),
