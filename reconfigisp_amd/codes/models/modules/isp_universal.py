@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .... import functional as F
 from . import registry as R
-from .pipeline_fusion import stats_plan, defect_shade, fused_forward, resize_plan, resize_store, serve, serve_frame, serve_load, serve_shade, sharpen_plan, sharpen_store, temporal_plan, wants_grad, warp_plan
+from .pipeline_fusion import fused_forward, output_plan, serve_frame_reported, serve_reported, stats_plan, temporal_plan, wants_grad
 
 
 class _FixedPipeline(nn.Module):
@@ -221,64 +221,19 @@ class _FixedPipeline(nn.Module):
         ``pipeline_fusion.sharpen_store`` says 'fused') or 'pass' (``risp_bgr8_to_nv12`` followed it).  Statistics, the temporal
         state and every other ``last_serve_*`` are unchanged.  ``last_serve_sharpen`` is 'pass', None without it."""
         with torch.no_grad():
-            # (the sharpen, warp and resize keywords are refused before the stage parameters are made: that is a launch)
-            if sharpen is not None:                     # (it plans the warp and the resize in front of it too)
-                sharpen_plan(raw_u16, raw_format, raw_width, (3,), sharpen, warp, out_size, out_window, resample, out_format,
-                             yuv_matrix, reverse_channels, out)
-            elif warp_plan(raw_u16, raw_format, raw_width, (3,), warp, out_size, out_window, resample, out_format, yuv_matrix,
-                           reverse_channels, out) is None:
-                resize_plan(raw_u16, raw_format, raw_width, (3,), out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out)
+            # (the output keywords, the statistics and the filter are refused before the stage parameters are made: that is a launch)
+            output_plan(raw_u16, raw_format, raw_width, (3,), sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix,
+                        reverse_channels, out)
             stats_plan(raw_u16, raw_format, raw_width, (3,), statistics)
             temporal_plan(raw_u16, raw_format, raw_width, (3,), temporal_denoise)
             pars = self._stage_params(raw_u16.size(0))
-            out, self.last_serve_route = serve(self.all_modules, pars, raw_u16, white_level, reverse_channels, out,
-                                                    black_level, cfa, fast_scene, fast_denoise, fast_cond, sharpen=sharpen,
-                                                    out_format=out_format, yuv_matrix=yuv_matrix, out_size=out_size,
-                                                    out_window=out_window, resample=resample, raw_format=raw_format,
-                                                    temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width, lens_shading=lens_shading,
-                                                    defect_correction=defect_correction, fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
-            self.last_serve_store = None if out_format == 'bgr8' else (
-                'fused' if self.last_serve_route in ('fused', 'classical') else 'pass')
-            self.last_serve_warp = None
-            if warp is not None:
-                self.last_serve_warp = 'pass'
-                if out_format != 'bgr8':
-                    self.last_serve_store = 'pass'      # the route served BGR for the warp launch
-            self.last_serve_resize = None
-            if out_size is not None or out_window is not None:
-                self.last_serve_resize = 'pass'
-                if out_format != 'bgr8':
-                    self.last_serve_store = 'resize' if resize_store(out_format) == 'fused' else 'pass'
-            self.last_serve_sharpen = None
-            if sharpen is not None:
-                self.last_serve_sharpen = 'pass'
-                if out_format != 'bgr8':                # the stages in front of the sharpen launch stored BGR
-                    self.last_serve_store = 'sharpen' if sharpen_store(out_format) == 'fused' else 'pass'
-            self.last_serve_load = serve_load(self.last_serve_route, raw_format)
-            self.last_serve_shade = None
-            if lens_shading is not None:
-                self.last_serve_shade = serve_shade(self.last_serve_route, raw_format) if raw_u16.data_ptr() % 8 == 0 else 'pass'
-                if self.last_serve_load is not None:
-                    self.last_serve_load = 'pass'
-            self.last_serve_defect = None
-            if defect_correction is not None:
-                self.last_serve_defect = defect_shade(raw_format) if lens_shading is not None else 'pass'
-                if self.last_serve_load is not None:
-                    self.last_serve_load = 'pass'
-                if lens_shading is not None:
-                    self.last_serve_shade = 'pass'
-            self.last_serve_stats = None
-            if statistics is not None:
-                self.last_serve_stats = 'pass'
-                if lens_shading is not None:
-                    self.last_serve_shade = 'pass'
-            self.last_serve_temporal = None
-            if temporal_denoise is not None:
-                self.last_serve_temporal = 'pass'
-                if self.last_serve_load is not None:
-                    self.last_serve_load = 'pass'
-                if lens_shading is not None:
-                    self.last_serve_shade = 'pass'
+            out, report = serve_reported(self.all_modules, pars, raw_u16, white_level, reverse_channels, out, black_level, cfa,
+                                         fast_scene, fast_denoise, fast_cond, sharpen=sharpen, out_format=out_format,
+                                         yuv_matrix=yuv_matrix, out_size=out_size, out_window=out_window, resample=resample,
+                                         raw_format=raw_format, temporal_denoise=temporal_denoise, statistics=statistics, warp=warp,
+                                         raw_width=raw_width, lens_shading=lens_shading, defect_correction=defect_correction,
+                                         fast_median=fast_median, fast_denoise_scene=fast_denoise_scene)
+            self._record(report)
         return out
 
     def serve_frame(self, raw_u16, white_level, patch_size, patch_stride, tile_batch=16, reverse_channels=False, out=None,
@@ -309,30 +264,18 @@ class _FixedPipeline(nn.Module):
         passed by name): one ``risp_bgr8_sharpen`` launch behind the last frame, the warp and the resize sharpens the image as
         returned, in front of the NV12 conversion (``last_serve_sharpen`` 'pass', ``last_serve_store`` as there)."""
         with torch.no_grad():
-            out = serve_frame(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride, tile_batch,
-                              reverse_channels, out, black_level, cfa, out_format, yuv_matrix, sharpen, out_size=out_size,
-                              out_window=out_window, resample=resample, raw_format=raw_format,
-                              temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
-            self.last_serve_route = 'tiled'
-            self.last_serve_stats = None if statistics is None else 'pass'
-            self.last_serve_temporal = None if temporal_denoise is None else 'pass'
-            self.last_serve_load = serve_load('tiled', raw_format)
-            self.last_serve_shade = None if lens_shading is None else serve_shade('tiled', raw_format)
-            self.last_serve_defect = None if defect_correction is None else (
-                defect_shade(raw_format) if lens_shading is not None else 'pass')
-            self.last_serve_store = None if out_format == 'bgr8' else 'pass'
-            self.last_serve_warp = None if warp is None else 'pass'
-            self.last_serve_resize = None
-            if out_size is not None or out_window is not None:
-                self.last_serve_resize = 'pass'
-                if out_format != 'bgr8':
-                    self.last_serve_store = 'resize' if resize_store(out_format) == 'fused' else 'pass'
-            self.last_serve_sharpen = None
-            if sharpen is not None:
-                self.last_serve_sharpen = 'pass'
-                if out_format != 'bgr8':
-                    self.last_serve_store = 'sharpen' if sharpen_store(out_format) == 'fused' else 'pass'
+            out, report = serve_frame_reported(self.all_modules, self._stage_params, raw_u16, white_level, patch_size, patch_stride,
+                                               tile_batch, reverse_channels, out, black_level, cfa, out_format, yuv_matrix, sharpen,
+                                               out_size=out_size, out_window=out_window, resample=resample, raw_format=raw_format,
+                                               temporal_denoise=temporal_denoise, statistics=statistics, warp=warp,
+                                               raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)
+            self._record(report)
         return out
+
+    def _record(self, report):
+        """what the serving call recorded about itself (``pipeline_fusion.SERVE_REPORT``) -> ``last_serve_*``"""
+        # (strings and None: ten trips through Module.__setattr__'s parameter and sub-module checks cost a warm call microseconds)
+        self.__dict__.update(('last_serve_' + key, value) for key, value in report.items())
 
     @property
     def trainable_parameters(self):

@@ -179,17 +179,26 @@ _CLASSICAL_DEMOSAIC = {T.DemosaicNearest: 'nearest', T.OriginDemosBilinear: 'bil
 _TONE_OP = {T.OriginToneCrysis: F.OP_TONE_CRYSIS, T.OriginToneFilmic: F.OP_TONE_FILMIC}
 
 
+def _classical_head(modules):
+    """(demosaic kind, indices of the stages behind it) when the pipeline, Skips stripped, opens with DemosaicNearest /
+    OriginDemosBilinear / OriginDemosLaplacian; None otherwise"""
+    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
+    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+        return None
+    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], idx[1:]
+
+
 def _classical_split(modules):
     """(demosaic kind, indices of the stages) when the pipeline, Skips stripped, is DemosaicNearest / OriginDemosBilinear /
     OriginDemosLaplacian -> at most MAX_CHAIN stages, each an element-wise one, OriginToneCrysis or OriginToneFilmic; None
     otherwise."""
-    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
-    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+    head = _classical_head(modules)
+    if head is None:
         return None
-    rest = idx[1:]
+    kind, rest = head
     if len(rest) > MAX_CHAIN or any(type(modules[k]) not in _CHAIN_OP and type(modules[k]) not in _TONE_OP for k in rest):
         return None
-    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], rest
+    return kind, rest
 
 
 def serve_route(modules):
@@ -220,6 +229,13 @@ def _tone_block(mod, par):
     return cached[1]
 
 
+def _stage_op(mod, par):
+    """(op code, parameter block) of an element-wise, Crysis or Filmic stage as the serving launches take it"""
+    if type(mod) in _TONE_OP:
+        return _TONE_OP[type(mod)], _tone_block(mod, par)
+    return _CHAIN_OP[type(mod)], _chain_param(mod, par)
+
+
 _SCENE_STAT = {T.Grayworld: F.SCENE_MEAN3, T.OriginWbWhiteworld: F.SCENE_MAX3, T.OriginToneReinhard: F.SCENE_LOGLUM}
 _SCENE_OP = {T.Grayworld: F.OP_GAIN3, T.OriginWbWhiteworld: F.OP_GAIN3_Q8, T.OriginToneReinhard: F.OP_TONE_REINHARD}
 
@@ -230,17 +246,17 @@ def scene_plan(modules):
     Malvar-He-Cutler demosaic followed by at most MAX_CHAIN stages, each an element-wise one, a classical Crysis / Filmic
     tone curve or one of the scene stages Grayworld, OriginWbWhiteworld, OriginToneReinhard, with one or two scene stages
     among them.  None otherwise - without a scene stage ``serve_route`` already names a one-launch route."""
-    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
-    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+    head = _classical_head(modules)
+    if head is None:
         return None
-    rest = idx[1:]
+    kind, rest = head
     kinds = [type(modules[k]) for k in rest]
     if len(rest) > MAX_CHAIN or any(t not in _CHAIN_OP and t not in _TONE_OP and t not in _SCENE_STAT for t in kinds):
         return None
     scene = [t in _SCENE_STAT for t in kinds]
     if not 1 <= sum(scene) <= 2:
         return None
-    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], rest, scene
+    return kind, rest, scene
 
 
 def _scene_vectors(mod, par):
@@ -273,12 +289,10 @@ def _serve_scene(plan, modules, param_tensors, raw_u16, divisor, reverse_channel
             params.append(F.serve_scene_finish(_SCENE_STAT[t], parts, h * w, a, b, None, tag=s))
             ops.append(_SCENE_OP[t])
             s += 1
-        elif t in _TONE_OP:
-            ops.append(_TONE_OP[t])
-            params.append(_tone_block(mod, par))
         else:
-            ops.append(_CHAIN_OP[t])
-            params.append(_chain_param(mod, par))
+            op, block = _stage_op(mod, par)
+            ops.append(op)
+            params.append(block)
     return F.serve_scene_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa)
 
 
@@ -292,17 +306,17 @@ def cond_plan(modules):
     curve or one of the heads ConditionalGamma, ConditionalWbManual, ConditionalWbQuadratic, with one to MAX_COND_HEADS heads
     among them.  None otherwise: without a head ``serve_route`` already names a one-launch route; a scene stage, a classical
     denoiser or BM3D, a CNN stage or a proxy demosaic beside a head keeps the list where it is today."""
-    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
-    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+    head = _classical_head(modules)
+    if head is None:
         return None
-    rest = idx[1:]
+    kind, rest = head
     kinds = [type(modules[k]) for k in rest]
     if len(rest) > MAX_CHAIN or any(t not in _CHAIN_OP and t not in _TONE_OP and t not in _COND_OP for t in kinds):
         return None
     heads = [t in _COND_OP for t in kinds]
     if not 1 <= sum(heads) <= MAX_COND_HEADS:
         return None
-    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], rest, heads
+    return kind, rest, heads
 
 
 def _cond_heads_ok(plan, modules, param_tensors):
@@ -333,12 +347,10 @@ def _serve_cond(plan, modules, param_tensors, raw_u16, divisor, reverse_channels
             params.append(F.serve_cond_finish(counts, par.detach(), mod.in_out_channels, _COND_OP[t][1], None, tag=s))
             ops.append(_COND_OP[t][0])
             s += 1
-        elif t in _TONE_OP:
-            ops.append(_TONE_OP[t])
-            params.append(_tone_block(mod, par))
         else:
-            ops.append(_CHAIN_OP[t])
-            params.append(_chain_param(mod, par))
+            op, block = _stage_op(mod, par)
+            ops.append(op)
+            params.append(block)
     return F.serve_classical_u8(raw_u16, divisor, kind, ops, params, reverse_channels, out, black_level, cfa)
 
 
@@ -355,17 +367,17 @@ def denoise_plan(modules):
     the learned parameters give the sizes the route serves (3 / 3 / (3, 3)) is known only from them: ``serve`` checks it."""
     if _serve_split(modules) is not None:
         return None
-    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
-    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+    head = _classical_head(modules)
+    if head is None:
         return None
-    rest = idx[1:]
+    kind, rest = head
     den = [k for k in rest if type(modules[k]) in _DENOISER]
     if len(den) != 1:
         return None
     stages = [k for k in rest if k != den[0]]
     if len(stages) > MAX_CHAIN or any(type(modules[k]) not in _CHAIN_OP and type(modules[k]) not in _TONE_OP for k in stages):
         return None
-    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], [k for k in stages if k < den[0]], den[0], [k for k in stages if k > den[0]]
+    return kind, [k for k in stages if k < den[0]], den[0], [k for k in stages if k > den[0]]
 
 
 def _denoise_args(mod, par):
@@ -408,10 +420,8 @@ def _median_args(mod, par):
 
 def _stage_lists(modules, param_tensors, stages):
     """(op codes, parameter blocks) of element-wise / Crysis / Filmic stages as the classical and the denoise launch take them"""
-    ops =[_TONE_OP.get(type(modules[k])) or _CHAIN_OP[type(modules[k])] for k in stages]
-    params = [_tone_block(modules[k], param_tensors[k]) if type(modules[k]) in _TONE_OP
-              else _chain_param(modules[k], param_tensors[k]) for k in stages]
-    return ops, params
+    pairs = [_stage_op(modules[k], param_tensors[k]) for k in stages]
+    return [op for op, _ in pairs], [block for _, block in pairs]
 
 
 _DENOISE_SCENE_STAT = {T.Grayworld: F.SCENE_MEAN3, T.OriginWbWhiteworld: F.SCENE_MAX3}
@@ -434,10 +444,10 @@ def denoise_scene_plan(modules):
     conditional heads - and lists without a scene stage (``denoise_plan``'s) or without a denoiser (``scene_plan``'s), so the
     plan is disjoint from every other.  None as well for non-local means with a scene stage behind it, which was measured
     slower than the default call at 64 x 256 x 256 (``_DENOISE_SCENE_SLOWER``); the kernels serve it all the same."""
-    idx = [k for k, m in enumerate(modules) if type(m) is not T.Skip]
-    if not idx or type(modules[idx[0]]) not in _CLASSICAL_DEMOSAIC:
+    head = _classical_head(modules)
+    if head is None:
         return None
-    rest = idx[1:]
+    kind, rest = head
     den = [k for k in rest if type(modules[k]) in _DENOISER]
     if len(den) != 1:
         return None
@@ -452,7 +462,7 @@ def denoise_scene_plan(modules):
     where = 'both' if len(sides) == 2 else ('front' if True in sides else 'behind')
     if (_DENOISER[type(modules[den[0]])], where) in _DENOISE_SCENE_SLOWER:
         return None
-    return _CLASSICAL_DEMOSAIC[type(modules[idx[0]])], stages, den[0], scene
+    return kind, stages, den[0], scene
 
 
 def _serve_denoise_scene(plan, den_args, modules, param_tensors, raw_u16, divisor, reverse_channels, out, black_level, cfa):
@@ -477,12 +487,10 @@ def _serve_denoise_scene(plan, den_args, modules, param_tensors, raw_u16, diviso
             params.append(F.serve_scene_finish(stat, parts, h * w, a, b, None, tag=s))
             ops.append(_SCENE_OP[t])
             s += 1
-        elif t in _TONE_OP:
-            ops.append(_TONE_OP[t])
-            params.append(_tone_block(mod, par))
         else:
-            ops.append(_CHAIN_OP[t])
-            params.append(_chain_param(mod, par))
+            op, block = _stage_op(mod, par)
+            ops.append(op)
+            params.append(block)
     return F.serve_denoise_scene_u8(raw_u16, divisor, kind, pre[0], pre[1], den_args[0], den_args[1], post[0], post[1],
                                     reverse_channels, out, black_level, cfa)
 
@@ -500,9 +508,25 @@ def _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w):
     return F.nv12_matrix(yuv_matrix)
 
 
-def _nv12_bgr(shape, device):
-    """the packed BGR image a route without a fused NV12 store serves into, kept per (shape, device, stream)"""
-    return F._scene_buffer(device, 'nv12_bgr', shape, torch.uint8)
+def _check_black_level(black_level, white_level):
+    if black_level != int(black_level) or not 0 <= black_level < white_level:
+        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
+
+
+def _frame_shape(raw, raw_format, raw_width, dims, typed=True):
+    """(the shape in front of the frames' own dimensions, H, W) of sensor frames as given, of ``dims`` dimensions: MIPI-packed
+    ones as ``_packed_plan`` checks them, otherwise one sample per element - uint16 where ``typed``; everything else is refused"""
+    names = lambda: ' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims)       # (only a refusal pays for it)
+    shaped = isinstance(raw, torch.Tensor) and raw.dim() in dims
+    if not typed and not shaped:
+        raise ValueError('expected %s frames, got %s' % (names(), tuple(getattr(raw, 'shape', ()))))
+    if raw_format != 'u16':
+        w = _packed_plan(raw, raw_format, raw_width, dims)[1]
+    elif typed and not (shaped and raw.dtype == torch.uint16):
+        raise ValueError('expected %s uint16 frames, got %s %s' % (names(), getattr(raw, 'dtype', type(raw)), tuple(getattr(raw, 'shape', ()))))
+    else:
+        w = raw.shape[-1]
+    return tuple(raw.shape[:-2]), raw.shape[-2], w
 
 
 SERVE_ROUTES = ('fused', 'classical', 'scene', 'denoise', 'denoise_scene', 'cond', 'composed', 'tiled')
@@ -526,6 +550,15 @@ def serve_load(route, raw_format):
     return 'fused' if (route, raw_format) in _FUSED_LOAD else 'pass'
 
 
+def _device_frames(raw, raw_format, raw_width, dims):
+    """``_frame_shape`` of frames that must be on the device: uint16 frames name a missing device first, packed ones bad frames"""
+    if raw_format == 'u16':
+        F._need_gpu(raw, 'raw')
+    shape = _frame_shape(raw, raw_format, raw_width, dims)
+    F._need_gpu(raw, 'raw')
+    return shape
+
+
 def _packed_plan(raw, raw_format, raw_width, dims):
     """``serve`` / ``serve_frame`` on MIPI-packed frames, checked on the host before anything else: (bits, W) for uint8 frames
     of ``dims`` dimensions whose last is the row pitch in bytes; everything else is refused"""
@@ -538,11 +571,6 @@ def _packed_plan(raw, raw_format, raw_width, dims):
     if raw.shape[-2] % 2:
         raise ValueError('packed frames of %d rows: H must be even' % raw.shape[-2])
     return bits, w
-
-
-def _packed_u16(shape, device):
-    """the uint16 frames a route without a fused packed load unpacks into, kept per (shape, device, stream)"""
-    return F._scene_buffer(device, 'raw_u16', shape, torch.uint16)
 
 
 # (route, raw_format) whose one launch applies the lens-shading correction in its load.  Only ('classical', 'u16') has such a
@@ -567,12 +595,6 @@ def serve_shade(route, raw_format):
     return 'fused' if (route, raw_format) in _FUSED_SHADE else 'pass'
 
 
-def _shaded_u16(shape, device):
-    """the uint16 frames a route without a fused shading load shades into, kept per (shape, device, stream); not the unpack
-    buffer: a caller may hold that one's frames"""
-    return F._scene_buffer(device, 'shaded_u16', shape, torch.uint16)
-
-
 # raw formats whose defective-pixel correction and lens shading run as ONE risp_raw_defect launch (with gains) instead of
 # risp_raw_defect followed by risp_raw_shade.  A format is listed only if the one launch beats the two by more than the larger
 # spread of the two legs in every measured row of profiles/serve_defect.txt (two sizes per format; DESIGN.md 4.6) - the rule of
@@ -590,28 +612,83 @@ def defect_shade(raw_format):
     return 'fused' if raw_format in _DEFECT_SHADE_FUSED else 'pass'
 
 
-def _defect_u16(shape, device):
-    """the uint16 frames the defective-pixel correction writes, kept per (shape, device, stream); neither the unpack buffer nor
-    the shade buffer: a caller may hold their frames, and the shade launch behind the correction reads these"""
-    return F._scene_buffer(device, 'defect_u16', shape, torch.uint16)
+def _sensor_input(raw, lead, h, w, white_level, black_level, cfa, raw_format, lens_shading, defect, temporal, stats, report):
+    """The sensor side of ``serve`` and ``serve_frame``, in front of the route or the tiles: contiguous device frames of
+    ``lead`` + (H, W) samples, uint16 or MIPI-packed ``raw_format``, and the sensor keywords -> (white level, black level,
+    aligned, packed, shade, frames).  The keywords are refused before anything is launched.  Behind a shading the samples have
+    black level 0 and the white level white_level - black_level: the two come back so.
+    ``frames()`` makes the uint16 frames the route reads, once, in buffers kept per (shape, device, stream): ``risp_raw_defect``
+    (shading too, in its own launch or with ``risp_raw_shade`` behind it: ``defect_shade``) | ``risp_raw_shade`` |
+    ``risp_raw_unpack``, or the uint16 input as given.  Each launch has a buffer of its own - a caller may hold another one's
+    frames, the shade launch behind a correction reads the correction's, and the temporal launch may alias neither its input
+    nor the state.  It is lazy: a route whose one launch loads ``packed`` = (uint8 frames, bits, W, raw_format) or applies
+    ``shade`` = ((gains, cell), the sensor's black level) itself never calls it.  Both are None where nothing behind the
+    pre-pass may see them: a correction or a shade launch decodes, a correction shades, and behind the temporal filter and
+    the statistics of a pre-pass nothing is packed or unshaded any more.
+    ``temporal`` runs here, once, on ``frames()`` - it advances the state - and ``stats`` behind it, on what the route is about
+    to read: the frames of a pre-pass or of the filter, otherwise the input as given, packed or not.
+    ``aligned``: whether what the route reads is 8-byte aligned (the cached buffers are).  ``report`` takes 'load', 'shade',
+    'defect', 'temporal' and 'stats' where their launches are issued."""
+    device, n = raw.device, lead[0] if lead else 1
+    bits = F.raw_format_bits(raw_format) or 16
+    code = F.cfa_code(cfa)
+    _check_black_level(black_level, white_level)
+    F._check_mirror(code, h, w)
+    pre_shade = None
+    if lens_shading is not None:
+        if w % 4:
+            raise ValueError('lens_shading on frames %d wide: W must be a multiple of 4' % w)
+        F.shading_check(lens_shading, h, w, device)
+        pre_shade, white_level, black_level = (lens_shading, int(black_level)), white_level - black_level, 0
+    if defect is not None:
+        F.defect_check(defect, h, w, device)
+    if temporal is not None:                                # an unprimed state under capture is refused too
+        temporal = F.temporal_check(temporal, n, h, w, device)
+        F._temporal_prime(temporal[0], torch.cuda.is_current_stream_capturing())
+    if stats is not None:
+        F.stats_check(stats, n, h, w, device)
+    made = []
 
+    def buffer(tag):
+        return F._scene_buffer(device, tag, lead + (h, w), torch.uint16)
 
-def _corrected(frames, defect, bits, w, raw_format, shade):
-    """the pre-pass of a call with ``defect_correction``: contiguous uint16 or packed ``frames`` -> corrected uint16 frames in the
-    cached buffers, shaded too with ``shade`` = ((gains, cell), black level) - in the same launch where ``defect_shade`` says so"""
-    shape, device = tuple(frames.shape[:-1]) + (w,), frames.device
-    if shade is None:
-        return F.raw_defect(frames, defect, bits, w, out=_defect_u16(shape, device))
-    if defect_shade(raw_format) == 'fused':
-        return F.raw_defect(frames, defect, bits, w, shade[0], shade[1], _defect_u16(shape, device))
-    return F.raw_shade(F.raw_defect(frames, defect, bits, w, out=_defect_u16(shape, device)), shade[0], shade[1], 16, w,
-                       _shaded_u16(shape, device))
+    def make():
+        if bits != 16:
+            report['load'] = 'pass'                         # whichever launch comes first decodes on the way
+        if defect is not None:
+            if pre_shade is None:
+                report['defect'] = 'pass'
+                return F.raw_defect(raw, defect, bits, w, out=buffer('defect_u16'))
+            report['defect'], report['shade'] = defect_shade(raw_format), 'pass'
+            if report['defect'] == 'fused':
+                return F.raw_defect(raw, defect, bits, w, pre_shade[0], pre_shade[1], buffer('defect_u16'))
+            return F.raw_shade(F.raw_defect(raw, defect, bits, w, out=buffer('defect_u16')), pre_shade[0], pre_shade[1], 16, w,
+                               buffer('shaded_u16'))
+        if pre_shade is not None:
+            report['shade'] = 'pass'
+            return F.raw_shade(raw, pre_shade[0], pre_shade[1], bits, w, buffer('shaded_u16'))
+        return raw if bits == 16 else F.raw_unpack(raw, bits, w, buffer('raw_u16'))
 
-
-def _temporal_u16(shape, device):
-    """the uint16 frames the temporal noise reduction writes, kept per (shape, device, stream); none of the pre-passes' buffers:
-    the launch reads theirs, and its output may alias neither its input nor the state"""
-    return F._scene_buffer(device, 'temporal_u16', shape, torch.uint16)
+    def frames():
+        if not made:
+            made.append(make())
+        return made[0]
+    prepass = defect is not None or pre_shade is not None
+    packed = (raw, bits, w, raw_format) if bits != 16 and not prepass else None
+    shade = pre_shade if defect is None else None
+    aligned = prepass or packed is not None or raw.data_ptr() % 8 == 0
+    if temporal is not None:
+        made[:] = [F.raw_temporal(frames(), temporal, black_level, buffer('temporal_u16'))]
+        report['temporal'] = 'pass'
+        packed, shade, aligned = None, None, True
+    if stats is not None:
+        if prepass or temporal is not None:
+            shade = None
+            F.raw_stats(frames(), stats, black_level, 16, w)
+        else:
+            F.raw_stats(raw, stats, black_level, bits, w)
+        report['stats'] = 'pass'
+    return white_level, black_level, aligned, packed, shade, frames
 
 
 def temporal_plan(raw, raw_format, raw_width, dims, temporal_denoise):
@@ -619,14 +696,8 @@ def temporal_plan(raw, raw_format, raw_width, dims, temporal_denoise):
     for an (H,W) frame -, nothing for None: what ``serve_frame`` and the modules' ``serve`` check before their first launch"""
     if temporal_denoise is None:
         return None
-    if raw_format != 'u16':
-        w = _packed_plan(raw, raw_format, raw_width, dims)[1]
-    elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint16 or raw.dim() not in dims:
-        raise ValueError('expected %s uint16 frames, got %s %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
-                                                                   getattr(raw, 'dtype', type(raw)), tuple(getattr(raw, 'shape', ()))))
-    else:
-        w = raw.shape[-1]
-    checked = F.temporal_check(temporal_denoise, 1 if raw.dim() == 2 else raw.shape[0], raw.shape[-2], w, raw.device)
+    lead, h, w = _frame_shape(raw, raw_format, raw_width, dims)
+    checked = F.temporal_check(temporal_denoise, lead[0] if lead else 1, h, w, raw.device)
     F._temporal_prime(checked[0], torch.cuda.is_current_stream_capturing())     # an unprimed state under capture is refused here
     return checked
 
@@ -655,49 +726,6 @@ def resize_store(out_format):
     return 'fused' if out_format in _RESIZE_NV12_FUSED else 'pass'
 
 
-def _resize_bgr(shape, device):
-    """the packed sensor-size image a call with ``out_size`` / ``out_window`` serves into, kept per (shape, device, stream);
-    not the NV12 route's image: the conversion launch behind a resize reads that one at the output's size"""
-    return F._scene_buffer(device, 'resize_bgr', shape, torch.uint8)
-
-
-def _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, lead, device):
-    """a call with ``out_size`` / ``out_window``, checked on the host before anything is launched: (size, window, the twelve
-    integers or None); ``lead`` is the shape in front of the image's own dimensions"""
-    size, win = F.resize_check(out_size, out_window, resample, h, w, out_format == 'nv12')
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, size[0], size[1])
-    if out is not None:
-        shape, align = ((size[0], size[1], 3), 1) if coef is None else ((size[0] + size[0] // 2, size[1]),
-                                                                         4 if resize_store('nv12') == 'fused' else 1)
-        F._u8_out(out, tuple(lead) + shape, device, align)
-    return size, win, coef
-
-
-def resize_plan(raw, raw_format, raw_width, dims, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out):
-    """``_resize_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keywords: what
-    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
-    if out_size is None and out_window is None:
-        return None
-    if not isinstance(raw, torch.Tensor) or raw.dim() not in dims:
-        raise ValueError('expected %s frames, got %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
-                                                        tuple(getattr(raw, 'shape', ()))))
-    w = raw.shape[-1] if raw_format == 'u16' else _packed_plan(raw, raw_format, raw_width, dims)[1]
-    return _resize_plan(out_size, out_window, resample, raw.shape[-2], w, out_format, yuv_matrix, reverse_channels, out,
-                        tuple(raw.shape[:-2]), raw.device)
-
-
-def _resized(img, plan, resample, out):
-    """the end of a call with ``out_size`` / ``out_window``: the served packed image -> ``out`` through ``risp_bgr8_resize``,
-    which stores NV12 itself where ``resize_store`` says so; otherwise the conversion launch follows it"""
-    size, win, coef = plan
-    if coef is None:
-        return F.bgr8_resize(img, size, win, resample, out=out)
-    if resize_store('nv12') == 'fused':
-        return F.bgr8_resize(img, size, win, resample, coef, 'bgr', out)
-    bgr = F.bgr8_resize(img, size, win, resample, out=_nv12_bgr(tuple(img.shape[:-3]) + (size[0], size[1], 3), img.device))
-    return F.bgr8_to_nv12(bgr, coef, 'bgr', out)
-
-
 # warp kernels whose launch stages the source box of a tile in LDS (risp_bgr8_warp with stage = 1) instead of sampling global
 # memory from every tile (stage = 0).  A kernel is listed only if stage = 1 beats stage = 0 by more than the larger spread of the
 # two legs in every measured row of that kernel in profiles/serve_warp.txt (two sizes x identity, a 2-degree rotation and a radial
@@ -717,52 +745,6 @@ def warp_stage(kernel):
     if kernel not in F.WARP_KERNELS:
         raise ValueError('unknown warp kernel %r: one of %s' % (kernel, ', '.join(F.WARP_KERNELS)))
     return 'lds' if kernel in _WARP_STAGED else 'gather'
-
-
-def _warp_bgr(shape, device):
-    """the packed sensor-size image a call with ``warp`` serves into, kept per (shape, device, stream); neither the resize's
-    nor the NV12 route's image: the launches behind the warp read those at the warp's size, which may be the sensor's"""
-    return F._scene_buffer(device, 'warp_bgr', shape, torch.uint8)
-
-
-def _warp_plan(warp, h, w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, lead, device):
-    """a call with ``warp``, checked on the host before anything is launched: (the checked warp, the resize plan of the warped
-    image or None, the twelve integers of an NV12 store without a resize or None); ``lead`` is the shape in front of the
-    image's own dimensions"""
-    wp = F.warp_check(warp, h, w, device, out_format == 'nv12')
-    wh, ww = wp[2]
-    if out_size is not None or out_window is not None:
-        return wp, _resize_plan(out_size, out_window, resample, wh, ww, out_format, yuv_matrix, reverse_channels, out, lead, device), None
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, wh, ww)
-    if out is not None:
-        F._u8_out(out, tuple(lead) + ((wh, ww, 3) if coef is None else (wh + wh // 2, ww)), device, 1)
-    return wp, None, coef
-
-
-def warp_plan(raw, raw_format, raw_width, dims, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out):
-    """``_warp_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keyword: what
-    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
-    if warp is None:
-        return None
-    if not isinstance(raw, torch.Tensor) or raw.dim() not in dims:
-        raise ValueError('expected %s frames, got %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
-                                                        tuple(getattr(raw, 'shape', ()))))
-    w = raw.shape[-1] if raw_format == 'u16' else _packed_plan(raw, raw_format, raw_width, dims)[1]
-    return _warp_plan(warp, raw.shape[-2], w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out,
-                      tuple(raw.shape[:-2]), raw.device)
-
-
-def _warped(img, plan, warp, resample, out):
-    """the end of a call with ``warp``: the served packed image -> ONE ``risp_bgr8_warp`` launch (``warp_stage`` picks its
-    form) into ``out``, into the resize's source image where ``out_size`` / ``out_window`` follow, or into the NV12
-    conversion's source image"""
-    wp, rplan, coef = plan
-    shape = tuple(img.shape[:-3]) + (wp[2][0], wp[2][1], 3)
-    if rplan is not None:
-        return _resized(F.bgr8_warp(img, warp, out=_resize_bgr(shape, img.device)), rplan, resample, out)
-    if coef is not None:
-        return F.bgr8_to_nv12(F.bgr8_warp(img, warp, out=_nv12_bgr(shape, img.device)), coef, 'bgr', out)
-    return F.bgr8_warp(img, warp, out=out)
 
 
 # output formats a sharpened call stores from the sharpen launch itself (risp_bgr8_sharpen with the matrix) instead of sharpening
@@ -788,68 +770,89 @@ def sharpen_store(out_format):
     return 'fused' if out_format in _SHARPEN_NV12_FUSED else 'pass'
 
 
-def _sharpen_bgr(shape, device):
-    """the packed image a call with ``sharpen`` puts in front of the sharpen launch, kept per (shape, device, stream); not the
-    warp's, the resize's or the NV12 route's image, whose shapes can coincide with it: the stages around the launch use those"""
-    return F._scene_buffer(device, 'sharpen_bgr', shape, torch.uint8)
-
-
-def _sharpen_plan(sharpen, h, w, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, lead, device):
-    """a call with ``sharpen``, checked on the host before anything is launched: (the checked tuple, the warp's plan or None,
-    the resize's plan where no warp is given or None, the twelve integers of an NV12 store or None, the size of the image as
-    returned).  The stages in front of the launch are planned for packed BGR; ``lead`` is the shape in front of the image's own
-    dimensions"""
-    F.sharpen_check(sharpen, out_format == 'nv12')
-    wplan = rplan = None
-    fh, fw = h, w
-    if warp is not None:
-        wplan = _warp_plan(warp, h, w, out_size, out_window, resample, 'bgr8', yuv_matrix, False, None, lead, device)
-        fh, fw = wplan[0][2] if wplan[1] is None else wplan[1][0]
-    elif out_size is not None or out_window is not None:
-        rplan = _resize_plan(out_size, out_window, resample, h, w, 'bgr8', yuv_matrix, False, None, lead, device)
-        fh, fw = rplan[0]
-    sp = F.sharpen_check(sharpen, out_format == 'nv12', fh, fw)
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, fh, fw)
-    if out is not None:
-        F._u8_out(out, tuple(lead) + ((fh, fw, 3) if coef is None else (fh + fh // 2, fw)), device, 1)
-    return sp, wplan, rplan, coef, (fh, fw)
-
-
-def sharpen_plan(raw, raw_format, raw_width, dims, sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix,
-                 reverse_channels, out):
-    """``_sharpen_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keyword: what
-    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
-    if sharpen is None:
+def _output_plan(h, w, lead, device, sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out):
+    """The output side of a call on H x W frames - ``warp`` -> ``out_size`` / ``out_window`` -> ``sharpen`` -> the NV12 store -,
+    checked on the host before anything is launched: None without the four keywords, otherwise (steps, the twelve integers of
+    an NV12 store or None, the size (FH, FW) of the image as returned, who stores NV12).  A step is (name - 'warp' | 'resize' |
+    'sharpen' -, its checked arguments, the size of its input image), in pipeline order: the image size walks from the
+    sensor's through the warp's to the resize's.  Who stores: None for 'bgr8', the last step's name where that launch stores
+    NV12 itself (``resize_store``, ``sharpen_store``; the warp has no such store), 'pass' where ``risp_bgr8_to_nv12`` follows.
+    The stages in front of a sharpen launch are planned for packed BGR; without one the warp is planned for NV12 even where a
+    resize follows it.  ``out`` is checked against the final shape with the alignment the storing launch needs; ``lead`` is the
+    shape in front of the image's own dimensions"""
+    resize = out_size is not None or out_window is not None
+    if sharpen is None and warp is None and not resize:
         return None
-    F.sharpen_check(sharpen, out_format == 'nv12')
-    if not isinstance(raw, torch.Tensor) or raw.dim() not in dims:
-        raise ValueError('expected %s frames, got %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
-                                                        tuple(getattr(raw, 'shape', ()))))
-    w = raw.shape[-1] if raw_format == 'u16' else _packed_plan(raw, raw_format, raw_width, dims)[1]
-    return _sharpen_plan(sharpen, raw.shape[-2], w, warp, out_size, out_window, resample, out_format, yuv_matrix,
-                         reverse_channels, out, tuple(raw.shape[:-2]), raw.device)
+    nv12 = out_format == 'nv12'
+    if sharpen is not None:
+        F.sharpen_check(sharpen, nv12)
+    steps = []
+    if warp is not None:
+        size = F.warp_check(warp, h, w, device, nv12 and sharpen is None)[2]
+        steps.append(('warp', warp, (h, w)))
+        h, w = size
+    if resize:
+        size, win = F.resize_check(out_size, out_window, resample, h, w, nv12 and sharpen is None)
+        steps.append(('resize', (size, win), (h, w)))
+        h, w = size
+    if sharpen is not None:
+        steps.append(('sharpen', F.sharpen_check(sharpen, nv12, h, w), (h, w)))
+    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
+    last = steps[-1][0]
+    fused = coef is not None and last != 'warp' and (resize_store if last == 'resize' else sharpen_store)('nv12') == 'fused'
+    store = None if coef is None else (last if fused else 'pass')
+    if out is not None:
+        F._u8_out(out, tuple(lead) + ((h, w, 3) if coef is None else (h + h // 2, w)), device, 4 if store == 'resize' else 1)
+    return steps, coef, (h, w), store
 
 
-def _sharpen_source(warp, out_size, out_window):
-    """the cached image the route of a call with ``sharpen`` serves into: that of the first stage behind the route"""
-    return _warp_bgr if warp is not None else (_resize_bgr if out_size is not None or out_window is not None else _sharpen_bgr)
+def output_plan(raw, raw_format, raw_width, dims, sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix,
+                reverse_channels, out):
+    """``_output_plan`` from the frames as given - uint16 or packed, of ``dims`` dimensions -, None without the keywords: what
+    ``serve_frame`` and the modules' ``serve`` check before their first launch"""
+    if sharpen is None and warp is None and out_size is None and out_window is None:
+        return None
+    if sharpen is not None:
+        F.sharpen_check(sharpen, out_format == 'nv12')
+    lead, h, w = _frame_shape(raw, raw_format, raw_width, dims, False)
+    return _output_plan(h, w, lead, raw.device, sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix,
+                        reverse_channels, out)
 
 
-def _sharpened(img, plan, warp, resample, reverse_channels, out):
-    """the end of a call with ``sharpen``: the served packed image -> the warp and / or the resize launch where asked for, into
-    ``_sharpen_bgr`` -> ONE ``risp_bgr8_sharpen`` launch into ``out``; with NV12 that launch stores NV12 itself where
-    ``sharpen_store`` says so, otherwise it writes the NV12 conversion's source image and ``risp_bgr8_to_nv12`` follows"""
-    sp, wplan, rplan, coef, (fh, fw) = plan
-    shape = tuple(img.shape[:-3]) + (fh, fw, 3)
-    if wplan is not None:
-        img = _warped(img, wplan, warp, resample, _sharpen_bgr(shape, img.device))
-    elif rplan is not None:
-        img = _resized(img, rplan, resample, _sharpen_bgr(shape, img.device))
-    if coef is None:
-        return F.bgr8_sharpen(img, sp, None, 'rgb' if reverse_channels else 'bgr', out)
-    if sharpen_store('nv12') == 'fused':
-        return F.bgr8_sharpen(img, sp, coef, 'bgr', out)
-    return F.bgr8_to_nv12(F.bgr8_sharpen(img, sp, out=_nv12_bgr(shape, img.device)), coef, 'bgr', out)
+def _source_image(name, size, lead, device):
+    """the cached packed image of ``size`` the launch ``name`` reads, kept per (shape, device, stream).  Every stage has an image of its
+    own, and so has the NV12 conversion ('nv12_bgr'): their shapes can coincide - a warp may keep the sensor's size, a resize
+    the warp's -, and a launch must not read the image it writes"""
+    return F._scene_buffer(device, name + '_bgr', tuple(lead) + tuple(size) + (3,), torch.uint8)
+
+
+def _deliver(img, plan, resample, reverse_channels, out, report):
+    """The end of a call with an output plan: the packed BGR image served into the first step's source image -> one launch per
+    step - ``risp_bgr8_warp`` (``warp_stage`` picks its form), ``risp_bgr8_resize``, ``risp_bgr8_sharpen`` (told the channel
+    order) -, each into the next step's source image and the last one into ``out``.  With NV12 the last launch stores NV12
+    itself where the plan says so; otherwise it writes the conversion's source image and ``risp_bgr8_to_nv12`` follows.
+    ``report`` takes the steps and 'store' as the launches are issued"""
+    steps, coef, final, store = plan
+    lead, device = tuple(img.shape[:-3]), img.device
+    for k, (name, args, _) in enumerate(steps):
+        nv12 = None
+        if k + 1 < len(steps):
+            dst = _source_image(steps[k + 1][0], steps[k + 1][2], lead, device)
+        elif coef is None:
+            dst = out
+        elif store == 'pass':
+            dst = _source_image('nv12', final, lead, device)
+        else:
+            dst, nv12 = out, coef
+        if name == 'warp':
+            img = F.bgr8_warp(img, args, out=dst)
+        elif name == 'resize':
+            img = F.bgr8_resize(img, args[0], args[1], resample, nv12, 'bgr', dst)
+        else:
+            img = F.bgr8_sharpen(img, args, nv12, 'rgb' if reverse_channels else 'bgr', dst)
+        report[name] = 'pass'
+    report['store'] = store
+    return F.bgr8_to_nv12(img, coef, 'bgr', out) if store == 'pass' else img
 
 
 def stats_plan(raw, raw_format, raw_width, dims, statistics):
@@ -860,15 +863,9 @@ def stats_plan(raw, raw_format, raw_width, dims, statistics):
     if not isinstance(statistics, F.RawStatistics):
         raise ValueError('statistics must be a RawStatistics (functional.raw_statistics builds one), got %s'
                          % (type(statistics).__name__,))
-    if raw_format != 'u16':
-        w = _packed_plan(raw, raw_format, raw_width, dims)[1]
-    elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint16 or raw.dim() not in dims:
-        raise ValueError('expected %s uint16 frames, got %s %s' % (' or '.join('(N,H,W)' if d == 3 else '(H,W)' for d in dims),
-                                                                   getattr(raw, 'dtype', type(raw)), tuple(getattr(raw, 'shape', ()))))
-    else:
-        w = raw.shape[-1]
+    lead, h, w = _frame_shape(raw, raw_format, raw_width, dims)
     F._need_gpu(raw, 'raw')
-    return F.stats_check(statistics, 1 if raw.dim() == 2 else raw.shape[0], raw.shape[-2], w, raw.device)
+    return F.stats_check(statistics, lead[0] if lead else 1, h, w, raw.device)
 
 
 def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
@@ -1049,156 +1046,72 @@ def serve(modules, param_tensors, raw_u16, white_level, reverse_channels=False, 
     ``sharpen``, ``out_format``, ``yuv_matrix``, ``out_size``, ``out_window``, ``resample``, ``raw_format``, ``temporal_denoise``, ``statistics``, ``warp``, ``raw_width``, ``lens_shading``, ``defect_correction`` and ``fast_median`` are keyword-only, and so is
     ``fast_denoise_scene``: it stays the last parameter (tests/test_serve_denoise_scene_plan_cpu.py holds every ``serve`` to that), the positional list in
     front of it is unchanged."""
-    packed = None
-    if raw_format != 'u16':
-        bits, w = _packed_plan(raw_u16, raw_format, raw_width, (3,))
-        F._need_gpu(raw_u16, 'raw')
-        raw_u16 = raw_u16.contiguous()
-        packed = (raw_u16, bits, w, raw_format)
-        n, h = raw_u16.shape[:2]
-    else:
-        F._need_gpu(raw_u16, 'raw')
-        if raw_u16.dtype != torch.uint16 or raw_u16.dim() != 3:
-            raise ValueError('expected (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    code = F.cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level < white_level:
-        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-    if packed is None:
-        raw_u16 = raw_u16.contiguous()
-        n, h, w = raw_u16.shape
-    F._check_mirror(code, h, w)
-    divisor = white_level - black_level
-    shade = None
-    if lens_shading is not None:
-        if w % 4:
-            raise ValueError('lens_shading on frames %d wide: W must be a multiple of 4' % w)
-        F.shading_check(lens_shading, h, w, raw_u16.device)
-        # behind the shading the samples have black level 0 and the white level white_level - black_level
-        shade, white_level, black_level = (lens_shading, int(black_level)), divisor, 0
-    defect = defect_correction
-    if defect is not None:
-        F.defect_check(defect, h, w, raw_u16.device)        # refused before anything is launched
-    temporal = temporal_denoise
-    if temporal is not None:                                # refused before anything is launched, an unprimed state under capture too
-        temporal = F.temporal_check(temporal, n, h, w, raw_u16.device)
-        F._temporal_prime(temporal[0], torch.cuda.is_current_stream_capturing())
-    stats = statistics
-    if stats is not None:
-        F.stats_check(stats, n, h, w, raw_u16.device)       # refused before anything is launched
-    if sharpen is not None:
-        plan = _sharpen_plan(sharpen, h, w, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out,
-                             (n,), raw_u16.device)          # refused before anything is launched
-        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
-                                   _sharpen_source(warp, out_size, out_window)((n, h, w, 3), raw_u16.device), black_level, cfa,
-                                   fast_scene, fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median,
-                                   shade=shade, defect=defect, stats=stats, temporal=temporal)
-        return _sharpened(img, plan, warp, resample, reverse_channels, out), route
-    if warp is not None:
-        plan = _warp_plan(warp, h, w, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels, out, (n,),
-                          raw_u16.device)                   # refused before anything is launched
-        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
-                                   _warp_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
-                                   fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect,
-                                   stats=stats, temporal=temporal)
-        return _warped(img, plan, warp, resample, out), route
-    if out_size is not None or out_window is not None:
-        plan = _resize_plan(out_size, out_window, resample, h, w, out_format, yuv_matrix, reverse_channels, out, (n,),
-                            raw_u16.device)                 # refused before anything is launched
-        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels,
-                                   _resize_bgr((n, h, w, 3), raw_u16.device), black_level, cfa, fast_scene, fast_denoise, fast_cond,
-                                   fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade, defect=defect,
-                                   stats=stats, temporal=temporal)
-        return _resized(img, plan, resample, out), route
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
-    if coef is not None:
-        if out is not None:
-            F._u8_out(out, (n, h + h // 2, w), raw_u16.device, 1)      # refused before anything is launched
-        img, route = _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, False, None, black_level, cfa, fast_scene,
-                                fast_denoise, fast_cond, fast_denoise_scene, coef, out, packed, fast_median, shade, defect, stats,
-                                temporal)
-        return (img if route in ('fused', 'classical') else F.bgr8_to_nv12(img, coef, 'bgr', out)), route
-    return _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-                      fast_denoise, fast_cond, fast_denoise_scene, packed=packed, fast_median=fast_median, shade=shade,
-                      defect=defect, stats=stats, temporal=temporal)
+    img, report = serve_reported(modules, param_tensors, raw_u16, white_level, reverse_channels, out, black_level, cfa, fast_scene,
+                                 fast_denoise, fast_cond, sharpen=sharpen, out_format=out_format, yuv_matrix=yuv_matrix,
+                                 out_size=out_size, out_window=out_window, resample=resample, raw_format=raw_format,
+                                 temporal_denoise=temporal_denoise, statistics=statistics, warp=warp, raw_width=raw_width,
+                                 lens_shading=lens_shading, defect_correction=defect_correction, fast_median=fast_median,
+                                 fast_denoise_scene=fast_denoise_scene)
+    return img, report['route']
 
 
-def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse_channels, out, black_level, cfa, fast_scene,
-               fast_denoise, fast_cond, fast_denoise_scene, coef=None, nv12_out=None, packed=None, fast_median=False, shade=None,
-               defect=None, stats=None, temporal=None):
-    """``serve`` behind its argument checks: the route and its launches.  With ``coef`` (NV12): 'fused' and 'classical' store
-    NV12 into ``nv12_out`` themselves, every other route serves BGR into the cached packed image for the conversion launch.
-    With ``packed`` = (uint8 frames, bits, W, raw_format), ``raw_u16`` being those frames: the route is the one uint16 frames
-    from the allocator take, 'fused' and 'classical' load the packed bytes where ``serve_load`` says so, and every other
-    route runs on ``frames()``, the cached uint16 stack the unpack launch fills.
-    With ``shade`` = ((gains, cell), the sensor's black level), ``black_level`` being 0 and ``white_level`` the divisor: the
-    route is again the one uint16 frames from the allocator take, 'classical' shades in its load where ``serve_shade`` says so
-    (uint16 input, 8-byte aligned), and every other route runs on ``frames()``, the cached uint16 stack the shade launch fills
-    from the uint16 or the packed frames.
-    With ``defect`` = (threshold, slope, defects): the route is once more the one uint16 frames from the allocator take and
-    every route runs on ``frames()``, the cached uint16 stack ``risp_raw_defect`` fills from the uint16 or the packed frames -
-    shaded too with ``shade``, by that launch or by ``risp_raw_shade`` behind it (``defect_shade``); no fused load is taken.
-    With ``stats`` (a checked ``F.RawStatistics``): ``risp_raw_stats`` reads what the route is about to read - behind a pre-pass
-    its cached frames, which are then made first and no fused shading load is taken, otherwise the input as given, packed or
-    not, with ``black_level``; the route is chosen as without it.
-    With ``temporal`` (a checked ``F.temporal_check`` tuple): ``risp_raw_temporal`` runs now, on ``frames()`` as the lines above
-    make them - the pre-pass's frames, the uint16 input, or the unpacked frames -, with ``black_level`` (0 behind a shading), into
-    a cached uint16 stack of its own, and advances the state; every route and the statistics run on that stack, the route being
-    the one uint16 frames from the allocator take, and nothing behind it sees packed bytes or a shading"""
+# what a serving call records about itself, the values ``_FixedPipeline.last_serve_*`` documents: 'route' is a name of
+# SERVE_ROUTES; every other entry is None where its keyword is not given, and otherwise says which launch did the work
+SERVE_REPORT = ('route', 'load', 'shade', 'defect', 'temporal', 'stats', 'warp', 'resize', 'sharpen', 'store')
+
+
+def serve_reported(modules, param_tensors, raw_u16, white_level, reverse_channels=False, out=None, black_level=0, cfa='rggb',
+                   fast_scene=False, fast_denoise=False, fast_cond=False, *, sharpen=None, out_format='bgr8',
+                   yuv_matrix='bt601_full', out_size=None, out_window=None, resample='triangle', raw_format='u16',
+                   temporal_denoise=None, statistics=None, warp=None, raw_width=None, lens_shading=None, defect_correction=None,
+                   fast_median=False, fast_denoise_scene=False):
+    """``serve`` with the record of what ran in place of the route: (image, report), a dict with the keys of ``SERVE_REPORT``,
+    each entry written where the launch that justifies it is issued"""
+    report = dict.fromkeys(SERVE_REPORT)
+    lead, h, w = _device_frames(raw_u16, raw_format, raw_width, (3,))
     device = raw_u16.device
-    if defect is not None:
-        (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
-        fmt, bits = ('u16', 16) if packed is None else (packed[3], packed[1])
-        prepass = shade
-
-        def frames():
-            return _corrected(raw_u16, defect, bits, w, fmt, prepass)
-        packed = shade = None                               # the pre-pass decodes and shades: nothing behind it sees either
-    elif shade is not None:
-        (n, h), w, aligned = raw_u16.shape[:2], (raw_u16.shape[2] if packed is None else packed[2]), True
-        fmt, bits = ('u16', 16) if packed is None else (packed[3], packed[1])
-
-        def frames():
-            return F.raw_shade(raw_u16, shade[0], shade[1], bits, w, _shaded_u16((n, h, w), device))
-        packed = None                                       # the shade launch decodes: nothing behind it sees packed bytes
-    elif packed is None:
-        n, h, w = raw_u16.shape
-        aligned = raw_u16.data_ptr() % 8 == 0
-
-        def frames():
-            return raw_u16
+    plan = _output_plan(h, w, lead, device, sharpen, warp, out_size, out_window, resample, out_format, yuv_matrix, reverse_channels,
+                        out)                                # refused before anything is launched
+    coef, dst = None, out
+    if plan is not None:
+        # the route serves packed BGR at the sensor's size into the source image of the first launch behind it
+        dst = _source_image(plan[0][0][0], (h, w), lead, device)
     else:
-        (n, h), w, aligned = raw_u16.shape[:2], packed[2], True
+        coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, h, w)
+        if coef is not None and out is not None:
+            F._u8_out(out, lead + (h + h // 2, w), device, 1)           # refused before anything is launched
+    img, report['route'] = _serve_routes(modules, param_tensors, raw_u16.contiguous(), lead, h, w, white_level, black_level, cfa,
+                                         raw_format, lens_shading, defect_correction, temporal_denoise, statistics,
+                                         reverse_channels, dst, coef, fast_scene, fast_denoise, fast_median, fast_denoise_scene,
+                                         fast_cond, report)
+    if plan is not None:
+        img = _deliver(img, plan, resample, reverse_channels, out, report)
+    elif coef is not None and report['store'] is None:
+        img, report['store'] = F.bgr8_to_nv12(img, coef, 'bgr', out), 'pass'
+    return img, report
 
-        def frames():
-            return F.raw_unpack(packed[0], packed[1], w, _packed_u16((n, h, w), device))
-    if temporal is not None:
-        # the filter runs now, once: it advances the state.  Behind it nothing sees packed bytes or a shading
-        filtered = F.raw_temporal(frames(), temporal, black_level, _temporal_u16((n, h, w), device))
-        packed, shade, aligned = None, None, True
 
-        def frames():
-            return filtered
-    if stats is not None:
-        if temporal is not None or defect is not None or shade is not None:
-            # the pre-pass runs now and the statistics read its frames; nothing behind it sees a shading (no fused shading load)
-            ready = frames()
-            shade = None
-
-            def frames():
-                return ready
-            F.raw_stats(ready, stats, black_level, 16, w)
-        elif packed is not None:
-            F.raw_stats(packed[0], stats, black_level, packed[1], w)
-        else:
-            F.raw_stats(raw_u16, stats, black_level, 16, w)
+def _serve_routes(modules, param_tensors, raw, lead, h, w, white_level, black_level, cfa, raw_format, lens_shading, defect, temporal,
+                  stats, reverse_channels, out, coef, fast_scene, fast_denoise, fast_median, fast_denoise_scene, fast_cond, report):
+    """``serve`` behind the checks of its output side: the sensor pre-pass (``_sensor_input``), the route and its launches ->
+    (image, route).  The route is the one uint16 frames from the allocator take, whatever the pre-pass did.  'fused' and
+    'classical' load ``packed`` bytes where ``serve_load`` says so, 'classical' shades in its load where ``serve_shade`` says so
+    (uint16 input, 8-byte aligned), and every other launch reads ``frames()``.  With ``coef`` (NV12, ``out`` being the NV12
+    buffer): 'fused' and 'classical' store NV12 into ``out`` themselves and report it, every other route serves BGR into the
+    cached packed image for the conversion launch.  ``report`` takes 'load', 'shade' and 'store' where a launch fuses them"""
+    n, device = lead[0], raw.device
+    white_level, black_level, aligned, packed, shade, frames = _sensor_input(
+        raw, lead, h, w, white_level, black_level, cfa, raw_format, lens_shading, defect, temporal, stats, report)
+    divisor = white_level - black_level
     code = F.cfa_code(cfa)
     # where a route without the NV12 store writes its packed image
-    dst = (lambda: out) if coef is None else (lambda: _nv12_bgr((n, h, w, 3), device))
-    if fast_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
+    dst = (lambda: out) if coef is None else (lambda: _source_image('nv12', (h, w), lead, device))
+    geometry = h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned      # what the classical kernels take
+    if fast_scene and geometry:
         plan = scene_plan(modules)
         if plan is not None:
             return _serve_scene(plan, modules, param_tensors, frames(), divisor, reverse_channels, dst(), black_level, cfa), 'scene'
-    if fast_denoise and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
+    if fast_denoise and geometry:
         plan = denoise_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
         if args is not None:
@@ -1206,7 +1119,7 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
             post_ops, post_params = _stage_lists(modules, param_tensors, plan[3])
             return F.serve_denoise_u8(frames(), divisor, plan[0], pre_ops, pre_params, args[0], args[1], post_ops, post_params,
                                       reverse_channels, dst(), black_level, cfa), 'denoise'
-    if fast_median and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
+    if fast_median and geometry:
         plan = denoise_plan(modules)
         if plan is not None and type(modules[plan[2]]) is T.OriginNoiseMedian:
             size = _median_args(modules[plan[2]], param_tensors[plan[2]])
@@ -1218,14 +1131,13 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
                                               reverse_channels, dst(), black_level, cfa), 'denoise'
                 return F.serve_median_u8(frames(), divisor, plan[0], pre_ops, pre_params, size, post_ops, post_params,
                                          reverse_channels, dst(), black_level, cfa), 'denoise'
-    if fast_denoise_scene and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned:
+    if fast_denoise_scene and geometry:
         plan = denoise_scene_plan(modules)
         args = _denoise_args(modules[plan[2]], param_tensors[plan[2]]) if plan is not None else None
         if args is not None:
             return _serve_denoise_scene(plan, args, modules, param_tensors, frames(), divisor, reverse_channels, dst(), black_level,
                                         cfa), 'denoise_scene'
-    if (fast_cond and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535 and aligned
-            and h * w <= 1 << 24):
+    if fast_cond and geometry and h * w <= 1 << 24:
         plan = cond_plan(modules)
         if plan is not None and _cond_heads_ok(plan, modules, param_tensors):
             return _serve_cond(plan, modules, param_tensors, frames(), divisor, reverse_channels, dst(), black_level, cfa), 'cond'
@@ -1237,24 +1149,30 @@ def _serve_routes(modules, param_tensors, raw_u16, white_level, divisor, reverse
         if args is None or (args[3] <= 3 and min(h, w) > 8):
             ops = [_CHAIN_OP[type(modules[k])] for k in chain]
             params = [_chain_param(modules[k], param_tensors[k]) for k in chain]
-            if packed is not None and serve_load('fused', packed[3]) == 'fused':
-                return F.serve_packed(packed[0], packed[1], w, divisor, ops, params, args, reverse_channels, coef,
-                                      out if coef is None else nv12_out, black_level, cfa), 'fused'
             if coef is not None:
-                return F.serve_nv12(frames(), divisor, ops, params, args, coef, nv12_out, black_level, cfa), 'fused'
+                report['store'] = 'fused'
+            if packed is not None and serve_load('fused', packed[3]) == 'fused':
+                report['load'] = 'fused'
+                return F.serve_packed(packed[0], packed[1], w, divisor, ops, params, args, reverse_channels, coef, out, black_level,
+                                      cfa), 'fused'
+            if coef is not None:
+                return F.serve_nv12(frames(), divisor, ops, params, args, coef, out, black_level, cfa), 'fused'
             return F.serve_u8(frames(), divisor, ops, params, args, reverse_channels, out, black_level, cfa), 'fused'
-    if (serve_route(modules) == 'classical' and h % 2 == 0 and h >= 4 and w % 4 == 0 and n <= 65535
-            and aligned):
+    if serve_route(modules) == 'classical' and geometry:
         kind, stages = _classical_split(modules)
         ops, params = _stage_lists(modules, param_tensors, stages)
-        if shade is not None and fmt == 'u16' and serve_shade('classical', fmt) == 'fused' and raw_u16.data_ptr() % 8 == 0:
-            return F.serve_classical_shaded(raw_u16, shade[0], divisor, kind, ops, params, reverse_channels, coef,
-                                            out if coef is None else nv12_out, shade[1], cfa), 'classical'
-        if packed is not None and serve_load('classical', packed[3]) == 'fused':
-            return F.serve_classical_packed(packed[0], packed[1], w, divisor, kind, ops, params, reverse_channels, coef,
-                                            out if coef is None else nv12_out, black_level, cfa), 'classical'
         if coef is not None:
-            return F.serve_classical_nv12(frames(), divisor, kind, ops, params, coef, nv12_out, black_level, cfa), 'classical'
+            report['store'] = 'fused'
+        if shade is not None and raw_format == 'u16' and serve_shade('classical', 'u16') == 'fused' and raw.data_ptr() % 8 == 0:
+            report['shade'] = 'fused'
+            return F.serve_classical_shaded(raw, shade[0], divisor, kind, ops, params, reverse_channels, coef, out, shade[1],
+                                            cfa), 'classical'
+        if packed is not None and serve_load('classical', packed[3]) == 'fused':
+            report['load'] = 'fused'
+            return F.serve_classical_packed(packed[0], packed[1], w, divisor, kind, ops, params, reverse_channels, coef, out,
+                                            black_level, cfa), 'classical'
+        if coef is not None:
+            return F.serve_classical_nv12(frames(), divisor, kind, ops, params, coef, out, black_level, cfa), 'classical'
         return F.serve_classical_u8(frames(), divisor, kind, ops, params, reverse_channels, out, black_level, cfa), 'classical'
     from ...data.gpu_input import raw_crops
     sel = torch.zeros((n, 3), device=device, dtype=torch.int32)
@@ -1342,96 +1260,61 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
     ``patch_size`` / ``patch_stride``: an int or a (rows, columns) pair; H, W, sizes and strides even.  Everything is issued
     on the current stream; the tile origins live on the device per geometry (``frame_geometry``).  Argument checks are those
     of ``serve``."""
+    return serve_frame_reported(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch, reverse_channels,
+                                out, black_level, cfa, out_format, yuv_matrix, sharpen, out_size=out_size, out_window=out_window,
+                                resample=resample, raw_format=raw_format, temporal_denoise=temporal_denoise, statistics=statistics,
+                                warp=warp, raw_width=raw_width, defect_correction=defect_correction, lens_shading=lens_shading)[0]
+
+
+def serve_frame_reported(modules, param_tensors, raw_u16, white_level, patch_size, patch_stride, tile_batch=16,
+                         reverse_channels=False, out=None, black_level=0, cfa='rggb', out_format='bgr8', yuv_matrix='bt601_full',
+                         sharpen=None, *, out_size=None, out_window=None, resample='triangle', raw_format='u16',
+                         temporal_denoise=None, statistics=None, warp=None, raw_width=None, defect_correction=None,
+                         lens_shading=None):
+    """``serve_frame`` with the record of what ran: (image, report), a dict with the keys of ``SERVE_REPORT`` as
+    ``serve_reported`` fills it, the route being 'tiled'"""
     from ...data.gpu_input import raw_crops
-    splan = sharpen_plan(raw_u16, raw_format, raw_width, (2, 3), sharpen, warp, out_size, out_window, resample, out_format,
-                         yuv_matrix, reverse_channels, out) # refused before anything is launched; it plans the warp and the resize too
-    wplan = None if splan is not None else warp_plan(raw_u16, raw_format, raw_width, (2, 3), warp, out_size, out_window, resample,
-                                                     out_format, yuv_matrix, reverse_channels, out)     # likewise
-    plan = None if wplan is not None or splan is not None else resize_plan(raw_u16, raw_format, raw_width, (2, 3), out_size, out_window, resample,
-                                                      out_format, yuv_matrix, reverse_channels, out)    # likewise
-    if statistics is not None:                              # refused before anything is launched
+    report = dict.fromkeys(SERVE_REPORT)
+    plan = output_plan(raw_u16, raw_format, raw_width, (2, 3), sharpen, warp, out_size, out_window, resample, out_format,
+                       yuv_matrix, reverse_channels, out)   # refused before anything is launched
+    if statistics is not None:                              # likewise
         stats_plan(raw_u16, raw_format, raw_width, (2, 3), statistics)
-        if black_level != int(black_level) or not 0 <= black_level < white_level:
-            raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-    temporal = temporal_plan(raw_u16, raw_format, raw_width, (2, 3), temporal_denoise)     # refused before anything is launched
-    if temporal is not None and (black_level != int(black_level) or not 0 <= black_level < white_level):
-        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-    prepass = lens_shading is not None or defect_correction is not None
-    if prepass:
-        if raw_format != 'u16':
-            bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
-        else:
-            if (not isinstance(raw_u16, torch.Tensor) or raw_u16.dtype != torch.uint16 or raw_u16.dim() not in (2, 3)
-                    or raw_u16.shape[-1] % 4):
-                raise ValueError('%s takes (H,W) or (N,H,W) uint16 frames with W a multiple of 4, got %s %s'
-                                 % ('lens_shading' if lens_shading is not None else 'defect_correction',
-                                    getattr(raw_u16, 'dtype', type(raw_u16)), tuple(getattr(raw_u16, 'shape', ()))))
-            bits, w = 16, raw_u16.shape[-1]
+        _check_black_level(black_level, white_level)
+    if temporal_denoise is not None:                        # likewise
+        temporal_plan(raw_u16, raw_format, raw_width, (2, 3), temporal_denoise)
+        _check_black_level(black_level, white_level)
+    if lens_shading is not None or defect_correction is not None:
+        # what the host can tell about a pre-pass is named before a missing device: the frames, then the correction's tuple
+        if raw_format == 'u16' and (not isinstance(raw_u16, torch.Tensor) or raw_u16.dtype != torch.uint16
+                                    or raw_u16.dim() not in (2, 3) or raw_u16.shape[-1] % 4):
+            raise ValueError('%s takes (H,W) or (N,H,W) uint16 frames with W a multiple of 4, got %s %s'
+                             % ('lens_shading' if lens_shading is not None else 'defect_correction',
+                                getattr(raw_u16, 'dtype', type(raw_u16)), tuple(getattr(raw_u16, 'shape', ()))))
         if defect_correction is not None:
-            F.defect_check(defect_correction, raw_u16.shape[-2], w)
-        F._need_gpu(raw_u16, 'raw')
-        if black_level != int(black_level) or not 0 <= black_level < white_level:
-            raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
-        if lens_shading is not None:
-            F.shading_check(lens_shading, raw_u16.shape[-2], w, raw_u16.device)
-        if defect_correction is not None:
-            raw_u16 = _corrected(raw_u16.contiguous(), defect_correction, bits, w, raw_format,
-                                 None if lens_shading is None else (lens_shading, int(black_level)))
-        else:
-            raw_u16 = F.raw_shade(raw_u16.contiguous(), lens_shading, int(black_level), bits, w,
-                                  _shaded_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
-        if lens_shading is not None:
-            white_level, black_level = white_level - black_level, 0
-        raw_format = 'u16'
-    if temporal is not None:                                # behind the pre-pass, in front of the statistics and the tiles
-        if raw_format != 'u16':
-            bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
-            F._need_gpu(raw_u16, 'raw')
-            raw_u16 = F.raw_unpack(raw_u16.contiguous(), bits, w, _packed_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
-            raw_format = 'u16'
-        F._need_gpu(raw_u16, 'raw')
-        raw_u16 = F.raw_temporal(raw_u16.contiguous(), temporal, int(black_level), _temporal_u16(tuple(raw_u16.shape), raw_u16.device))
-    if statistics is not None:
-        if prepass or temporal is not None:                 # the statistics of the pre-pass's or the filter's frames
-            F.raw_stats(raw_u16, statistics, int(black_level), 16)
-        else:                                               # of the input as given, packed or not
-            F.raw_stats(raw_u16.contiguous(), statistics, int(black_level), F.raw_format_bits(raw_format) or 16,
-                        raw_width if raw_format != 'u16' else None)
-    if raw_format != 'u16':
-        bits, w = _packed_plan(raw_u16, raw_format, raw_width, (2, 3))
-        F._need_gpu(raw_u16, 'raw')
-        raw_u16 = F.raw_unpack(raw_u16.contiguous(), bits, w, _packed_u16(tuple(raw_u16.shape[:-1]) + (w,), raw_u16.device))
-    F._need_gpu(raw_u16, 'raw')
-    if raw_u16.dtype != torch.uint16 or raw_u16.dim() not in (2, 3):
-        raise ValueError('expected (H,W) or (N,H,W) uint16 frames, got %s %s' % (raw_u16.dtype, tuple(raw_u16.shape)))
-    code = F.cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level < white_level:
-        raise ValueError('black_level %r: an integer with 0 <= black_level < white_level (%r)' % (black_level, white_level))
+            F.defect_check(defect_correction, *_frame_shape(raw_u16, raw_format, raw_width, (2, 3))[1:])
+    lead, H, W = _device_frames(raw_u16, raw_format, raw_width, (2, 3))
+    device, single = raw_u16.device, not lead
+    # defect (+ shade) | shade | unpack -> temporal -> statistics, once for the whole frames, in front of the tiles
+    white_level, black_level, _, _, _, frames = _sensor_input(raw_u16.contiguous(), lead, H, W, white_level, black_level, cfa,
+                                                              raw_format, lens_shading, defect_correction, temporal_denoise,
+                                                              statistics, report)
+    frames = frames()[None] if single else frames()
     if int(tile_batch) < 1:
         raise ValueError('tile_batch %r: at least one tile per forward' % (tile_batch,))
-    single = raw_u16.dim() == 2
-    frames = (raw_u16[None] if single else raw_u16).contiguous()
-    n, H, W = frames.shape
-    F._check_mirror(code, H, W)
+    n, code = frames.shape[0], F.cfa_code(cfa)
     size, stride = _pair(patch_size), _pair(patch_stride)
-    origins, sel = frame_geometry(H, W, size, stride, cfa, frames.device)
+    origins, sel = frame_geometry(H, W, size, stride, cfa, device)
     count, tile_batch = origins.shape[0], int(tile_batch)
-    coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W) if plan is None and wplan is None and splan is None else None
-    if splan is not None:
-        # every frame is served at the sensor's size into the cached image of the first launch behind the loop
-        final, out = out, _sharpen_source(warp, out_size, out_window)((H, W, 3) if single else (n, H, W, 3), frames.device)
-    elif wplan is not None:
-        # every frame is served at the sensor's size into the warp's cached image; the warp launch behind the loop reads it
-        final, out = out, _warp_bgr((H, W, 3) if single else (n, H, W, 3), frames.device)
-    elif plan is not None:
-        # every frame is served at the sensor's size into the cached image; the resize launch behind the loop writes `out`
-        final, out = out, _resize_bgr((H, W, 3) if single else (n, H, W, 3), frames.device)
-    elif coef is None:
-        out = F._u8_out(out, (H, W, 3) if single else (n, H, W, 3), frames.device, 1)
+    final, coef = out, None
+    if plan is not None:
+        # every frame is blended at the sensor's size into the source image of the first launch behind the loop
+        out = _source_image(plan[0][0][0], (H, W), lead, device)
     else:
-        out = F._u8_out(out, (H + H // 2, W) if single else (n, H + H // 2, W), frames.device, 1)
-        bgr = _nv12_bgr((H, W, 3), frames.device)
-    stack = torch.empty((count, 3) + size, device=frames.device, dtype=torch.float32)
+        coef = _nv12_plan(out_format, yuv_matrix, reverse_channels, H, W)
+        out = F._u8_out(out, lead + ((H, W, 3) if coef is None else (H + H // 2, W)), device, 1)
+        if coef is not None:
+            bgr, report['store'] = _source_image('nv12', (H, W), (), device), 'pass'    # converted frame by frame behind the blend
+    stack = torch.empty((count, 3) + size, device=device, dtype=torch.float32)
     if callable(param_tensors):
         param_tensors = param_tensors(min(tile_batch, count))
     with torch.no_grad():
@@ -1449,13 +1332,10 @@ def serve_frame(modules, param_tensors, raw_u16, white_level, patch_size, patch_
             else:
                 F.tile_blend_u8(stack, origins, (H, W), stride, False, bgr, code)
                 F.bgr8_to_nv12(bgr, coef, 'bgr', out if single else out[k])
-    if splan is not None:
-        return _sharpened(out, splan, warp, resample, reverse_channels, final)
-    if wplan is not None:
-        return _warped(out, wplan, warp, resample, final)
+    report['route'] = 'tiled'
     if plan is not None:
-        return _resized(out, plan, resample, final)
-    return out
+        out = _deliver(out, plan, resample, reverse_channels, final, report)
+    return out, report
 
 
 def wants_grad(x, raw_params):

@@ -228,17 +228,19 @@ def test_host_refusals_come_before_the_device():
         F.bgr8_sharpen(img, (256, 4, 40, 2))
     raw = torch.zeros((2, 8, 12), dtype=torch.uint16)
     with pytest.raises(ValueError, match='amount'):
-        PF.sharpen_plan(raw, 'u16', None, (3,), (5000, 0, 0, 1), None, None, None, 'triangle', 'bgr8', 'bt601_full', False, None)
+        PF.output_plan(raw, 'u16', None, (3,), (5000, 0, 0, 1), None, None, None, 'triangle', 'bgr8', 'bt601_full', False, None)
     with pytest.raises(ValueError, match='4:2:0'):
-        PF.sharpen_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, (5, 6), None, 'triangle', 'nv12', 'bt601_full', False, None)
+        PF.output_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, (5, 6), None, 'triangle', 'nv12', 'bt601_full', False, None)
     with pytest.raises(ValueError, match='reverse_channels'):
-        PF.sharpen_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, None, None, 'triangle', 'nv12', 'bt601_full', True, None)
+        PF.output_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, None, None, 'triangle', 'nv12', 'bt601_full', True, None)
     with pytest.raises(ValueError, match='out must be'):
-        PF.sharpen_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, None, None, 'triangle', 'bgr8', 'bt601_full', False,
-                        torch.zeros((2, 8, 12), dtype=torch.uint8))
-    plan = PF.sharpen_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, (4, 6), None, 'triangle', 'nv12', 'bt709_full', False, None)
-    assert plan[0] == (256, 4, 40, 2) and plan[1] is None and plan[2][0] == (4, 6) and len(plan[3]) == 12 and plan[4] == (4, 6)
-    assert PF.sharpen_plan(raw, 'u16', None, (3,), None, None, None, None, 'triangle', 'bgr8', 'bt601_full', False, None) is None
+        PF.output_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, None, None, 'triangle', 'bgr8', 'bt601_full', False,
+                       torch.zeros((2, 8, 12), dtype=torch.uint8))
+    steps, coef, final, store = PF.output_plan(raw, 'u16', None, (3,), (256, 4, 40, 2), None, (4, 6), None, 'triangle', 'nv12',
+                                               'bt709_full', False, None)
+    assert [name for name, _, _ in steps] == ['resize', 'sharpen']              # no warp step
+    assert steps[0][1][0] == (4, 6) and steps[1][1] == (256, 4, 40, 2) and len(coef) == 12 and final == (4, 6)
+    assert PF.output_plan(raw, 'u16', None, (3,), None, None, None, None, 'triangle', 'bgr8', 'bt601_full', False, None) is None
 
 
 def _serve_functions():
