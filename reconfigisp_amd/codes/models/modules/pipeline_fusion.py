@@ -598,7 +598,7 @@ def serve_shade(route, raw_format):
 # raw formats whose defective-pixel correction and lens shading run as ONE risp_raw_defect launch (with gains) instead of
 # risp_raw_defect followed by risp_raw_shade.  A format is listed only if the one launch beats the two by more than the larger
 # spread of the two legs in every measured row of profiles/serve_defect.txt (two sizes per format) - the rule of
-# _FUSED_LOAD, _FUSED_SHADE and _MEDIAN_SIZES.  The verdict line of that file is this table.  Measured: the one launch is 7.8 to
+# every measured table here, tools/serve_bench.beats.  The verdict line of that file is this table.  Measured: the one launch is 7.8 to
 # 9.9 us faster in all six rows (0.83-0.92 x) against spreads of 0.2 to 2.0 us - the second launch costs a launch and a second trip
 # of the frames through the cache, the gains cost the first one three multiplies per sample beside some sixty instructions.
 _DEFECT_SHADE_FUSED = frozenset({'u16', 'raw10', 'raw12'})
@@ -705,7 +705,7 @@ def temporal_plan(raw, raw_format, raw_width, dims, temporal_denoise):
 # output formats a resized call stores from the resize launch itself (risp_bgr8_resize with the matrix) instead of resizing to
 # packed BGR and converting that with risp_bgr8_to_nv12.  'nv12' is listed only if the fused store beats the two launches by
 # more than the larger spread of the two legs in every measured row of profiles/serve_resize.txt (two sizes, triangle and
-# bicubic) - the rule of _FUSED_LOAD, _FUSED_SHADE and _DEFECT_SHADE_FUSED.  The verdict line of that file is this
+# bicubic) - the rule of every measured table here, tools/serve_bench.beats.  The verdict line of that file is this
 # table.  Measured: at 64 x 256 x 256 -> 128 x 128 the fused store is 6.4 us (triangle) and 4.3 us (bicubic) faster, far beyond
 # the spread; on the 3000 x 4000 frame -> 1080 x 1920 it is 0.5 us faster against a spread of 0.4 us (triangle) and 1.4 us SLOWER
 # (bicubic) - the NV12 store keeps half the threads of phase 2 idle, and the conversion launch costs 4 us there.  Three rows of
@@ -729,7 +729,7 @@ def resize_store(out_format):
 # warp kernels whose launch stages the source box of a tile in LDS (risp_bgr8_warp with stage = 1) instead of sampling global
 # memory from every tile (stage = 0).  A kernel is listed only if stage = 1 beats stage = 0 by more than the larger spread of the
 # two legs in every measured row of that kernel in profiles/serve_warp.txt (two sizes x identity, a 2-degree rotation and a radial
-# correction) - the rule of _FUSED_LOAD, _FUSED_SHADE, _DEFECT_SHADE_FUSED and _RESIZE_NV12_FUSED.  The verdict line
+# correction) - the rule of every measured table here, tools/serve_bench.beats.  The verdict line
 # of that file is this table.  Measured: staging LOSES in all twelve rows - 3000 x 4000 bilinear 284-292 us against 58-68 us, bicubic
 # 336-344 against 180-215; 64 x 256 x 256 97-99 against 23-25 and 115-118 against 66-78, spreads under 8 us: a launch that asks for 64 KB
 # of LDS keeps two workgroups on a CU, and a tile's chain of loads, barriers, taps and stores has nothing to hide behind.  So the
@@ -750,7 +750,7 @@ def warp_stage(kernel):
 # output formats a sharpened call stores from the sharpen launch itself (risp_bgr8_sharpen with the matrix) instead of sharpening
 # to packed BGR and converting that with risp_bgr8_to_nv12.  'nv12' is listed only if the fused store beats the two launches by
 # more than the larger spread of the two legs in every measured row of profiles/serve_sharpen.txt (three sizes, both radii;
-# DESIGN.md 4.6) - the rule of _FUSED_LOAD, _FUSED_SHADE, _DEFECT_SHADE_FUSED and _RESIZE_NV12_FUSED.  The verdict line of that
+# DESIGN.md 4.6) - the rule of every measured table here, tools/serve_bench.beats.  The verdict line of that
 # file is this table.  Measured: the fused store wins all six rows - 64 x 256 x 256 15.3 / 16.5 us (radius 1 / 2) against 21.9 / 23.0,
 # 3000 x 4000 38.1 / 40.7 against 47.8 / 51.2, 1080 x 1920 9.8 / 9.9 against 16.3 / 16.3, spreads of at most 0.7 us: the NV12 store
 # reads the sharpened tile from LDS, where the BGR store reads it too, and writes half the bytes, while the conversion launch reads

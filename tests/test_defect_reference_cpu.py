@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import defect_reference as DR
+from serve_verdicts import read_verdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -247,11 +248,7 @@ def test_defect_shade_is_a_pure_table_and_the_table_is_the_measured_verdict():
         assert PF.defect_shade(fmt) == ('fused' if fmt in PF._DEFECT_SHADE_FUSED else 'pass')
     with pytest.raises(ValueError, match='raw_format'):
         PF.defect_shade('raw14')
-    text = open(os.path.join(ROOT, 'profiles', 'serve_defect.txt')).read()
-    lines = re.findall(r'^verdict: _DEFECT_SHADE_FUSED = (.*)$', text, flags=re.M)
-    assert len(lines) == 1, 'profiles/serve_defect.txt states the verdict in one line'
-    measured = frozenset() if lines[0].strip() == 'none' else frozenset(lines[0].split())
-    assert measured == PF._DEFECT_SHADE_FUSED
+    assert read_verdict('serve_defect.txt', '_DEFECT_SHADE_FUSED') == PF._DEFECT_SHADE_FUSED
 
 
 def test_the_entry_point_is_declared():

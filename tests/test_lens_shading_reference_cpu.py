@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import lens_shading_reference as LS
+from serve_verdicts import read_verdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(4, 4), (4, 8), (6, 12), (34, 68)]
@@ -188,10 +189,7 @@ def test_serve_shade_is_a_pure_table_and_the_table_is_the_measured_verdict():
         PF.serve_shade('nope', 'u16')
     with pytest.raises(ValueError, match='raw_format'):
         PF.serve_shade('classical', 'raw14')
-    text = open(os.path.join(ROOT, 'profiles', 'serve_shade.txt')).read()
-    lines = re.findall(r'^verdict: _FUSED_SHADE = (.*)$', text, flags=re.M)
-    assert len(lines) == 1, 'profiles/serve_shade.txt states the verdict in one line'
-    measured = frozenset() if lines[0].strip() == 'none' else frozenset(tuple(t.split('/')) for t in lines[0].split())
+    measured = frozenset(tuple(t.split('/')) for t in read_verdict('serve_shade.txt', '_FUSED_SHADE'))
     assert measured == PF._FUSED_SHADE
 
 

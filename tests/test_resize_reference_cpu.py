@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import resize_reference as RR  # noqa: E402
+from serve_verdicts import read_verdict  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIG = ((4000, 1920), (4000, 640), (4000, 500), (3000, 1080))
@@ -217,11 +218,7 @@ def test_resize_store_is_a_pure_table_and_the_table_is_the_measured_verdict():
     assert PF.resize_store('nv12') == ('fused' if 'nv12' in PF._RESIZE_NV12_FUSED else 'pass')
     with pytest.raises(ValueError, match='out_format'):
         PF.resize_store('i420')
-    text = open(os.path.join(ROOT, 'profiles', 'serve_resize.txt')).read()
-    lines = re.findall(r'^verdict: _RESIZE_NV12_FUSED = (.*)$', text, flags=re.M)
-    assert len(lines) == 1, 'profiles/serve_resize.txt states the verdict in one line'
-    measured = frozenset() if lines[0].strip() == 'none' else frozenset(lines[0].split())
-    assert measured == PF._RESIZE_NV12_FUSED
+    assert read_verdict('serve_resize.txt', '_RESIZE_NV12_FUSED') == PF._RESIZE_NV12_FUSED
 
 
 def test_the_entry_point_is_declared():

@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sharpen_reference as SR  # noqa: E402
+from serve_verdicts import read_verdict  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -294,8 +295,4 @@ def test_sharpen_store_is_a_pure_table_and_the_table_is_the_measured_verdict():
     for bad in ('yuv', None, 0):
         with pytest.raises(ValueError, match='out_format'):
             PF.sharpen_store(bad)
-    text = open(os.path.join(ROOT, 'profiles', 'serve_sharpen.txt')).read()
-    lines = re.findall(r'^verdict: _SHARPEN_NV12_FUSED = (.*)$', text, flags=re.M)
-    assert len(lines) == 1, 'profiles/serve_sharpen.txt states the verdict in one line'
-    measured = frozenset() if lines[0].strip() == 'none' else frozenset(lines[0].split())
-    assert measured == PF._SHARPEN_NV12_FUSED
+    assert read_verdict('serve_sharpen.txt', '_SHARPEN_NV12_FUSED') == PF._SHARPEN_NV12_FUSED

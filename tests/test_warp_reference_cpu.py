@@ -13,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import warp_reference as WR  # noqa: E402
+from serve_verdicts import read_verdict  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -344,8 +345,4 @@ def test_warp_stage_is_a_pure_table_and_the_table_is_the_measured_verdict():
     for kernel in ('box', None, 0):
         with pytest.raises(ValueError, match='kernel'):
             PF.warp_stage(kernel)
-    text = open(os.path.join(ROOT, 'profiles', 'serve_warp.txt')).read()
-    lines = re.findall(r'^verdict: _WARP_STAGED = (.*)$', text, flags=re.M)
-    assert len(lines) == 1, 'profiles/serve_warp.txt states the verdict in one line'
-    measured = frozenset() if lines[0].strip() == 'none' else frozenset(lines[0].split())
-    assert measured == PF._WARP_STAGED
+    assert read_verdict('serve_warp.txt', '_WARP_STAGED') == PF._WARP_STAGED

@@ -16,29 +16,19 @@ Each round times every candidate once (REPS launches between two events, rotatin
 per candidate: the rounds, median, minimum and spread - the spread between the rounds of ONE candidate is the noise a
 difference between two candidates has to clear.  The bytes of route and serve_u8 are compared first.  Last, tensor2bgr on
 the host for the frame (what the drivers do today)."""
-import argparse
 import ctypes as C
-import os
-import sys
+import functools
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import torch
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd import lib as L  # noqa: E402
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.utils import util  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd import lib as L
+from reconfigisp_amd.codes.utils import util
 
-HBM_PEAK = 8.0e12
 WHITE = 1023.0
 OPS = [F.OP_WB_MANUAL, F.OP_GAMMA, F.OP_GTM_MANUAL]
-
-
-def frames_u16(n, h, w, seed):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
 
 
 class Candidates:
@@ -113,11 +103,18 @@ PARENT = None           # --parent-lib: a second build of the library, bound wit
 CFA_NAMES = ['serve_rggb', 'serve_grbg', 'serve_gbrg', 'serve_bggr', 'serve_b512', 'workaround']
 
 
-def load_parent(path):
-    global PARENT
-    PARENT = C.CDLL(os.path.abspath(path))
-    res, args = L.SIGNATURES['risp_serve_u8']
-    PARENT.risp_serve_u8.restype, PARENT.risp_serve_u8.argtypes = res, args
+def timed_rotating(fns, reps):
+    """serve_bench.timed over the resident inputs in turn: the index stays inside the window, as the recorded rounds had it"""
+    for k in range(4):
+        fns[k % len(fns)]()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for k in range(reps):
+        fns[k % len(fns)]()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3
 
 
 def measure(sets, reps, rounds, emit):
@@ -134,31 +131,15 @@ def measure(sets, reps, rounds, emit):
             c.out_serve.zero_()
             c.serve_parent()
             assert torch.equal(c.out_route, c.out_serve), 'the parent build and the route disagree'
-    res = {k: [] for k in names}
-    for _ in range(rounds):
-        for name in names:
-            fns = [getattr(c, name) for c in sets]
-            for k in range(4):
-                fns[k % len(fns)]()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for k in range(reps):
-                fns[k % len(fns)]()
-            e1.record()
-            e1.synchronize()
-            res[name].append(e0.elapsed_time(e1) / reps * 1e3)
+    res = SB.rounds_of({name: [getattr(c, name) for c in sets] for name in names}, reps, rounds, False, timed_rotating)
     n, h, w = sets[0].shape
     pix = n * h * w
-    for name in names:
-        v = res[name]
-        med = sorted(v)[len(v) // 2]
-        emit('  %-12s rounds %s' % (name, ' '.join('%.2f' % t for t in v)))
-        emit('  %-12s median %.2f us  min %.2f  spread %.2f' % (name, med, min(v), max(v) - min(v)))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    bps = 5.0 * pix / (med['serve'] * 1e-6)
-    emit('  serve_u8 moves 5 B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak; fp32 launch (64 B/pixel): %.2f TB/s' % (
-        bps / 1e12, 100 * bps / HBM_PEAK, HBM_PEAK / 1e12, 64.0 * pix / (med['fp32_launch'] * 1e-6) / 1e12))
+    for name, v in res.items():
+        for line in SB.leg_lines(name, v, 12, '%.2f'):
+            emit(line)
+    med = {k: SB.median(v) for k, v in res.items()}
+    emit('  serve_u8 moves 5 B/pixel: %s; fp32 launch (64 B/pixel): %.2f TB/s' % (
+        SB.hbm_share(5.0 * pix, med['serve']), 64.0 * pix / (med['fp32_launch'] * 1e-6) / 1e12))
     emit('  serve_u8 / fp32 launch = %.3f   serve_u8 / route = %.3f   (%.0f MPix/s)' % (
         med['serve'] / med['fp32_launch'], med['serve'] / med['route'], pix / med['serve']))
     emit('  against serve_u8: ' + '  '.join('%s %.3f' % (k[6:] if k.startswith('serve_') else k, med[k] / med['serve'])
@@ -173,56 +154,36 @@ COMPOSED_ARCH = 'Demosaic_01_sRGB_07_11_01_14'      # as an IspUniversal its bil
 def measure_composed(reps, rounds, emit):
     """net.serve() on the composed route (risp_raw_crop[_cfa] -> fused_forward with a CNN stage -> risp_quantise_u8[_flip]), host
     side included, with and without a phase and a black level"""
-    from reconfigisp_amd.codes.models import networks
-    opt = {'network_G': {'which_model_G': 'IspUniversal', 'architecture': COMPOSED_ARCH, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    net = networks.define_G(opt).cuda().eval()
-    raw = frames_u16(8, 256, 256, 30)
+    net = SB.pipeline(COMPOSED_ARCH, 'IspUniversal')
+    raw = SB.frames_u16(8, 256, 256, 30, WHITE)
     buf = torch.empty((8, 256, 256, 3), device='cuda', dtype=torch.uint8)
     legs = {'rggb_b0': dict(), 'bggr_b64': dict(black_level=64, cfa='bggr')}
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, kw in legs.items():
-            for k in range(3):
-                net.serve(raw, WHITE, out=buf, **kw)
-            assert net.last_serve_route == 'composed'
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for k in range(reps):
-                net.serve(raw, WHITE, out=buf, **kw)
-            e1.record()
-            e1.synchronize()
-            res[name].append(e0.elapsed_time(e1) / reps * 1e3)
+    for kw in legs.values():
+        net.serve(raw, WHITE, out=buf, **kw)
+        assert net.last_serve_route == 'composed'
+    # a partial, not a closure: the window holds the call of net.serve and nothing around it, as the recorded rounds had it
+    res = SB.rounds_of({name: functools.partial(net.serve, raw, WHITE, out=buf, **kw) for name, kw in legs.items()}, reps, rounds, False)
     for name, v in res.items():
-        emit('  %-12s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        emit('  %-12s median %.1f us  min %.1f  spread %.1f' % (name, sorted(v)[len(v) // 2], min(v), max(v) - min(v)))
-    emit('  bggr_b64 / rggb_b0 = %.3f' % (sorted(res['bggr_b64'])[rounds // 2] / sorted(res['rggb_b0'])[rounds // 2]))
+        for line in SB.leg_lines(name, v, 12):
+            emit(line)
+    emit('  bggr_b64 / rggb_b0 = %.3f' % (SB.median(res['bggr_b64']) / SB.median(res['rggb_b0'])))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=2000)
-    ap.add_argument('--rounds', type=int, default=7)
+    global PARENT
+    ap = SB.parser(2000, 7)
     ap.add_argument('--parent-lib', default=None, help='a second build of libreconfigisp_hip.so (the parent commit\'s): its '
                     'risp_serve_u8 is timed in the same rounds')
     args = ap.parse_args()
     if args.parent_lib:
-        load_parent(args.parent_lib)
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+        PARENT = SB.load_parent(args.parent_lib, ['risp_serve_u8'])
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('64 x 256 x 256, %d launches per round, rotating over 4 resident inputs; us per call' % args.reps)
-    measure([Candidates(frames_u16(64, 256, 256, 10 + k)) for k in range(4)], args.reps, args.rounds, emit)
+    measure([Candidates(SB.frames_u16(64, 256, 256, 10 + k, WHITE)) for k in range(4)], args.reps, args.rounds, emit)
     frame_reps = max(20, args.reps // 10)
     emit('1 x 3000 x 4000, %d launches per round; us per call' % frame_reps)
-    frame = Candidates(frames_u16(1, 3000, 4000, 20))
+    frame = Candidates(SB.frames_u16(1, 3000, 4000, 20, WHITE))
     measure([frame], frame_reps, args.rounds, emit)
     last = frame.plan.outs[-1]
     torch.cuda.synchronize()
@@ -236,10 +197,7 @@ def main():
     emit('composed route, IspUniversal %s (proxy CNN bilateral), 8 x 256 x 256, net.serve(out=) %d calls per round; us per call'
          % (COMPOSED_ARCH, frame_reps))
     measure_composed(frame_reps, args.rounds, emit)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -16,35 +16,15 @@ Each round times every leg once (REPS calls, after 3 warm ones); per leg: the ro
 between the rounds of ONE leg is the noise a difference between two legs has to clear.  The bytes of classical and composed
 are compared first.  Bytes moved are algorithmic counts from the module list (fp32 planes written and read back by the
 composed route; 2 read + 3 written by the one launch), the share of HBM peak is those bytes over the median time."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
+from reconfigisp_amd.codes.models.modules import tools_origin as T
 
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from reconfigisp_amd.codes.models.modules import tools_origin as T  # noqa: E402
-
-HBM_PEAK = 8.0e12
 WHITE = 1023.0
 ARCHS = ['Demosaic_02_sRGB_11_01_14', 'Demosaic_03_sRGB_11_04_01']
 HEADLINE = 'Demosaic_01_sRGB_07_11_01_14'
-
-
-def frames_u16(n, h, w, seed):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
-
-
-def pipeline(arch):
-    opt = {'network_G': {'which_model_G': 'OriginUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    return networks.define_G(opt).cuda().eval()
 
 
 def composed_bytes_per_pixel(modules):
@@ -61,23 +41,10 @@ def composed_bytes_per_pixel(modules):
     return total + (12 + 12 * run if run else 0)
 
 
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def measure(arch, head, raw, reps, rounds, emit):
     n, h, w = raw.shape
     pix = n * h * w
-    net = pipeline(arch)
+    net = SB.pipeline(arch)
     buf = {k: torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for k in ('classical', 'classical_bggr', 'composed', 'serve_u8')}
     route = PF.serve_route
 
@@ -104,18 +71,14 @@ def measure(arch, head, raw, reps, rounds, emit):
     assert net.last_serve_route == 'classical'
     torch.cuda.synchronize()
     assert torch.equal(buf['classical'], buf['composed']), 'the one launch and the composed route disagree'
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {k: SB.median(v) for k, v in res.items()}
     bpp = {'classical': 5, 'classical_bggr': 5, 'composed': composed_bytes_per_pixel(net.all_modules), 'serve_u8': 5}
     emit(' %s, %d x %d x %d, %d calls per round; us per call' % (arch, n, h, w, reps))
     for name, v in res.items():
-        emit('  %-14s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = bpp[name] * pix / (med[name] * 1e-6)
-        emit('  %-14s median %.1f us  min %.1f  spread %.1f   %d B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), max(v) - min(v), bpp[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
+        rounds_line, stats_line = SB.leg_lines(name, v, 14)
+        emit(rounds_line)
+        emit(stats_line + '   %d B/pixel: %s' % (bpp[name], SB.hbm_share(bpp[name] * pix, med[name])))
     emit('  classical / composed = %.3f   classical_bggr / classical = %.3f   classical / serve_u8 = %.3f   (%.0f MPix/s)' % (
         med['classical'] / med['composed'], med['classical_bggr'] / med['classical'], med['classical'] / med['serve_u8'],
         pix / med['classical']))
@@ -123,31 +86,19 @@ def measure(arch, head, raw, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_classical.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('net.serve(raw, out=buf), host side included; serve_u8: %s' % HEADLINE)
-    head = pipeline(HEADLINE)
-    batch, frame = frames_u16(64, 256, 256, 10), frames_u16(1, 3000, 4000, 20)
+    head = SB.pipeline(HEADLINE)
+    batch, frame = SB.frames_u16(64, 256, 256, 10, WHITE), SB.frames_u16(1, 3000, 4000, 20, WHITE)
     wins = []
     for arch in ARCHS:
         for raw, reps in ((batch, args.reps), (frame, max(20, args.reps // 3))):
             med = measure(arch, head, raw, reps, args.rounds, emit)
             wins.append(med['classical'] < med['composed'])
     emit('the one launch beats the composed route in %d of %d cases' % (sum(wins), len(wins)))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -18,35 +18,14 @@ Each round times every leg once (REPS calls, after 3 warm ones); per leg: the ro
 between the rounds of ONE leg is the noise a difference between two legs has to clear.  A configuration keeps its place in
 cond_plan when the composed median exceeds the cond median by more than the larger of the two spreads.  The bytes of the two
 legs are compared first.  Bytes moved are algorithmic counts from the module list."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
-
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
+import serve_bench as SB
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
 WHITE = 1023.0
 ARCHS = [(1, 'Demosaic_01_sRGB_16_14'), (2, 'Demosaic_01_sRGB_17_16_14'), (3, 'Demosaic_01_sRGB_17_18_16_14')]
 BINS = [4, 8]
-
-
-def frames_u16(n, h, w, seed):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
-
-
-def pipeline(arch, bins):
-    ch = [3 * bins, 8]
-    opt = {'network_G': {'which_model_G': 'IspUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8,
-                         'conditional_modules': {'gamma_in_channels': ch, 'wb_manual_in_channels': ch, 'wb_quadratic_in_channels': ch}}}
-    torch.manual_seed(10)
-    return networks.define_G(opt).cuda().eval()
 
 
 def bytes_per_pixel(modules):
@@ -63,23 +42,12 @@ def bytes_per_pixel(modules):
     return cond, total + src + 12 * run
 
 
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def measure(arch, bins, raw, reps, rounds, emit):
     n, h, w = raw.shape
     pix = n * h * w
-    net = pipeline(arch, bins)
+    ch = [3 * bins, 8]
+    net = SB.pipeline(arch, 'IspUniversal', conditional_modules={'gamma_in_channels': ch, 'wb_manual_in_channels': ch,
+                                                                  'wb_quadratic_in_channels': ch})
     buf = {k: torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for k in ('cond', 'composed')}
 
     def cond():
@@ -95,19 +63,15 @@ def measure(arch, bins, raw, reps, rounds, emit):
     assert net.last_serve_route == 'cond'
     torch.cuda.synchronize()
     assert torch.equal(buf['cond'], buf['composed']), 'the conditional route and the composed route disagree'
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {k: SB.median(v) for k, v in res.items()}
     bpp = dict(zip(('cond', 'composed'), bytes_per_pixel(net.all_modules)))
     emit(' %s, %d bins, %d x %d x %d, %d calls per round; us per call' % (arch, bins, n, h, w, reps))
     for name, v in res.items():
-        emit('  %-9s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        emit('  %-9s median %.1f us  min %.1f  spread %.1f   %d B/pixel: %.3f TB/s' % (
-            name, med[name], min(v), spread[name], bpp[name], bpp[name] * pix / (med[name] * 1e-6) / 1e12))
-    keeps = med['composed'] - med['cond'] > max(spread.values())
+        rounds_line, stats_line = SB.leg_lines(name, v, 9)
+        emit(rounds_line)
+        emit(stats_line + '   %d B/pixel: %.3f TB/s' % (bpp[name], bpp[name] * pix / (med[name] * 1e-6) / 1e12))
+    keeps = SB.beats(res['cond'], res['composed'])
     emit('  cond / composed = %.3f   (%.0f MPix/s against %.0f)   %s' % (
         med['cond'] / med['composed'], pix / med['cond'], pix / med['composed'],
         'beats the composed route by more than the larger spread' if keeps else 'does NOT clear the larger spread'))
@@ -115,20 +79,11 @@ def measure(arch, bins, raw, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=50)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_cond.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(50, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('net.serve(raw, out=buf[, fast_cond=True]), host side included')
-    batch, frame = frames_u16(64, 256, 256, 10), frames_u16(1, 3000, 4000, 20)
+    batch, frame = SB.frames_u16(64, 256, 256, 10, WHITE), SB.frames_u16(1, 3000, 4000, 20, WHITE)
     wins = {}
     for heads, arch in ARCHS:
         for bins in BINS:
@@ -136,10 +91,7 @@ def main():
                 wins.setdefault(heads, []).append(measure(arch, bins, raw, reps, args.rounds, emit))
     for heads, w in wins.items():
         emit('%d head%s: the conditional route clears the rule in %d of %d cases' % (heads, '' if heads == 1 else 's', sum(w), len(w)))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

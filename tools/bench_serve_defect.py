@@ -25,21 +25,13 @@ fused beats pass when median(pass) - median(fused) exceeds the larger of the two
 pipeline_fusion._DEFECT_SHADE_FUSED only if that holds at both sizes, and the line `verdict: _DEFECT_SHADE_FUSED = ...` says which
 (tests/test_defect_reference_cpu.py compares it with the table).  Bytes are algorithmic counts, the rate is those bytes over the
 median time."""
-import argparse
-import os
-import sys
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from bench_serve_packed import frames_int, pack, pipeline, timed  # noqa: E402
-from bench_serve_shade import vignette  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCH = 'Demosaic_02_sRGB_11_01_14'
 FORMATS = ['u16', 'raw10', 'raw12']
 WHITE, BLACK, CELL = 1023.0, 64, 64
@@ -50,14 +42,14 @@ def measure(net, shape, seed, fmt, reps, rounds, emit):
     n, h, w = shape
     pix = n * h * w
     bits = F.RAW_FORMAT[fmt] or 16
-    x = frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK
-    raw = (x.to(torch.uint16) if fmt == 'u16' else pack(x, bits)).cuda()
+    x = SB.frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK
+    raw = (x.to(torch.uint16) if fmt == 'u16' else SB.pack(x, bits)).cuda()
     fkw = {} if fmt == 'u16' else dict(raw_format=fmt, raw_width=w)
     rng = np.random.default_rng(seed)
     coords = np.stack([rng.integers(0, h, int(h * w * LISTED)), rng.integers(0, w, int(h * w * LISTED))], axis=1)
     bitmap = F.defect_map(coords, h, w).cuda()
     dyn, dc = (THRESHOLD, SLOPE, None), (THRESHOLD, SLOPE, bitmap)
-    shading = (F.shading_map(vignette(h, w), h, w, CELL).cuda(), CELL)
+    shading = (F.shading_map(SB.vignette(h, w), h, w, CELL).cuda(), CELL)
     out_f, out_p, out_d, out_s = (torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for _ in range(4))
     u16 = torch.empty((n, h, w), device='cuda', dtype=torch.uint16)
     io = bits / 8 + 2.0
@@ -103,26 +95,19 @@ def measure(net, shape, seed, fmt, reps, rounds, emit):
     assert torch.equal(out_f, out_p), 'one launch and two disagree'
     assert len(torch.unique(out_f)) > 32
     changed = (out_d != out_s).any(dim=-1).float().mean().item()
-    res = {k: [] for k in legs}
-    for r in range(rounds + 1):                             # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            t = timed(fn, reps)
-            if r:
-                res[name].append(t)
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, True)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %s, %d x %d x %d, %d calls per round; us per call; the correction changes %.2f %% of the served pixels' % (
         fmt, ARCH, n, h, w, reps, 100 * changed))
     for name, v in res.items():
-        emit('  %-10s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = bpp[name] * pix / (med[name] * 1e-6)
-        emit('  %-10s median %.1f us  min %.1f  spread %.1f   %.3f B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), spread[name], bpp[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
+        rounds_line, stats_line = SB.leg_lines(name, v, 10)
+        emit(rounds_line)
+        emit(stats_line + '   %.3f B/pixel: %s' % (bpp[name], SB.hbm_share(bpp[name] * pix, med[name])))
     emit('  (a) defect / shade = %.2f   defect_map / defect = %.2f%s' % (
         med['defect'] / med['shade'], med['defect_map'] / med['defect'],
         '   defect / unpack = %.2f' % (med['defect'] / med['unpack']) if 'unpack' in med else ''))
-    gain, noise = med['pass'] - med['fused'], max(spread['pass'], spread['fused'])
-    won = gain > noise
+    gain, noise = SB.margin(res['fused'], res['pass'])
+    won = SB.beats(res['fused'], res['pass'])
     emit('  (b) pass - fused = %.1f us against a spread of %.1f us: one launch %s   fused / pass = %.3f' % (
         gain, noise, 'BEATS two' if won else 'does NOT beat two', med['fused'] / med['pass']))
     emit('  (c) serve_dc - serve = %.1f us: serve_dc / serve = %.3f   (%.0f MPix/s with the correction)' % (
@@ -131,24 +116,15 @@ def measure(net, shape, seed, fmt, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_defect.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('(a) defect / defect_map / unpack / shade: the pre-pass launches alone   (b) fused / pass: net.serve(raw, out=, '
          'defect_correction=, lens_shading=) with one pre-pass launch or two   (c) serve_dc / serve: net.serve(raw, out=) with and '
          'without defect_correction; host side included')
     table = PF._DEFECT_SHADE_FUSED
     batch, frame = (64, 256, 256), (1, 3000, 4000)
-    net = pipeline(ARCH)
+    net = SB.pipeline(ARCH)
     rows = {}
     try:
         for fmt in FORMATS:
@@ -158,12 +134,9 @@ def main():
         PF._DEFECT_SHADE_FUSED = table
     for fmt in FORMATS:
         emit('%s: one launch beats two by more than the spread in %d of %d rows' % (fmt, sum(rows[fmt]), len(rows[fmt])))
-    emit('verdict: _DEFECT_SHADE_FUSED = %s' % (' '.join(f for f in FORMATS if all(rows[f])) or 'none'))
+    emit(SB.verdict_line('_DEFECT_SHADE_FUSED', [f for f in FORMATS if all(rows[f])]))
     emit('pipeline_fusion.defect_shade answers \'fused\' for: %s' % (', '.join(sorted(table)) or 'no format'))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

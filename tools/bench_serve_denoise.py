@@ -15,39 +15,15 @@ Each round times every leg once (REPS calls, after 3 warm ones); per leg: the ro
 between the rounds of ONE leg is the noise a difference between two legs has to clear.  The bytes of the two legs are compared
 first.  Bytes moved are algorithmic counts from the module list (fp32 planes written and read back by the composed route;
 2 read + 3 written by the one launch)."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
-
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from reconfigisp_amd.codes.models.modules import tools_origin as T  # noqa: E402
+import serve_bench as SB
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
+from reconfigisp_amd.codes.models.modules import tools_origin as T
 
 WHITE = 1023.0
 DEMOSAICS = [('bilinear', 2), ('malvar', 3)]
 DENOISERS = [('bilateral', 7), ('median', 8), ('fastnlm', 9)]
-
-
-def frames_u16(n, h, w, seed):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
-
-
-def pipeline(arch):
-    opt = {'network_G': {'which_model_G': 'OriginUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    net = networks.define_G(opt).cuda().eval()
-    for name, par in net.named_parameters():
-        if 'median' in name:                               # sigmoid(-2.5) < 1 / 7: the 3 x 3 window (the initial value gives 9 x 9)
-            with torch.no_grad():
-                par.fill_(-2.5)
-    return net
 
 
 def composed_bytes_per_pixel(modules):
@@ -68,23 +44,10 @@ def composed_bytes_per_pixel(modules):
     return total + flush()
 
 
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def measure(arch, raw, reps, rounds, emit):
     n, h, w = raw.shape
     pix = n * h * w
-    net = pipeline(arch)
+    net = SB.pipeline(arch, median=SB.MEDIAN_3X3)
     buf = {k: torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for k in ('denoise', 'composed')}
 
     def denoise():
@@ -100,37 +63,25 @@ def measure(arch, raw, reps, rounds, emit):
     assert net.last_serve_route == 'denoise'
     torch.cuda.synchronize()
     assert torch.equal(buf['denoise'], buf['composed']), 'the one launch and the composed route disagree'
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {k: SB.median(v) for k, v in res.items()}
     bpp = {'denoise': 5, 'composed': composed_bytes_per_pixel(net.all_modules)}
     emit(' %s, %d x %d x %d, %d calls per round; us per call' % (arch, n, h, w, reps))
     for name, v in res.items():
-        emit('  %-9s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        emit('  %-9s median %.1f us  min %.1f  spread %.1f   %d B/pixel: %.3f TB/s' % (
-            name, med[name], min(v), max(v) - min(v), bpp[name], bpp[name] * pix / (med[name] * 1e-6) / 1e12))
+        rounds_line, stats_line = SB.leg_lines(name, v, 9)
+        emit(rounds_line)
+        emit(stats_line + '   %d B/pixel: %.3f TB/s' % (bpp[name], bpp[name] * pix / (med[name] * 1e-6) / 1e12))
     emit('  denoise / composed = %.3f   (%.0f MPix/s against %.0f)' % (
         med['denoise'] / med['composed'], pix / med['denoise'], pix / med['composed']))
     return med
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=100)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_denoise.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(100, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('net.serve(raw, out=buf[, fast_denoise=True]), host side included')
-    batch, frame = frames_u16(64, 256, 256, 10), frames_u16(1, 3000, 4000, 20)
+    batch, frame = SB.frames_u16(64, 256, 256, 10, WHITE), SB.frames_u16(1, 3000, 4000, 20, WHITE)
     wins = {}
     for den, code in DENOISERS:
         for dem, kind in DEMOSAICS:
@@ -140,10 +91,7 @@ def main():
                 wins.setdefault(den, []).append(med['denoise'] < med['composed'])
     for den, w in wins.items():
         emit('%s: the one launch beats the composed route in %d of %d cases' % (den, sum(w), len(w)))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

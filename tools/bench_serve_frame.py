@@ -19,26 +19,21 @@ three legs are compared first.
 The blend step alone, on a random stack of the same geometry: risp_tile_blend_u8 against risp_tile_blend + risp_quantise_u8
 into a preallocated fp32 frame, the same way.  Bytes are algorithmic counts from the shapes (the forward is the same in every
 leg and is left out)."""
-import argparse
 import contextlib
 import io
-import os
-import sys
 from collections import OrderedDict
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd import lib as L  # noqa: E402
-from reconfigisp_amd.codes.data.gpu_input import raw_crops  # noqa: E402
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import create_model  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from reconfigisp_amd.codes.test_split import run_frame  # noqa: E402
-from reconfigisp_amd.codes.utils.util_path_restore import blend_tiles, gather_tiles, tile_grid  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd import lib as L
+from reconfigisp_amd.codes.data.gpu_input import raw_crops
+from reconfigisp_amd.codes.models import create_model
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
+from reconfigisp_amd.codes.test_split import run_frame
+from reconfigisp_amd.codes.utils.util_path_restore import blend_tiles, gather_tiles, tile_grid
 
 WHITE = 1023.0
 ARCH = 'Bayer_01_Demosaic_02_sRGB_13'
@@ -57,56 +52,31 @@ def model():
     return m
 
 
-def timed(fn, reps):
-    for _ in range(2):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def rounds_of(legs, reps, rounds):
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps[name]))
-    return res
+    """two warm calls per leg and round, as the recorded profile was measured"""
+    return SB.rounds_of(legs, reps, rounds, False, lambda fn, n: SB.timed(fn, n, warm=2))
 
 
 def report(res, bytes_moved, emit, rate):
     """``rate``: the legs are nothing but those bytes (the blend step alone), so bytes over time is a rate worth printing"""
     med = {}
     for name, v in res.items():
-        med[name] = sorted(v)[len(v) // 2]
-        emit('  %-13s rounds %s' % (name, ' '.join('%.0f' % t for t in v)))
-        emit('  %-13s median %.0f us  min %.0f  spread %.0f   %.0f MB %s' % (
-            name, med[name], min(v), max(v) - min(v), bytes_moved[name] / 1e6,
+        med[name] = SB.median(v)
+        rounds_line, stats_line = SB.leg_lines(name, v, 13, '%.0f')
+        emit(rounds_line)
+        emit(stats_line + '   %.0f MB %s' % (
+            bytes_moved[name] / 1e6,
             ': %.2f TB/s' % (bytes_moved[name] / (med[name] * 1e-6) / 1e12) if rate else 'at its two ends (the forward not counted)'))
     return med
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=10)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_frame.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(10, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     m = model()
     net = m.netG
-    bay = make_batch(1, H, W, seed=20)[0][:, 0]
-    raw = (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()[0]        # (H,W) uint16
+    raw = SB.frames_u16(1, H, W, 20, WHITE)[0]                                                    # (H,W) uint16
     frame32 = torch.from_numpy(raw.cpu().to(torch.int32).numpy().astype(np.float32) / np.float32(WHITE))[None, None].cuda()
     pos = tile_grid(H, W, SIZE, STRIDE)
     pos_dev = torch.from_numpy(pos).cuda()
@@ -181,10 +151,7 @@ def main():
     emit(' the blend step alone, random (%d,3,%d,%d) stack, %d calls per round; us per call' % (count, SIZE[0], SIZE[1], 5 * args.reps))
     med = report(rounds_of(steps, {k: 5 * args.reps for k in steps}, args.rounds), {'blend_u8': back_u8, 'blend+quant': back_two}, emit, True)
     emit('  blend_u8 / blend+quant = %.3f' % (med['blend_u8'] / med['blend+quant']))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

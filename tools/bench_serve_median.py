@@ -17,60 +17,23 @@ Each round times every leg once (REPS calls, after 3 warm ones); per leg: the ro
 between the rounds of ONE leg is the noise a difference between two legs has to clear.  The bytes of route and default are
 compared first.  The rule for _MEDIAN_SIZES: a size is listed only where the route beats the default call by more than the
 larger spread of the two legs in all four rows of that size (both demosaics, both frame sizes)."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
-
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd import lib as L  # noqa: E402
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd import lib as L
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
 WHITE = 1023.0
 DEMOSAICS = [('bilinear', 2), ('laplacian', 3)]
 SIZES = [5, 7, 9, 11, 13, 15]
 
 
-def frames_u16(n, h, w, seed):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
-
-
-def pipeline(arch, k):
-    opt = {'network_G': {'which_model_G': 'OriginUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    net = networks.define_G(opt).cuda().eval()
-    p = ((k - 3) // 2 + 0.5) / 7                           # the middle of the parameter range that gives size k
-    for name, par in net.named_parameters():
-        if 'median' in name:
-            with torch.no_grad():
-                par.fill_(float(torch.logit(torch.tensor(p))))
-    return net
-
-
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def measure(dem, kind, k, raw, planes, reps, rounds, emit):
     n, h, w = raw.shape
     arch = 'Demosaic_%02d_sRGB_11_08_01' % kind
-    net = pipeline(arch, k)
+    p = ((k - 3) // 2 + 0.5) / 7                           # the middle of the parameter range that gives size k
+    net = SB.pipeline(arch, median=float(torch.logit(torch.tensor(p))))
     buf = {name: torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for name in ('route', 'default')}
     x, y = planes
 
@@ -92,16 +55,13 @@ def measure(dem, kind, k, raw, planes, reps, rounds, emit):
     assert net.last_serve_route == 'denoise' and calls == {'risp_serve_median_u8': 1}, calls
     torch.cuda.synchronize()
     assert torch.equal(buf['route'], buf['default']), 'the one launch and the default call disagree'
-    res = {name: [] for name in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {name: sorted(v)[len(v) // 2] for name, v in res.items()}
-    spread = {name: max(v) - min(v) for name, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {name: SB.median(v) for name, v in res.items()}
+    spread = {name: SB.spread(v) for name, v in res.items()}
     emit(' %s, median %d x %d, %d x %d x %d, %d calls per round; us per call' % (arch, k, k, n, h, w, reps))
     for name, v in res.items():
-        emit('  %-8s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-    won = med['default'] - med['route'] > max(spread['route'], spread['default'])
+        emit(SB.leg_lines(name, v, 8)[0])
+    won = SB.beats(res['route'], res['default'])
     emit('  K=%-2d %-9s %dx%dx%d  route %.1f +- %.1f us  default %.1f +- %.1f us  median alone %.1f +- %.1f us  '
          'route / default = %.3f  route - median alone = %.1f us  %s' % (
              k, dem, n, h, w, med['route'], spread['route'], med['default'], spread['default'], med['median'], spread['median'],
@@ -110,23 +70,14 @@ def measure(dem, kind, k, raw, planes, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=100)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_median.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(100, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('net.serve(raw, out=buf[, fast_median=True]), host side included; (+- is the spread between the rounds of a leg)')
     PF._MEDIAN_SIZES = frozenset(SIZES)                    # the measurement decides the table: every size takes the launch here
     sets = []
     for shape, seed, reps in (((64, 256, 256), 10, args.reps), ((1, 3000, 4000), 20, max(5, args.reps // 3))):
-        raw = frames_u16(*shape, seed)
+        raw = SB.frames_u16(*shape, seed, WHITE)
         x = torch.rand((shape[0], 3) + shape[1:], device='cuda')
         sets.append((raw, (x, torch.empty_like(x)), reps))
     wins = {k: [] for k in SIZES}
@@ -138,10 +89,7 @@ def main():
     lost = [k for k in SIZES if not all(wins[k])]
     emit('fast_median=True beats the default call by more than the spread at both sizes for: %s' % (', '.join(map(str, won)) or '-'))
     emit('and does not for: %s' % (', '.join(map(str, lost)) or '-'))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

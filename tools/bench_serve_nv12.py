@@ -17,53 +17,20 @@ Each round times every leg once (REPS calls, after 3 warm ones); per leg: the ro
 between the rounds of ONE leg is the noise a difference between two legs has to clear.  The bytes of (b) and (c) are compared
 first.  Verdict per case: (c) beats (b) when median(b) - median(c) exceeds the larger of the two spreads; (c) / (a) is
 reported.  Bytes are algorithmic counts, the share of HBM peak is those bytes over the median time."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-
-HBM_PEAK = 8.0e12
 WHITE = 1023.0
 ARCHS = [('Demosaic_01_sRGB_07_11_01_14', 'fused'), ('Demosaic_02_sRGB_11_01_14', 'classical')]
 BPP = {'bgr': 5.0, 'bgr_pass': 9.5, 'nv12': 3.5, 'pass': 4.5, 'bgr_bggr': 5.0, 'nv12_bggr': 3.5}
 
 
-def frames_u16(n, h, w, seed):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * WHITE).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
-
-
-def pipeline(arch):
-    opt = {'network_G': {'which_model_G': 'OriginUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    return networks.define_G(opt).cuda().eval()
-
-
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def measure(arch, route, raw, reps, rounds, emit):
     n, h, w = raw.shape
     pix = n * h * w
-    net = pipeline(arch)
+    net = SB.pipeline(arch)
     bgr = torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8)
     yuv_b, yuv_c = (torch.empty((n, h + h // 2, w), device='cuda', dtype=torch.uint8) for _ in range(2))
 
@@ -92,20 +59,15 @@ def measure(arch, route, raw, reps, rounds, emit):
     assert net.last_serve_route == route and net.last_serve_store == 'fused'
     torch.cuda.synchronize()
     assert torch.equal(yuv_b, yuv_c), 'the fused NV12 store and the conversion launch disagree'
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s (%s), %d x %d x %d, %d calls per round; us per call' % (arch, route, n, h, w, reps))
     for name, v in res.items():
-        emit('  %-9s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = BPP[name] * pix / (med[name] * 1e-6)
-        emit('  %-9s median %.1f us  min %.1f  spread %.1f   %.1f B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), spread[name], BPP[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
-    gain, noise = med['bgr_pass'] - med['nv12'], max(spread['bgr_pass'], spread['nv12'])
-    won = gain > noise
+        rounds_line, stats_line = SB.leg_lines(name, v, 9)
+        emit(rounds_line)
+        emit(stats_line + '   %.1f B/pixel: %s' % (BPP[name], SB.hbm_share(BPP[name] * pix, med[name])))
+    gain, noise = SB.margin(res['nv12'], res['bgr_pass'])
+    won = SB.beats(res['nv12'], res['bgr_pass'])
     emit('  (b) - (c) = %.1f us against a spread of %.1f us: the fused store %s   (c) / (b) = %.3f   (c) / (a) = %.3f   '
          'nv12_bggr / bgr_bggr = %.3f   (%.0f MPix/s)' % (
              gain, noise, 'BEATS the conversion launch' if won else 'does NOT beat the conversion launch', med['nv12'] / med['bgr_pass'],
@@ -114,30 +76,18 @@ def measure(arch, route, raw, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_nv12.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('(a) bgr: net.serve(raw, out=)   (b) bgr_pass: (a) + bgr8_to_nv12(out=)   (c) nv12: net.serve(raw, out=, out_format=nv12)   '
          'pass: bgr8_to_nv12(out=) alone; matrix bt601_full, host side included')
-    batch, frame = frames_u16(64, 256, 256, 10), frames_u16(1, 3000, 4000, 20)
+    batch, frame = SB.frames_u16(64, 256, 256, 10, WHITE), SB.frames_u16(1, 3000, 4000, 20, WHITE)
     wins = []
     for arch, route in ARCHS:
         for raw, reps in ((batch, args.reps), (frame, max(20, args.reps // 3))):
             wins.append(measure(arch, route, raw, reps, args.rounds, emit))
     emit('the fused NV12 store beats BGR + conversion by more than the spread in %d of %d cases' % (sum(wins), len(wins)))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -19,60 +19,14 @@ between the rounds of ONE leg is the noise a difference between two legs has to 
 compared first.  Verdict per case: (c) beats (b) when median(b) - median(c) exceeds the larger of the two spreads; a route keeps
 its fused load for a format when that holds on the 3000 x 4000 frame.  (c) / (a) is reported, not judged.  Bytes are
 algorithmic counts, the share of HBM peak is those bytes over the median time."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCHS = [('Demosaic_01_sRGB_07_11_01_14', 'fused'), ('Demosaic_02_sRGB_11_01_14', 'classical')]
 ALL_FUSED = frozenset((route, fmt) for route in ('fused', 'classical') for fmt in ('raw10', 'raw12'))
-
-
-def frames_int(n, h, w, seed, white):
-    bay = make_batch(n, h, w, seed=seed)[0][:, 0]
-    return (bay * white).round().clamp(0, white).to(torch.int32)
-
-
-def pack(x, bits):
-    """(N,H,W) int32 samples below 2^bits -> (N,H,W * bits / 8) uint8 on the host (include/risp.h has the layout)"""
-    n, h, w = x.shape
-    if bits == 10:
-        g = x.view(n, h, w // 4, 4)
-        low = (g[..., 0] & 3) | (g[..., 1] & 3) << 2 | (g[..., 2] & 3) << 4 | (g[..., 3] & 3) << 6
-        grp = torch.cat([g >> 2, low[..., None]], dim=-1)
-    else:
-        g = x.view(n, h, w // 2, 2)
-        grp = torch.cat([g >> 4, ((g[..., 0] & 15) | (g[..., 1] & 15) << 4)[..., None]], dim=-1)
-    return grp.to(torch.uint8).reshape(n, h, w * bits // 8).contiguous()
-
-
-def pipeline(arch):
-    opt = {'network_G': {'which_model_G': 'OriginUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    return networks.define_G(opt).cuda().eval()
-
-
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
 
 
 def measure(arch, route, shape, seed, fmt, out_format, reps, rounds, emit):
@@ -80,10 +34,10 @@ def measure(arch, route, shape, seed, fmt, out_format, reps, rounds, emit):
     bits = F.RAW_FORMAT[fmt]
     white = float((1 << bits) - 1)
     pix = n * h * w
-    x = frames_int(n, h, w, seed, white)
-    raw, packed = x.to(torch.uint16).cuda(), pack(x, bits).cuda()
+    x = SB.frames_int(n, h, w, seed, white)
+    raw, packed = x.to(torch.uint16).cuda(), SB.pack(x, bits).cuda()
     assert torch.equal(F.raw_unpack(packed, bits, w).cpu(), raw.cpu()), 'the unpack launch and the host packer disagree'
-    net = pipeline(arch)
+    net = SB.pipeline(arch)
     nv12 = out_format == 'nv12'
     oshape = (n, h + h // 2, w) if nv12 else (n, h, w, 3)
     out_a, out_b, out_c = (torch.empty(oshape, device='cuda', dtype=torch.uint8) for _ in range(3))
@@ -109,20 +63,15 @@ def measure(arch, route, shape, seed, fmt, out_format, reps, rounds, emit):
     assert net.last_serve_route == route and net.last_serve_load == 'fused'
     torch.cuda.synchronize()
     assert torch.equal(out_a, out_b) and torch.equal(out_a, out_c), 'the legs disagree'
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s (%s), %d x %d x %d, %s in, %s out, %d calls per round; us per call' % (arch, route, n, h, w, fmt, out_format, reps))
     for name, v in res.items():
-        emit('  %-10s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = bpp[name] * pix / (med[name] * 1e-6)
-        emit('  %-10s median %.1f us  min %.1f  spread %.1f   %.2f B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), spread[name], bpp[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
-    gain, noise = med['unpack_u16'] - med['packed'], max(spread['unpack_u16'], spread['packed'])
-    won = gain > noise
+        rounds_line, stats_line = SB.leg_lines(name, v, 10)
+        emit(rounds_line)
+        emit(stats_line + '   %.2f B/pixel: %s' % (bpp[name], SB.hbm_share(bpp[name] * pix, med[name])))
+    gain, noise = SB.margin(res['packed'], res['unpack_u16'])
+    won = SB.beats(res['packed'], res['unpack_u16'])
     emit('  (b) - (c) = %.1f us against a spread of %.1f us: the fused load %s   (c) / (b) = %.3f   (c) / (a) = %.3f   (%.0f MPix/s)' % (
         gain, noise, 'BEATS the unpack launch' if won else 'does NOT beat the unpack launch', med['packed'] / med['unpack_u16'],
         med['packed'] / med['u16'], pix / med['packed']))
@@ -130,18 +79,9 @@ def measure(arch, route, shape, seed, fmt, out_format, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_packed.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('(a) u16: net.serve(raw_u16, out=)   (b) unpack_u16: raw_unpack(packed, out=) + (a)   (c) packed: net.serve(packed, out=, '
          'raw_format=) with the fused load   unpack: raw_unpack(out=) alone; host side included')
     table = PF._FUSED_LOAD
@@ -163,10 +103,7 @@ def main():
     emit('                                                                      and does not for: %s' % (
         ', '.join('%s/%s' % k for k, v in sorted(verdict.items()) if not v) or 'no route'))
     emit('pipeline_fusion.serve_load answers \'fused\' for: %s' % (', '.join('%s/%s' % k for k in sorted(table)) or 'no route'))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

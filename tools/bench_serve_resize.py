@@ -23,19 +23,12 @@ of fused and pass are compared first.  Row verdict: fused beats pass when median
 two spreads; 'nv12' enters pipeline_fusion._RESIZE_NV12_FUSED only if that holds in all four rows, and the line
 `verdict: _RESIZE_NV12_FUSED = ...` says so (tests/test_resize_reference_cpu.py compares it with the table).  Bytes are
 algorithmic counts, the rate is those bytes over the median time."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from bench_serve_packed import frames_int, pipeline, timed  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCH = 'Demosaic_02_sRGB_11_01_14'
 WHITE, BLACK = 1023.0, 64
 MATRIX = 'bt709_video'
@@ -46,7 +39,7 @@ def measure(net, shape, size, window, seed, reps, rounds, emit):
     n, h, w = shape
     oh, ow = size
     y0, x0, wh, ww = window if window is not None else (0, 0, h, w)
-    raw = (frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
+    raw = (SB.frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
     img = net.serve(raw, WHITE, black_level=BLACK).clone()
     assert net.last_serve_route == 'classical'
     u8 = lambda *s: torch.empty(s, device='cuda', dtype=torch.uint8)
@@ -86,30 +79,22 @@ def measure(net, shape, size, window, seed, reps, rounds, emit):
     theirs = leg_serve_torch()
     diff = (theirs.int() - out_rs.int()).abs()
     assert len(torch.unique(out_rs)) > 32
-    res = {k: [] for k in legs}
-    for r in range(rounds + 1):                             # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            t = timed(fn, reps)
-            if r:
-                res[name].append(t)
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, True)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %d x %d x %d, window %s -> %d x %d, %d calls per round; us per call; tile rows %d, span %d; torch differs from '
          'serve_rs in %.1f %% of the bytes, by at most %d' % (ARCH, n, h, w, (y0, x0, wh, ww), oh, ow, reps,
                                                               *F.resize_tile_rows(wh, oh, 'triangle', y0),
                                                               100 * (diff > 0).float().mean().item(), diff.max().item()))
     for name, v in res.items():
-        emit('  %-14s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        line = '  %-14s median %.1f us  min %.1f  spread %.1f' % (name, med[name], min(v), spread[name])
+        rounds_line, line = SB.leg_lines(name, v, 14)
+        emit(rounds_line)
         if nbytes[name] is not None:
-            rate = nbytes[name] / (med[name] * 1e-6)
-            line += '   %.1f MB: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (nbytes[name] / 1e6, rate / 1e12, 100 * rate / HBM_PEAK,
-                                                                                  HBM_PEAK / 1e12)
+            line += '   %.1f MB: %s' % (nbytes[name] / 1e6, SB.hbm_share(nbytes[name], med[name]))
         emit(line)
     won = []
     for k in VERDICT_KERNELS:
-        gain, noise = med['pass_' + k] - med['fused_' + k], max(spread['pass_' + k], spread['fused_' + k])
-        won.append(gain > noise)
+        gain, noise = SB.margin(res['fused_' + k], res['pass_' + k])
+        won.append(SB.beats(res['fused_' + k], res['pass_' + k]))
         emit('  (b) %-8s pass - fused = %.1f us against a spread of %.1f us: the fused store %s   fused / pass = %.3f' % (
             k, gain, noise, 'BEATS two launches' if won[-1] else 'does NOT beat two launches', med['fused_' + k] / med['pass_' + k]))
     emit('  (c) serve_rs - serve = %.1f us: serve_rs / serve = %.3f;  serve_torch - serve = %.1f us: serve_rs / serve_torch = %.3f   '
@@ -120,32 +105,20 @@ def measure(net, shape, size, window, seed, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_resize.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('(a) bgr_K / nv12_K: the resize launch alone   (b) fused_K / pass_K: NV12 from the resize launch or from resize-to-BGR plus '
          'risp_bgr8_to_nv12   (c) serve_rs / serve / serve_torch: net.serve(raw, out=) with out_size, without, and followed by '
          'torch.nn.functional.interpolate; host side included')
-    net = pipeline(ARCH)
+    net = SB.pipeline(ARCH)
     rows = []
     rows += measure(net, (1, 3000, 4000), (1080, 1920), (375, 0, 2250, 4000), 20, max(20, args.reps // 3), args.rounds, emit)
     rows += measure(net, (64, 256, 256), (128, 128), None, 10, args.reps, args.rounds, emit)
     emit('the fused NV12 store beats two launches by more than the spread in %d of %d rows' % (sum(rows), len(rows)))
-    emit('verdict: _RESIZE_NV12_FUSED = %s' % ('nv12' if all(rows) else 'none'))
+    emit(SB.verdict_line('_RESIZE_NV12_FUSED', ['nv12'] if all(rows) else []))
     emit("pipeline_fusion.resize_store('nv12') answers %r" % PF.resize_store('nv12'))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -13,23 +13,17 @@ the host side included (what a caller pays), timed between two device events:
 Each round times every leg once (REPS calls, after 3 warm ones); per leg: the rounds, median, minimum and spread - the spread
 between the rounds of ONE leg is the noise a difference between two legs has to clear.  The bytes of the two legs are compared
 first and the number that differ is printed (gray-world and Reinhard sum in another order: rounding ties may differ by one)."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-import torch  # noqa: E402
-
-from bench_serve_classical import WHITE, frames_u16, pipeline, timed  # noqa: E402
+import serve_bench as SB
+from bench_serve_classical import WHITE
 
 ARCHS = [('Demosaic_02_sRGB_05_01', 1), ('Demosaic_03_sRGB_06_02', 2)]
 
 
 def measure(arch, scenes, raw, reps, rounds, emit):
     n, h, w = raw.shape
-    net = pipeline(arch)
+    net = SB.pipeline(arch)
     buf = {k: torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for k in ('scene', 'composed')}
     legs = {'scene': lambda: net.serve(raw, WHITE, out=buf['scene'], fast_scene=True),
             'composed': lambda: net.serve(raw, WHITE, out=buf['composed'])}
@@ -40,45 +34,30 @@ def measure(arch, scenes, raw, reps, rounds, emit):
     torch.cuda.synchronize()
     d = (buf['scene'].int() - buf['composed'].int()).abs()
     assert d.max().item() <= 1, 'the scene route and the composed route differ by more than a rounding tie'
-    res = {k: [] for k in legs}
-    for _ in range(rounds):
-        for name, fn in legs.items():
-            res[name].append(timed(fn, reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, False)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s (%d scene stage%s), %d x %d x %d, %d calls per round; us per call; %d of %d bytes differ by one' % (
         arch, scenes, 's' * (scenes > 1), n, h, w, reps, int((d != 0).sum().item()), d.numel()))
     for name, v in res.items():
-        emit('  %-9s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        emit('  %-9s median %.1f us  min %.1f  spread %.1f' % (name, med[name], min(v), max(v) - min(v)))
+        for line in SB.leg_lines(name, v, 9):
+            emit(line)
     emit('  scene / composed = %.3f   (%.0f MPix/s)' % (med['scene'] / med['composed'], n * h * w / med['scene']))
     return med
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_scene.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('net.serve(raw, out=buf), host side included')
-    batch, frame = frames_u16(64, 256, 256, 10), frames_u16(1, 3000, 4000, 20)
+    batch, frame = SB.frames_u16(64, 256, 256, 10, WHITE), SB.frames_u16(1, 3000, 4000, 20, WHITE)
     wins = []
     for arch, scenes in ARCHS:
         for raw, reps in ((batch, args.reps), (frame, max(20, args.reps // 3))):
             med = measure(arch, scenes, raw, reps, args.rounds, emit)
             wins.append(med['scene'] < med['composed'])
     emit('the scene route beats the composed route in %d of %d cases' % (sum(wins), len(wins)))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -23,23 +23,14 @@ compared first.  Row verdict: fused beats pass when median(pass) - median(fused)
 says which (tests/test_lens_shading_reference_cpu.py compares it with the table).  u16 against u16_parent shows whether the
 existing instantiations saw the new template parameter: their difference has to lie within the spreads.  Bytes are algorithmic
 counts, the share of HBM peak is those bytes over the median time."""
-import argparse
-import ctypes as C
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd import lib as L
+from reconfigisp_amd.codes.data.synthetic_raw import make_batch
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd import lib as L  # noqa: E402
-from reconfigisp_amd.codes.data.synthetic_raw import make_batch  # noqa: E402
-from reconfigisp_amd.codes.models import networks  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCHS = ['Demosaic_02_sRGB_11_01_14', 'Demosaic_03_sRGB_11_04_01']
 ENTRY = ('classical', 'u16')
 WHITE, BLACK, CELL = 4095.0, 64, 64
@@ -47,47 +38,13 @@ CALL = 'risp_serve_classical_u8'
 PARENT = None           # --parent-lib: risp_serve_classical_u8 of a second build of the library, bound with the same signature
 
 
-def load_parent(path):
-    global PARENT
-    lib = C.CDLL(os.path.abspath(path))
-    PARENT = getattr(lib, CALL)
-    PARENT.restype, PARENT.argtypes = L.SIGNATURES[CALL]
-
-
-def pipeline(arch):
-    opt = {'network_G': {'which_model_G': 'OriginUniversal', 'architecture': arch, 'module_path': None,
-                         'individual_module_paths': [None] * 8}}
-    torch.manual_seed(10)
-    return networks.define_G(opt).cuda().eval()
-
-
-def vignette(h, w):
-    """a (4,33,33) gain image: 1 at the centre, up to 2 in the corners, a little colour shading between the planes"""
-    y, x = np.meshgrid(np.linspace(-1, 1, 33), np.linspace(-1, 1, 33), indexing='ij')
-    r2 = (y * y + x * x) / 2
-    return np.stack([1 + (0.85 + 0.05 * c) * r2 for c in range(4)])
-
-
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3
-
-
 def measure(arch, shape, seed, reps, rounds, emit):
     n, h, w = shape
     pix = n * h * w
     bay = make_batch(n, h, w, seed=seed)[0][:, 0]
     raw = (bay * (WHITE - BLACK) + BLACK).round().clamp(0, WHITE).to(torch.int32).to(torch.uint16).cuda()
-    shading = (F.shading_map(vignette(h, w), h, w, CELL).cuda(), CELL)
-    net = pipeline(arch)
+    shading = (F.shading_map(SB.vignette(h, w), h, w, CELL).cuda(), CELL)
+    net = SB.pipeline(arch)
     out_f, out_p, out_u = (torch.empty((n, h, w, 3), device='cuda', dtype=torch.uint8) for _ in range(3))
     shaded = torch.empty((n, h, w), device='cuda', dtype=torch.uint16)
     bpp = {'fused': 2 + 3.0, 'pass': 2 + 2 + 2 + 3.0, 'u16': 2 + 3.0, 'u16_parent': 2 + 3.0, 'shade': 2 + 2.0}
@@ -106,9 +63,19 @@ def measure(arch, shape, seed, reps, rounds, emit):
     def leg_shade():
         F.raw_shade(raw, shading, BLACK, out=shaded)
 
-    legs = {'fused': leg_fused, 'pass': leg_pass, 'u16': leg_u16, 'shade': leg_shade}
+    own = getattr(L.load(), CALL)
+    legs = {'fused': (leg_fused, own), 'pass': (leg_pass, own), 'u16': (leg_u16, own), 'shade': (leg_shade, own)}
     if PARENT is not None:
-        legs['u16_parent'] = leg_u16
+        legs['u16_parent'] = (leg_u16, PARENT)
+
+    def timed_bound(leg, reps):                             # a leg is (call, the build whose kernel is bound while it is timed)
+        fn, kernel = leg
+        L._FN[CALL] = kernel
+        try:
+            return SB.timed(fn, reps)
+        finally:
+            L._FN[CALL] = own
+
     leg_shade(), leg_fused()
     assert net.last_serve_route == 'classical' and net.last_serve_shade == 'fused'
     leg_pass()
@@ -117,17 +84,7 @@ def measure(arch, shape, seed, reps, rounds, emit):
     torch.cuda.synchronize()
     assert torch.equal(out_f, out_p) and torch.equal(out_f, out_u), 'the legs disagree'
     assert len(torch.unique(out_f)) > 32
-    own = getattr(L.load(), CALL)
-    res = {k: [] for k in legs}
-    for r in range(rounds + 1):                             # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            L._FN[CALL] = PARENT if name == 'u16_parent' else own
-            try:
-                t = timed(fn, reps)
-            finally:
-                L._FN[CALL] = own
-            if r:
-                res[name].append(t)
+    res = SB.rounds_of(legs, reps, rounds, True, timed_bound)
     if PARENT is not None:
         out_u.zero_()
         L._FN[CALL] = PARENT
@@ -137,44 +94,34 @@ def measure(arch, shape, seed, reps, rounds, emit):
             L._FN[CALL] = own
         torch.cuda.synchronize()
         assert torch.equal(out_u, out_f), 'the parent build and this one disagree'
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %d x %d x %d, cell %d, %d calls per round; us per call' % (arch, n, h, w, CELL, reps))
     for name, v in res.items():
-        emit('  %-10s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = bpp[name] * pix / (med[name] * 1e-6)
-        emit('  %-10s median %.1f us  min %.1f  spread %.1f   %.2f B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), spread[name], bpp[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
-    gain, noise = med['pass'] - med['fused'], max(spread['pass'], spread['fused'])
-    won = gain > noise
+        rounds_line, stats_line = SB.leg_lines(name, v, 10)
+        emit(rounds_line)
+        emit(stats_line + '   %.2f B/pixel: %s' % (bpp[name], SB.hbm_share(bpp[name] * pix, med[name])))
+    gain, noise = SB.margin(res['fused'], res['pass'])
+    won = SB.beats(res['fused'], res['pass'])
     emit('  pass - fused = %.1f us against a spread of %.1f us: the fused shading load %s   fused / pass = %.3f   fused / u16 = %.3f   '
          '(%.0f MPix/s)' % (gain, noise, 'BEATS the shade launch' if won else 'does NOT beat the shade launch',
                             med['fused'] / med['pass'], med['fused'] / med['u16'], pix / med['fused']))
     if PARENT is not None:
-        diff, noise = med['u16'] - med['u16_parent'], max(spread['u16'], spread['u16_parent'])
+        diff, noise = SB.margin(res['u16_parent'], res['u16'])
         emit('  u16 - u16_parent = %.1f us against a spread of %.1f us: the existing instantiation is %s' % (
             diff, noise, 'within the noise of the parent build\'s' if abs(diff) <= noise else 'NOT within the noise of the parent build\'s'))
     return won
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
+    global PARENT
+    ap = SB.parser(300, 7)
     ap.add_argument('--parent-lib', default=None, help='a second build of libreconfigisp_hip.so (the parent commit\'s): its '
                     'risp_serve_classical_u8 is timed in the same rounds as leg u16_parent')
     args = ap.parse_args()
     if args.parent_lib:
-        load_parent(args.parent_lib)
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_shade.py --reps %d --rounds %d%s   (%s)' % (args.reps, args.rounds, ' --parent-lib <the parent commit\'s build>'
-                                                                       if args.parent_lib else '', torch.cuda.get_device_name(0)))
+        PARENT = getattr(SB.load_parent(args.parent_lib, [CALL]), CALL)
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args, ' --parent-lib <the parent commit\'s build>' if args.parent_lib else ''))
     emit('fused: net.serve(raw, out=, lens_shading=) with the fused shading load   pass: the same call, risp_raw_shade first   '
          'u16: net.serve(shaded, out=)   u16_parent: u16 with the parent build\'s kernel   shade: raw_shade(out=) alone; host side included')
     table = PF._FUSED_SHADE
@@ -187,12 +134,9 @@ def main():
     finally:
         PF._FUSED_SHADE = table
     emit('the fused shading load beats shade launch + uint16 call by more than the spread in %d of %d rows' % (sum(rows), len(rows)))
-    emit('verdict: _FUSED_SHADE = %s' % ('/'.join(ENTRY) if all(rows) else 'none'))
+    emit(SB.verdict_line('_FUSED_SHADE', ['/'.join(ENTRY)] if all(rows) else []))
     emit('pipeline_fusion.serve_shade answers \'fused\' for: %s' % (', '.join('%s/%s' % k for k in sorted(table)) or 'no route'))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -25,19 +25,12 @@ of fused and pass are compared first.  Row verdict: fused beats pass when median
 two spreads; 'nv12' enters pipeline_fusion._SHARPEN_NV12_FUSED only if that holds in every row, and the line
 `verdict: _SHARPEN_NV12_FUSED = ...` says so (tests/test_sharpen_reference_cpu.py compares it with the table).  Bytes are
 algorithmic counts (6 per pixel for BGR out, 4.5 for NV12), the rate is those bytes over the median time.  No counters are read."""
-import argparse
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from bench_serve_packed import frames_int, pipeline, timed  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCH = 'Demosaic_02_sRGB_11_01_14'
 WHITE, BLACK = 1023.0, 64
 MATRIX = 'bt709_video'
@@ -61,7 +54,7 @@ def torch_sharpen(img, sharpen):
 
 def measure(net, shape, resize, seed, reps, rounds, emit):
     n, h, w = shape
-    raw = (frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
+    raw = (SB.frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
     rkw = {} if resize is None else dict(out_size=resize[0], out_window=resize[1])
     img = net.serve(raw, WHITE, black_level=BLACK, **rkw).clone()
     assert net.last_serve_route == 'classical'
@@ -103,31 +96,23 @@ def measure(net, shape, resize, seed, reps, rounds, emit):
     diff = (theirs.int() - out_sv.int()).abs()
     changed = (out_sv != img).float().mean().item()
     assert len(torch.unique(out_sv)) > 32 and changed > 0.05
-    res = {k: [] for k in legs}
-    for rnd in range(rounds + 1):                           # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            t = timed(fn, reps)
-            if rnd:
-                res[name].append(t)
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, True)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %d x %d x %d%s, sharpened image %d x %d, %d calls per round; us per call; the sharpening changes %.1f %% of the bytes; '
          'torch differs from serve_sh in %.2f %% of the bytes, by at most %d'
          % (ARCH, n, h, w, '' if resize is None else ', window %s -> %d x %d' % (resize[1], resize[0][0], resize[0][1]), ih, iw, reps,
             100 * changed, 100 * (diff > 0).float().mean().item(), diff.max().item()))
     for name, v in res.items():
-        emit('  %-12s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        line = '  %-12s median %.1f us  min %.1f  spread %.1f' % (name, med[name], min(v), spread[name])
+        rounds_line, line = SB.leg_lines(name, v, 12)
+        emit(rounds_line)
         if nbytes[name] is not None:
-            rate = nbytes[name] / (med[name] * 1e-6)
-            line += '   %.1f MB: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (nbytes[name] / 1e6, rate / 1e12, 100 * rate / HBM_PEAK,
-                                                                                  HBM_PEAK / 1e12)
+            line += '   %.1f MB: %s' % (nbytes[name] / 1e6, SB.hbm_share(nbytes[name], med[name]))
         emit(line)
     won = []
     for r in F.SHARPEN_RADII:
         f, p = 'fused_r%d' % r, 'pass_r%d' % r
-        gain, noise = med[p] - med[f], max(spread[p], spread[f])
-        won.append(gain > noise)
+        gain, noise = SB.margin(res[f], res[p])
+        won.append(SB.beats(res[f], res[p]))
         emit('  (b) radius %d  pass - fused = %.1f us against a spread of %.1f us: the fused store %s   fused / pass = %.3f' % (
             r, gain, noise, 'BEATS two launches' if won[-1] else 'does NOT beat two launches', med[f] / med[p]))
     emit('  (a) bgr_r2 / resize = %.3f   bgr_r1 / resize = %.3f' % (med['bgr_r2'] / med['resize'], med['bgr_r1'] / med['resize']))
@@ -139,33 +124,21 @@ def measure(net, shape, resize, seed, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_sharpen.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     emit('(a) bgr_rR / nv12_rR: the sharpen launch alone, resize: risp_bgr8_resize at the same size   (b) fused_rR / pass_rR: NV12 from '
          'the sharpen launch or from sharpen-to-BGR plus risp_bgr8_to_nv12   (c) serve_sh / serve / serve_torch: net.serve(raw, out=) '
          'with sharpen, without, and followed by the same filter from torch ops; host side included; no counters were read')
-    net = pipeline(ARCH)
+    net = SB.pipeline(ARCH)
     rows = []
     rows += measure(net, (64, 256, 256), None, 10, args.reps, args.rounds, emit)
     rows += measure(net, (1, 3000, 4000), None, 20, max(20, args.reps // 3), args.rounds, emit)
     rows += measure(net, (1, 3000, 4000), ((1080, 1920), (375, 0, 2250, 4000)), 20, max(20, args.reps // 3), args.rounds, emit)
     emit('the fused NV12 store beats two launches by more than the spread in %d of %d rows' % (sum(rows), len(rows)))
-    emit('verdict: _SHARPEN_NV12_FUSED = %s' % ('nv12' if all(rows) else 'none'))
+    emit(SB.verdict_line('_SHARPEN_NV12_FUSED', ['nv12'] if all(rows) else []))
     emit("pipeline_fusion.sharpen_store('nv12') answers %r" % PF.sharpen_store('nv12'))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

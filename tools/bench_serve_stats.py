@@ -22,21 +22,12 @@ timed between two device events:
 With --variant a third input, 4 x 3000 x 4000 (3008 tiles of 64 rows), is timed for the launch legs alone.
 Each round times every leg once (REPS calls, the torch leg REPS / 10, after 3 warm ones), after one round that is not kept; per
 leg: the rounds, median, minimum and spread.  Bytes are algorithmic counts, the rate is those bytes over the median time."""
-import argparse
-import ctypes as C
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd import lib as L
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd import lib as L  # noqa: E402
-from bench_serve_packed import frames_int, pack, pipeline, timed  # noqa: E402
-from bench_serve_shade import vignette  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCH = 'Demosaic_02_sRGB_11_01_14'
 FORMATS = ['u16', 'raw10', 'raw12']
 WHITE, BLACK, CELL = 1023.0, 64, 64
@@ -65,11 +56,11 @@ def measure(net, shape, zone, seed, fmt, reps, rounds, variants, emit, launch_on
     n, h, w = shape
     pix = n * h * w
     bits = F.RAW_FORMAT[fmt] or 16
-    x = frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK
+    x = SB.frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK
     x16 = x.to(torch.uint16).cuda()
-    raw = x16 if fmt == 'u16' else pack(x, bits).cuda()
+    raw = x16 if fmt == 'u16' else SB.pack(x, bits).cuda()
     fkw = {} if fmt == 'u16' else dict(raw_format=fmt, raw_width=w)
-    shading = (F.shading_map(vignette(h, w), h, w, CELL).cuda(), CELL)
+    shading = (F.shading_map(SB.vignette(h, w), h, w, CELL).cuda(), CELL)
     st = F.raw_statistics(n, h, w, zone=zone, bins=BINS, hist_shift=SHIFT, lo=LO, hi=HI)
     others = {name: F.raw_statistics(n, h, w, zone=zone, bins=BINS, hist_shift=SHIFT, lo=LO, hi=HI) for name in variants}
     out_a, out_b = (torch.empty((1 if launch_only else n, h, w, 3), device='cuda', dtype=torch.uint8) for _ in range(2))
@@ -106,7 +97,6 @@ def measure(net, shape, zone, seed, fmt, reps, rounds, variants, emit, launch_on
         bpp[name] = bits / 8
     if not launch_only:
         legs.update(shade=leg_shade, serve_st=leg_serve_st, serve=leg_serve, torch=leg_torch)
-    few = {'torch': max(3, reps // 10)}
     leg_stats()
     if not launch_only:
         leg_serve_st(), leg_serve()
@@ -119,58 +109,39 @@ def measure(net, shape, zone, seed, fmt, reps, rounds, variants, emit, launch_on
     assert torch.equal(tz, st.zones) and torch.equal(th, st.hist), 'torch and the launch disagree'
     for name, o in others.items():
         assert torch.equal(o.zones, st.zones) and torch.equal(o.hist, st.hist), 'build %s disagrees' % name
-    res = {k: [] for k in legs}
-    for r in range(rounds + 1):                             # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            t = timed(fn, few.get(name, reps))
-            if r:
-                res[name].append(t)
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, {name: max(3, reps // 10) if name == 'torch' else reps for name in legs}, rounds, True)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %s, %d x %d x %d, zones of %d x %d, %d calls per round; us per call' % (fmt, ARCH, n, h, w, zone[0], zone[1], reps))
     for name, v in res.items():
-        emit('  %-9s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = bpp[name] * pix / (med[name] * 1e-6)
-        emit('  %-9s median %.1f us  min %.1f  spread %.1f   %.3f B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), spread[name], bpp[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
+        rounds_line, stats_line = SB.leg_lines(name, v, 9)
+        emit(rounds_line)
+        emit(stats_line + '   %.3f B/pixel: %s' % (bpp[name], SB.hbm_share(bpp[name] * pix, med[name])))
     if not launch_only:
         emit('  stats / shade = %.2f   serve_st - serve = %.1f us (serve_st / serve = %.3f)   torch / stats = %.1f' % (
             med['stats'] / med['shade'], med['serve_st'] - med['serve'], med['serve_st'] / med['serve'], med['torch'] / med['stats']))
-    for name in variants:
-        if name == 'direct':
-            continue
-        gain, noise = med[name] - med['direct'], max(spread[name], spread['direct'])
+    won = {name: SB.beats(res['direct'], res[name]) for name in variants if name != 'direct'}
+    for name in won:
+        gain, noise = SB.margin(res['direct'], res[name])
         emit('  %s - direct = %+.1f us against a spread of %.1f us: the in-tree form %s' % (
-            name, gain, noise, 'WINS' if gain > noise else ('LOSES' if -gain > noise else 'is level')))
-    return {name: med[name] - med['direct'] > max(spread[name], spread['direct']) for name in variants if name != 'direct'}
+            name, gain, noise, 'WINS' if won[name] else ('LOSES' if SB.beats(res[name], res['direct']) else 'is level')))
+    return won
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
+    ap = SB.parser(300, 7)
     ap.add_argument('--variant', action='append', default=[], metavar='NAME=LIB.so',
                     help='another build of the library whose risp_raw_stats is timed in the same rounds')
     args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
+    emit = SB.Report(args.out)
     variants = {'direct': L.load().risp_raw_stats} if args.variant else {}
     for spec in args.variant:
         name, path = spec.split('=', 1)
-        fn = C.CDLL(os.path.abspath(path)).risp_raw_stats
-        fn.restype, fn.argtypes = L.SIGNATURES['risp_raw_stats']
-        variants[name] = fn
-    emit('tools/bench_serve_stats.py --reps %d --rounds %d%s   (%s)' % (
-        args.reps, args.rounds, ''.join(' --variant %s=..' % v for v in variants if v != 'direct'), torch.cuda.get_device_name(0)))
+        variants[name] = SB.load_parent(path, ['risp_raw_stats']).risp_raw_stats
+    emit(SB.header(__file__, args, ''.join(' --variant %s=..' % v for v in variants if v != 'direct')))
     emit('stats: functional.raw_stats alone (memset and launch)   shade: functional.raw_shade alone   serve_st / serve: '
          'net.serve(raw, out=) with and without statistics=   torch: the same statistics from torch ops on the unpacked frames; '
          'host side included')
-    net = pipeline(ARCH)
+    net = SB.pipeline(ARCH)
     wins = {name: [] for name in variants if name != 'direct'}
     for fmt in FORMATS:
         for shape, zone, seed, reps in (((64, 256, 256), (32, 32), 10, args.reps), ((1, 3000, 4000), (200, 200), 20, max(20, args.reps // 3))):
@@ -184,10 +155,7 @@ def main():
                 wins[name].append(won)
     for name, rows in wins.items():
         emit('%s: the in-tree form wins beyond the spread in %d of %d rows' % (name, sum(rows), len(rows)))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -21,21 +21,11 @@ two device events:
 Each round times every leg once (REPS calls, after 3 warm ones), after one round that is not kept; per leg: the rounds, median,
 minimum and spread - the spread between the rounds of ONE leg is the noise a difference between two legs has to clear.  Bytes are
 algorithmic counts, the rate is those bytes over the median time."""
-import argparse
-import ctypes as C
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd import lib as L  # noqa: E402
-from bench_serve_packed import frames_int, pipeline, timed  # noqa: E402
-from bench_serve_shade import vignette  # noqa: E402
-
-HBM_PEAK = 8.0e12
 ARCH = 'Demosaic_02_sRGB_11_01_14'
 WHITE, BLACK, CELL = 1023.0, 64, 64
 PARAMS = (64, 40, 10, 24)
@@ -67,9 +57,9 @@ def torch_temporal(cur, state, iy, ix, params, black):
 def measure(net, shape, seed, reps, rounds, nocopy, emit):
     n, h, w = shape
     pix = n * h * w
-    raw = (frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
-    start = (frames_int(n, h, w, seed + 1, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
-    shading = (F.shading_map(vignette(h, w), h, w, CELL).cuda(), CELL)
+    raw = (SB.frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
+    start = (SB.frames_int(n, h, w, seed + 1, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
+    shading = (F.shading_map(SB.vignette(h, w), h, w, CELL).cuda(), CELL)
     states = {k: F.temporal_state(n, h, w) for k in ('temporal', 'launch', 'serve', 'torch')}
     for st in states.values():
         st.frames.copy_(start)
@@ -112,21 +102,14 @@ def measure(net, shape, seed, reps, rounds, nocopy, emit):
         torch.cuda.synchronize()
         assert torch.equal(u16_l, u16) and torch.equal(states['launch'].frames, start), 'the build without the copy copied'
         legs['launch'] = leg_launch
-    res = {k: [] for k in legs}
-    for r in range(rounds + 1):                             # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            t = timed(fn, reps if name != 'torch' else max(5, reps // 10))
-            if r:
-                res[name].append(t)
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, {name: max(5, reps // 10) if name == 'torch' else reps for name in legs}, rounds, True)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %d x %d x %d, %d calls per round (torch: a tenth); us per call; the first filtered frame differs from its input in '
          '%.1f %% of the samples' % (ARCH, n, h, w, reps, 100 * moved))
     for name, v in res.items():
-        emit('  %-10s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        rate = bpp[name] * pix / (med[name] * 1e-6)
-        emit('  %-10s median %.1f us  min %.1f  spread %.1f   %.0f B/pixel: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (
-            name, med[name], min(v), spread[name], bpp[name], rate / 1e12, 100 * rate / HBM_PEAK, HBM_PEAK / 1e12))
+        rounds_line, stats_line = SB.leg_lines(name, v, 10)
+        emit(rounds_line)
+        emit(stats_line + '   %.0f B/pixel: %s' % (bpp[name], SB.hbm_share(bpp[name] * pix, med[name])))
     if 'launch' in med:
         emit('  (a) temporal / shade = %.2f   launch / shade = %.2f   the copy costs temporal - launch = %.1f us' % (
             med['temporal'] / med['shade'], med['launch'] / med['shade'], med['temporal'] - med['launch']))
@@ -138,33 +121,18 @@ def measure(net, shape, seed, reps, rounds, nocopy, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
+    ap = SB.parser(300, 7)
     ap.add_argument('--nocopy-lib', default=None, help='a build of the library with -DRISP_TEMPORAL_NO_COPY: times the launch alone')
     args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    nocopy = None
-    if args.nocopy_lib:
-        nocopy = C.CDLL(os.path.abspath(args.nocopy_lib))
-        nocopy.risp_raw_temporal.restype, nocopy.risp_raw_temporal.argtypes = L.SIGNATURES['risp_raw_temporal']
-    emit('tools/bench_serve_temporal.py --reps %d --rounds %d%s   (%s)' % (
-        args.reps, args.rounds, ' --nocopy-lib' if nocopy is not None else '', torch.cuda.get_device_name(0)))
+    emit = SB.Report(args.out)
+    nocopy = SB.load_parent(args.nocopy_lib, ['risp_raw_temporal']) if args.nocopy_lib else None
+    emit(SB.header(__file__, args, ' --nocopy-lib' if nocopy is not None else ''))
     emit('(a) temporal / launch / shade: risp_raw_temporal with and without its state copy beside risp_raw_shade   (b) serve_tnr / '
          'serve: net.serve(raw, out=) with and without temporal_denoise   (c) torch: the filter from torch ops; host side included')
-    net = pipeline(ARCH)
+    net = SB.pipeline(ARCH)
     for shape, seed, reps in (((64, 256, 256), 10, args.reps), ((1, 3000, 4000), 20, max(20, args.reps // 3))):
         measure(net, shape, seed, reps, args.rounds, nocopy, emit)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':

@@ -26,20 +26,15 @@ the two spreads; a kernel enters pipeline_fusion._WARP_STAGED only if that holds
 meshes), and the line `verdict: _WARP_STAGED = ...` says so (tests/test_warp_reference_cpu.py compares it with the table).  Bytes
 are algorithmic counts, the rate is those bytes over the median time.  With RISP_HIP_LIBRARY set the rows are those of that build
 (profiles/serve_warp_lds.txt: a build whose stage = 1 launch asks for 16 KB of LDS, make EXTRA=-DRISP_WARP_AB_LDS=16384)."""
-import argparse
 import math
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import torch
 
-import reconfigisp_amd.functional as F  # noqa: E402
-from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF  # noqa: E402
-from bench_serve_packed import frames_int, pipeline, timed  # noqa: E402
+import serve_bench as SB
+import reconfigisp_amd.functional as F
+from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF
 
-HBM_PEAK = 8.0e12
 ARCH = 'Demosaic_02_sRGB_11_01_14'
 WHITE, BLACK = 1023.0, 64
 CELL = 64
@@ -58,7 +53,7 @@ def meshes(h, w):
 
 def measure(net, shape, seed, reps, rounds, emit):
     n, h, w = shape
-    raw = (frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
+    raw = (SB.frames_int(n, h, w, seed, int(WHITE) - BLACK) + BLACK).to(torch.uint16).cuda()
     img = net.serve(raw, WHITE, black_level=BLACK).clone()
     assert net.last_serve_route == 'classical'
     u8 = lambda *s: torch.empty(s, device='cuda', dtype=torch.uint8)
@@ -111,30 +106,22 @@ def measure(net, shape, seed, reps, rounds, emit):
     theirs = leg_serve_grid()
     diff = (theirs.int() - out_s.int()).abs()
     assert len(torch.unique(out_s)) > 32
-    res = {k: [] for k in legs}
-    for r in range(rounds + 1):                             # round 0 brings the clocks up and is not kept
-        for name, fn in legs.items():
-            t = timed(fn, reps)
-            if r:
-                res[name].append(t)
-    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-    spread = {k: max(v) - min(v) for k, v in res.items()}
+    res = SB.rounds_of(legs, reps, rounds, True)
+    med = {k: SB.median(v) for k, v in res.items()}
     emit(' %s, %d x %d x %d -> the same size, cell %d, %d calls per round; us per call; grid_sample differs from serve_warp in '
          '%.1f %% of the bytes, by at most %d' % (ARCH, n, h, w, CELL, reps, 100 * (diff > 0).float().mean().item(), diff.max().item()))
     for name, v in res.items():
-        emit('  %-22s rounds %s' % (name, ' '.join('%.1f' % t for t in v)))
-        line = '  %-22s median %.1f us  min %.1f  spread %.1f' % (name, med[name], min(v), spread[name])
+        rounds_line, line = SB.leg_lines(name, v, 22)
+        emit(rounds_line)
         if nbytes[name] is not None:
-            rate = nbytes[name] / (med[name] * 1e-6)
-            line += '   %.1f MB: %.3f TB/s = %.1f %% of the %.1f TB/s HBM peak' % (nbytes[name] / 1e6, rate / 1e12, 100 * rate / HBM_PEAK,
-                                                                                  HBM_PEAK / 1e12)
+            line += '   %.1f MB: %s' % (nbytes[name] / 1e6, SB.hbm_share(nbytes[name], med[name]))
         emit(line)
     won = {k: [] for k in F.WARP_KERNELS}
     for k in F.WARP_KERNELS:
         for m in MESHES:
             s0, s1 = '%s_%s_s0' % (k, m), '%s_%s_s1' % (k, m)
-            gain, noise = med[s0] - med[s1], max(spread[s0], spread[s1])
-            won[k].append(gain > noise)
+            gain, noise = SB.margin(res[s1], res[s0])
+            won[k].append(SB.beats(res[s1], res[s0]))
             emit('  (a) %-8s %-8s s0 - s1 = %.1f us against a spread of %.1f us: staging %s   s1 / s0 = %.3f;  against resize_%s: '
                  's0 %.2f x, s1 %.2f x' % (k, m, gain, noise, 'BEATS the gather' if won[k][-1] else 'does NOT beat the gather',
                                            med[s1] / med[s0], 'triangle' if k == 'bilinear' else 'bicubic',
@@ -148,37 +135,24 @@ def measure(net, shape, seed, reps, rounds, emit):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='also write the report to this file')
-    ap.add_argument('--reps', type=int, default=300)
-    ap.add_argument('--rounds', type=int, default=7)
-    args = ap.parse_args()
-    lines = []
-
-    def emit(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    emit('tools/bench_serve_warp.py --reps %d --rounds %d   (%s)' % (args.reps, args.rounds, torch.cuda.get_device_name(0)))
+    args = SB.parser(300, 7).parse_args()
+    emit = SB.Report(args.out)
+    emit(SB.header(__file__, args))
     if os.environ.get('RISP_HIP_LIBRARY'):                  # an ablation build (make EXTRA=-DRISP_WARP_AB_LDS=..): its rows, not the library's
         emit('RISP_HIP_LIBRARY=%s %s' % (os.environ['RISP_HIP_LIBRARY'], os.environ.get('RISP_BENCH_NOTE', '')))
     emit('(a) K_M_s0 / K_M_s1: the warp launch alone, sampling global memory or the staged box; resize_K: the resize launch at the '
          'same sizes   (b) serve_warp / serve / serve_grid: net.serve(raw, out=) with warp, without, and followed by '
          'torch.nn.functional.grid_sample; host side included')
-    net = pipeline(ARCH)
+    net = SB.pipeline(ARCH)
     rows = {k: [] for k in F.WARP_KERNELS}
     for shape, seed, reps in (((1, 3000, 4000), 20, max(20, args.reps // 3)), ((64, 256, 256), 10, args.reps)):
         for k, v in measure(net, shape, seed, reps, args.rounds, emit).items():
             rows[k] += v
     for k in F.WARP_KERNELS:
         emit('%s: staging beats the gather by more than the spread in %d of %d rows' % (k, sum(rows[k]), len(rows[k])))
-    staged = [k for k in F.WARP_KERNELS if all(rows[k])]
-    emit('verdict: _WARP_STAGED = %s' % (' '.join(staged) if staged else 'none'))
+    emit(SB.verdict_line('_WARP_STAGED', [k for k in F.WARP_KERNELS if all(rows[k])]))
     emit('pipeline_fusion.warp_stage answers %s' % ', '.join('%s: %r' % (k, PF.warp_stage(k)) for k in F.WARP_KERNELS))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    emit.write()
 
 
 if __name__ == '__main__':
