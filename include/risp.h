@@ -1044,6 +1044,79 @@ int risp_raw_temporal(const uint16_t *cur, uint16_t *state, uint16_t *out, int p
 int risp_raw_stats(const void *raw, int bits, int stride, int black_level, long long *zones, int *hist, int zone_h, int zone_w,
                    int bins, int hist_shift, int lo, int hi, int N, int H, int W, void *stream);
 
+/* Auto white balance and auto exposure on the device (risp_control.hip): the 3A controller of a capture loop, the block that reads
+ * the statistics above and sets the next frame's gains.  Its output is a lens-shading map - a Q12 gain per Bayer plane, applied
+ * in front of everything (risp_raw_shade and every fused shading load) -, and the statistics are taken behind the shading, so
+ * rewriting the map from the statistics of frame t closes the loop for frame t+1.  An integer function of zones, hist and the
+ * state, fixed to the bit (tests/control_reference.py restates it in numpy int64).
+ *
+ * Inputs.  zones (N,ZH,ZW,4,3) int64 [sum, count, sharp] and hist (N,4,bins) int32 as risp_raw_stats writes them for N frames of
+ * H x W with (zone_h, zone_w, bins, hist_shift); cfa = k, a RISP_CFA_* code: colour q of (r, gr, gb, b) lives in plane q ^ k.
+ * The state (e, wr, wb): Q12 unsigned, at most 65535 - the exposure gain and the red and blue white-balance gains; green is
+ * 4096.  A control specification is RISP_CONTROL_SPEC_INTS integers, in this order, ranges in brackets:
+ *     fill [0..256]   y_lo <= y_hi [0..65535]   rg_lo <= rg_hi, bg_lo <= bg_hi [0..4095, Q8 ratios]   min_share [0..256]
+ *     wb_dead [0..4095]   wb_speed [0..256]   wb_min <= wb_max [256..65535]
+ *     pct [1..65536]   target [1..65535]   ceil [1..65535]   ae_dead [0..4095]   ae_speed [0..256]   e_min <= e_max [256..65535]
+ * The N images of a call are pooled: a call has one state and one gain map.
+ *
+ * White balance, a grey-candidate gray world over the zones.  For image n and zone (zy,zx): rows = min(zone_h, H - zy * zone_h),
+ * cols = min(zone_w, W - zx * zone_w), area = (rows / 2) * (cols / 2) - by the rules of risp_raw_stats every plane of the zone has
+ * exactly area samples.
+ *     filled     for all four planes  count >= 1  and  count * 256 >= fill * area                           (64-bit)
+ *     m          per plane (sum + (count >> 1)) / count, an unsigned 64-bit division; at most 65535 (a quotient above, which
+ *                no statistics of risp_raw_stats give, counts as 65535)
+ *     mr = m[r]     mg = (m[gr] + m[gb] + 1) >> 1     mb = m[b]
+ *     candidate  filled  and  y_lo <= mg <= y_hi  and  rg_lo * mg <= 256 * mr <= rg_hi * mg  and  bg_lo * mg <= 256 * mb <= bg_hi * mg
+ *                (unsigned 32-bit: the largest product is 4095 * 65535 < 2^28)
+ *     over all candidates   AR += mr   AG += mg   AB += mb   K += 1                                          (64-bit)
+ *     solved     K >= 1  and  K * 256 >= min_share * N * ZH * ZW  and  AR > 0  and  AB > 0
+ *     solved:    cr = clamp((AG << 12) / AR, 1024, 16384), cb likewise from AB (64-bit);
+ *                wr' = damp(wr, cr, wb_dead, wb_speed, wb_min, wb_max), wb' likewise;   otherwise wr' = wr and wb' = wb.
+ * Exposure, from the green histograms.
+ *     Hg[b] = sum over n of hist[n][gr][b] + hist[n][gb][b]   (64-bit)        T = sum of Hg;   T == 0: e' = e, M = P = 0
+ *     v(b)  = min((b << hist_shift) + ((1 << hist_shift) >> 1), 65535)        the bin's centre
+ *     M     = (sum of Hg[b] * v(b) + (T >> 1)) / T                            the mean green level
+ *     b*    = the smallest b with cum(b) * 65536 >= T * pct,  cum(b) = Hg[0] + .. + Hg[b]
+ *     P     = min(((b* + 1) << hist_shift) - 1, 65535)                        the upper edge of that bin
+ *     corr  = clamp((target << 12) / max(M, 1), 1024, 16384)
+ *     if P * corr > (ceil << 12)   highlight protection takes over:   corr = clamp((ceil << 12) / max(P, 1), 1024, 16384)
+ *     e'    = damp(e, corr, ae_dead, ae_speed, e_min, e_max)
+ * damp(cur, corr, dead, speed, lo, hi):  |corr - 4096| <= dead makes corr 4096;  step = 4096 + (((corr - 4096) * speed) >> 8), a
+ * signed 32-bit arithmetic shift (floor), step in 1024 .. 16384;  the result is clamp((cur * step + 2048) >> 12, lo, hi), with
+ * cur * step < 2^30.  Speed 0 switches that half of the controller off.
+ * Gains and the map.  g[p] = min((e' * w + 2048) >> 12, 65535) for plane p, w = wr' where p ^ k is r, wb' where it is b, 4096 on
+ * the two greens (unsigned 32-bit);  out[i][j][p] = min((base[i][j][p] * g[p] + 2048) >> 12, 65535) for a base map (GH,GW,4)
+ * uint16 (unsigned 32-bit: 65535 * 65535 + 2048 < 2^32);  without a base map the base is 4096 everywhere and out == g[p].
+ * Sizes.  N * ZH * ZW <= 2^24 and N * H * W / 2 < 2^40, so that every sum fits: AR, AG, AB <= 2^24 * 65535 < 2^40 and
+ * AG << 12 < 2^52;  T < 2^40, sum of Hg * v < 2^56, cum * 65536 and T * pct <= 2^56;  count * 256 and fill * area < 2^48.
+ *
+ * The state is RISP_CONTROL_STATE_INTS = 16 contiguous int32 on the device:  [0] e  [1] wr  [2] wb  [3] updates so far, mod 2^31
+ * [4] M  [5] P  [6] min(K, 2^31 - 1)  [7] flags: bit 0 white balance solved, bit 1 T > 0, bit 2 the ceiling took over
+ * [8..11] g[0..3]  [12..15] 0.  The host may read it whenever it likes; nothing makes it.
+ *
+ * risp_control_solve: ONE launch of 256-thread workgroups, one per 256 zones, at least 1 and at most 1024; zones and histogram
+ * words are walked grid-stride.  A thread per zone does the four divisions and the candidate test; wave shuffles, then LDS,
+ * reduce AR, AG, AB, K per workgroup, the green histogram words go into a copy of Hg in LDS.  scratch is 5 + bins uint64
+ * [ticket, AR, AG, AB, K, Hg[bins]], zeroed once by the caller: a workgroup adds its non-zero partials with 64-bit agent-scope
+ * atomics and then draws a ticket; the workgroup that draws the last one takes every accumulator with an atomic exchange against
+ * 0 - which leaves scratch zero for the next launch or replay -, solves, writes the 16 state words and resets the ticket.  No
+ * workgroup waits or polls.  spec is a HOST array, read before the launch.  Rules (anything else is refused before anything is
+ * issued, the message names the value): no NULL, the specification's ranges, N >= 1, H even, W >= 4 and W % 4 == 0, zone_h even
+ * and >= 2, zone_w >= 4 and zone_w % 4 == 0, ZH == ceil(H / zone_h), ZW == ceil(W / zone_w), the two sizes above, bins 1 .. 1024,
+ * hist_shift 0 .. 16, cfa 0 .. 3, zones and scratch 8-byte, hist and state 4-byte aligned.
+ *
+ * risp_gain_map: one streaming launch, a thread per node: out (GH,GW,4) uint16 from base (NULL: 4096 everywhere) and the state's
+ * words 8 .. 11, 8 bytes loaded and 8 stored per node.  Rules: state and out not NULL, GH and GW >= 2, GH * GW <= 2^30, base
+ * and out 8-byte and state 4-byte aligned, out may not overlap base.
+ * Not covered: metering weights per zone, a per-image gain map, exposure time or analogue gain handed to a sensor driver, flicker
+ * and scene-change detection, a colour-temperature prior or locus, the gains folded into an existing map without the second
+ * launch, statistics gathered in the shade launch. */
+#define RISP_CONTROL_SPEC_INTS 19
+#define RISP_CONTROL_STATE_INTS 16
+int risp_control_solve(const long long *zones, const int *hist, int *state, unsigned long long *scratch, const int *spec, int N,
+                       int ZH, int ZW, int H, int W, int zone_h, int zone_w, int bins, int hist_shift, int cfa, void *stream);
+int risp_gain_map(const uint16_t *base, const int *state, uint16_t *out, int GH, int GW, void *stream);
+
 /* A scaled, cropped output at the end of the serving path (risp_resize.hip): the scaler / crop block behind an ISP's colour
  * pipeline.  Packed 8-bit images are resampled separably, antialiased on reduction, with an integer tap table per axis - the
  * design of Pillow's ImagingResample, made reproducible to the bit: Q14 weights, every row of weights sums to exactly 16384, and

@@ -1866,6 +1866,136 @@ def raw_stats(frames, st, black_level=0, bits=16, width=None):
     return st
 
 
+CONTROL_FIELDS = ('fill', 'y_lo', 'y_hi', 'rg_lo', 'rg_hi', 'bg_lo', 'bg_hi', 'min_share', 'wb_dead', 'wb_speed', 'wb_min', 'wb_max',
+                  'pct', 'target', 'ceil', 'ae_dead', 'ae_speed', 'e_min', 'e_max')
+_CONTROL_RANGES = dict(fill=(0, 256), y_lo=(0, 65535), y_hi=(0, 65535), rg_lo=(0, 4095), rg_hi=(0, 4095), bg_lo=(0, 4095),
+                       bg_hi=(0, 4095), min_share=(0, 256), wb_dead=(0, 4095), wb_speed=(0, 256), wb_min=(256, 65535),
+                       wb_max=(256, 65535), pct=(1, 65536), target=(1, 65535), ceil=(1, 65535), ae_dead=(0, 4095),
+                       ae_speed=(0, 256), e_min=(256, 65535), e_max=(256, 65535))
+_CONTROL_PAIRS = (('y_lo', 'y_hi'), ('rg_lo', 'rg_hi'), ('bg_lo', 'bg_hi'), ('wb_min', 'wb_max'), ('e_min', 'e_max'))
+# settings for 10-bit samples with the black level taken off (tests/control_reference.py has the scene they were tried on): zones at
+# least 3/4 inside lo .. hi, green mean 16 .. 900, red and blue within 1/4 .. 4 of green, 1/8 of the zones grey enough, a white
+# balance that moves 5/8 of the way once it is more than 1 % off, the mean green level drawn to 170 unless the 99 % point would pass
+# 900, 5/8 of the way once it is more than 3 % off; gains from 1/4 up
+_CONTROL_DEFAULTS = dict(fill=192, y_lo=16, y_hi=900, rg_lo=64, rg_hi=1024, bg_lo=64, bg_hi=1024, min_share=32, wb_dead=40,
+                         wb_speed=160, wb_min=1024, wb_max=65535, pct=64880, target=170, ceil=900, ae_dead=120, ae_speed=160,
+                         e_min=1024, e_max=65535)
+
+
+def control_spec(**fields):
+    """The control specification of the device-side auto white balance / auto exposure, checked on the host -> the tuple of its
+    nineteen integers in the order of ``CONTROL_FIELDS`` (include/risp.h has their meaning and ranges).  A field not given
+    takes its default.  Bools, non-integers, values outside the ranges and a lower bound above its upper bound are refused."""
+    unknown = sorted(set(fields) - set(CONTROL_FIELDS))
+    if unknown:
+        raise ValueError('unknown control field %s: one of %s' % (', '.join(unknown), ', '.join(CONTROL_FIELDS)))
+    spec = {}
+    for name in CONTROL_FIELDS:
+        value = fields.get(name, _CONTROL_DEFAULTS[name])
+        lo, hi = _CONTROL_RANGES[name]
+        spec[name] = _small_int(value, lo, hi)
+        if spec[name] is None:
+            raise ValueError('%s %r: an integer in %d .. %d' % (name, value, lo, hi))
+    for low, high in _CONTROL_PAIRS:
+        if spec[low] > spec[high]:
+            raise ValueError('%s %d above %s %d' % (low, spec[low], high, spec[high]))
+    return tuple(spec[name] for name in CONTROL_FIELDS)
+
+
+class GainControl:
+    """The device-side 3A controller of a ``RawStatistics``: auto white balance and auto exposure whose output is a lens-shading
+    map.  ``.state``: sixteen ``torch.int32`` on the device - [e, wr, wb, updates, M, P, K, flags, g[0..3], 0 x 4], Q12 gains
+    (include/risp.h has the definition to the bit); ``.gains``: the (GH,GW,4) ``torch.uint16`` map of cell ``cell`` for the
+    statistics' H x W frames, ``base`` (an existing lens shading of the same cell; kept, never written) times the plane gains, or
+    the plane gains alone; ``.shading`` = (``.gains``, ``cell``) is what ``serve(lens_shading=, statistics=st)`` takes.  The
+    statistics are taken behind the shading, so ``update(st)`` after a served frame closes the loop for the next one.  ``cfa``
+    says which plane holds which colour (``stats_planes``); ``fields`` are those of ``control_spec``.  The N images of a call
+    are pooled: one state, one map."""
+
+    def __init__(self, st, cell=256, base=None, cfa='rggb', **fields):
+        if not isinstance(st, RawStatistics):
+            raise ValueError('a gain control is built for a RawStatistics (functional.raw_statistics builds one), got %s'
+                             % (type(st).__name__,))
+        zh, zw, bins, shift, _, _ = stats_check(st, st.n, st.h, st.w)
+        self.spec = control_spec(**fields)
+        self.cfa = cfa_code(cfa)
+        if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
+            raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
+        self.n, self.h, self.w, self.grid, self.cell = st.n, st.h, st.w, st.grid, cell
+        self.geometry = (zh, zw, bins, shift)
+        if self.n * self.grid[0] * self.grid[1] > 1 << 24:
+            raise ValueError('%d x %d x %d zones: more than 2^24' % ((self.n,) + tuple(self.grid)))
+        if self.n * self.h * self.w // 2 >= 1 << 40:
+            raise ValueError('%d frames of %d x %d: N * H * W / 2 reaches 2^40' % (self.n, self.h, self.w))
+        _need_gpu(st.zones, 'statistics.zones')
+        device = st.zones.device
+        k = cell.bit_length() - 1
+        self.base = None
+        if base is not None:
+            self.base = shading_check((base, cell), self.h, self.w, device)[0]
+        self.state = torch.zeros(16, dtype=torch.int32, device=device)
+        self._scratch = torch.zeros(5 + bins, dtype=torch.int64, device=device)     # [ticket, AR, AG, AB, K, Hg[bins]]
+        self.gains = torch.empty((((self.h - 1) >> k) + 2, ((self.w - 1) >> k) + 2, 4), dtype=torch.uint16, device=device)
+        shading_check(self.shading, self.h, self.w, device)
+        self._spec_c = (C.c_int * len(self.spec))(*self.spec)
+        self.reset()
+
+    @property
+    def shading(self):
+        return self.gains, self.cell
+
+    def reset(self, exposure=4096, wb=(4096, 4096)):
+        """Start over from these Q12 gains (256 .. 65535 each): the scratch is zeroed, the state written and the map made, so the
+        next frame is served with them.  -> self"""
+        try:
+            wr, wb_ = wb
+        except (TypeError, ValueError):
+            raise ValueError('wb is (red, blue), two Q12 gains, got %r' % (wb,)) from None
+        words = []
+        for name, value in (('exposure', exposure), ('wb red', wr), ('wb blue', wb_)):
+            words.append(_small_int(value, 256, 65535))
+            if words[-1] is None:
+                raise ValueError('%s %r: a Q12 gain, an integer in 256 .. 65535' % (name, value))
+        e, wr, wb_ = words
+        gains = [wr if p ^ self.cfa == 0 else wb_ if p ^ self.cfa == 3 else 4096 for p in range(4)]
+        words += [0] * 5 + [min((e * g + 2048) >> 12, 65535) for g in gains] + [0] * 4
+        self._scratch.zero_()
+        self.state.copy_(torch.tensor(words, dtype=torch.int32))
+        L.call('risp_gain_map', _p(self.base), _p(self.state), _p(self.gains), self.gains.shape[0], self.gains.shape[1], _stream())
+        return self
+
+    def update(self, st):
+        return control_update(self, st)
+
+    def __repr__(self):
+        return 'GainControl(%d, %d, %d, cell=%d, cfa=%d%s)' % (self.n, self.h, self.w, self.cell, self.cfa,
+                                                              ', base' if self.base is not None else '')
+
+
+def gain_control(st, cell=256, base=None, cfa='rggb', **fields):
+    """A ``GainControl`` for the ``RawStatistics`` ``st``: built once, it owns ``.state``, ``.gains`` and its scratch, and its
+    map holds the initial gains (1.0) from the start."""
+    return GainControl(st, cell, base, cfa, **fields)
+
+
+def control_update(ctl, st):
+    """One step of the device-side 3A loop in TWO launches on the current stream (``risp_control_solve``, ``risp_gain_map``):
+    the statistics ``st`` - those of a frame served with ``lens_shading=ctl.shading, statistics=st`` - move ``ctl.state`` and
+    rewrite ``ctl.gains`` for the next frame.  ``st`` is checked again (``stats_check``) and must have the frames, zones and
+    bins ``ctl`` was built for.  Nothing is allocated and nothing on the device is read by the host, so the call can be
+    captured in a graph behind the serving call.  -> ctl"""
+    if not isinstance(ctl, GainControl):
+        raise ValueError('control_update takes a GainControl (functional.gain_control builds one), got %s' % (type(ctl).__name__,))
+    zh, zw, bins, shift, _, _ = stats_check(st, ctl.n, ctl.h, ctl.w, ctl.state.device)
+    if (zh, zw, bins, shift) != ctl.geometry:
+        raise ValueError('statistics with zones of %d x %d, %d bins and hist_shift %d: the gain control was built for zones of '
+                         '%d x %d, %d bins and hist_shift %d' % ((zh, zw, bins, shift) + ctl.geometry))
+    L.call('risp_control_solve', _p(st.zones), _p(st.hist), _p(ctl.state), _p(ctl._scratch), ctl._spec_c, ctl.n, ctl.grid[0],
+           ctl.grid[1], ctl.h, ctl.w, zh, zw, bins, shift, ctl.cfa, _stream())
+    L.call('risp_gain_map', _p(ctl.base), _p(ctl.state), _p(ctl.gains), ctl.gains.shape[0], ctl.gains.shape[1], _stream())
+    return ctl
+
+
 def serve_classical_shaded(raw_u16, shading, divisor, demosaic, ops, params, reverse_channels=False, matrix=None, out=None,
                            black_level=0, cfa='rggb'):
     """``serve_classical_u8`` / ``serve_classical_nv12`` with the lens-shading correction inside the load, still ONE launch

@@ -203,6 +203,8 @@ SIGNATURES = {
     'risp_raw_temporal': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bgr8_resize': (_i, [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _s]),
     'risp_raw_stats': (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_control_solve': (_i, [_f, _f, _f, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
+    'risp_gain_map': (_i, [_f, _f, _f, _i, _i, _s]),
     'risp_bgr8_warp': (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_bgr8_sharpen': (_i, [_f, _f, C.POINTER(_i), _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     'risp_serve_scene_groups': (_i, [_i, _i]),
