@@ -76,7 +76,7 @@ int risp_wb_quadratic_bwd(const float *x, const float *p, const float *gy, float
 /* Per-image per-channel statistics of an (N,C,H,W) tensor (NC = N*C planes):
  * stats[plane*4+{0,1,2}] = {min, sum, max}; arg[plane*2+{0,1}] = first (row-major) index of
  * the min / max (may be NULL).  Used by SRCNNRes (srcnn_res_arch.py:36-40) and gray-world.
- * Any HW > 0: planes of HW % 4 == 0 pixels through 16-byte loads, others through element loads.
+ * Any HW > 0: planes of HW % 4 == 0 pixels at a 16-byte aligned x through 16-byte loads, others through element loads.
  * scratch: risp_channel_stats_scratch_floats(NC,HW) floats.  Deterministic (no atomics). */
 size_t risp_channel_stats_scratch_floats(int NC, int HW);
 int risp_channel_stats(const float *x, float *stats, int32_t *arg, float *scratch, int NC, int HW,
@@ -631,7 +631,9 @@ int risp_origin_fastnlm(const float *x, float *y, const int32_t *block_size, con
  * 'filmic' (2: a=white_point, b=exposure_bias) - :526-543, :566-581, :604-623; whitebalance
  * 'whiteworld' (3: a=white_point_ratio, stats from risp_channel_stats) - :647-662.
  * a, b: (N) device arrays; scratch: risp_origin_tonemap_scratch_floats(N) floats (per-image constants and the
- * partial sums of Reinhard's log-average luminance, added in a fixed order: deterministic). */
+ * partial sums of Reinhard's log-average luminance, added in a fixed order: deterministic).
+ * HW % 4 == 0, and x and y 16-byte aligned (the planes are read and written in 16-byte vectors): anything else is
+ * refused before a launch and the message names the pointer. */
 size_t risp_origin_tonemap_scratch_floats(int N);
 int risp_origin_tonemap(const float *x, float *y, int mode, const float *a, const float *b, const float *stats,
                         float *scratch, int N, int HW, float in_scale, float out_div, void *stream);

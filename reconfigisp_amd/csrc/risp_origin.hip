@@ -780,6 +780,9 @@ int risp_origin_tonemap(const float *x, float *y, int mode, const float *a, cons
                    "risp_origin_tonemap: bad arguments (mode %d)", mode);
     RISP_CHECK_ARG((mode != TM_REINHARD && mode != TM_FILMIC) || b, "risp_origin_tonemap: second parameter missing");
     RISP_CHECK_ARG(mode != TM_GAIN || stats, "risp_origin_tonemap: white-world needs the channel statistics");
+    // every kernel below reads x and writes y in 16-byte vectors
+    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(x) % 16 == 0, "risp_origin_tonemap: x must be 16-byte aligned (%p)", (const void *)x);
+    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(y) % 16 == 0, "risp_origin_tonemap: y must be 16-byte aligned (%p)", (const void *)y);
     hipStream_t s = (hipStream_t)stream;
     const int hw4 = HW / 4;
     int bx = (hw4 + 255) / 256;

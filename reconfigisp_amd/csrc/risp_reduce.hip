@@ -391,7 +391,9 @@ int risp_channel_stats(const float *x, float *stats, int32_t *arg, float *scratc
     RISP_CHECK_ARG(x && stats && scratch && NC > 0 && NC <= 65535 && HW > 0,
                    "risp_channel_stats: bad arguments (NC=%d HW=%d)", NC, HW);
     const int nb = stat_blocks(HW);
-    if (HW % 4 == 0)
+    // the 16-byte loads need an aligned x: a contiguous view with a storage offset that is no multiple of 4 floats takes
+    // the element loads (as stats_bwd_launch and risp_histc decide)
+    if (HW % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0)
         hipLaunchKernelGGL(stats_partial_kernel, dim3(nb, NC), dim3(256), 0, (hipStream_t)stream, x, scratch, HW / 4, nb);
     else
         hipLaunchKernelGGL(stats_partial_scalar_kernel, dim3(nb, NC), dim3(256), 0, (hipStream_t)stream, x, scratch, HW, nb);

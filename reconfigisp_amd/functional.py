@@ -2868,9 +2868,16 @@ _TONEMAP = {'reinhard': (0, 'white_point', 'middle_grey'), 'crysisengine': (1, '
             'filmic': (2, 'white_point', 'exposure_bias')}
 
 
+def _aligned16(x):
+    """risp_origin_tonemap reads its planes in 16-byte vectors and refuses any other pointer: a contiguous view whose
+    storage offset is no multiple of 4 floats is copied to a fresh tensor first"""
+    return x.clone() if x.data_ptr() % 16 else x
+
+
 def _hip_origin_tonemap(x, option, params, scales=(1.0, 1.0)):
     x = _dev(x.detach(), 'img')
     _check_bgr(x)
+    x = _aligned16(x)
     n, hw = x.shape[0], x.shape[2] * x.shape[3]
     mode, ka, kb = _TONEMAP[option]
     a = _vec(params[ka], n, x.device)
@@ -2885,6 +2892,7 @@ def _hip_origin_tonemap(x, option, params, scales=(1.0, 1.0)):
 def _hip_origin_whiteworld(x, ratio, scales=(1.0, 1.0)):
     x = _dev(x.detach(), 'img')
     _check_bgr(x)
+    x = _aligned16(x)
     n, hw = x.shape[0], x.shape[2] * x.shape[3]
     stats, _ = channel_stats(x, want_arg=False)
     y = torch.empty_like(x)
@@ -2900,7 +2908,8 @@ def _hip_origin_denoise(x, option, params, scales=(1.0, 1.0)):
     if option == 'bm3d':                  # any H, W >= n1
         return _hip_origin_bm3d(x, 2.55 * _vec(params['cff'], x.shape[0], x.device), params['n1'], params['cspace'],
                                 params['wtransform'], params['neighborhood'], scales)[0]
-    _check_bgr(x)
+    if x.dim() != 4 or x.shape[1] != 3:   # any H, W above the radius: the entry points pick the tile form themselves
+        raise ValueError('expected a (N,3,H,W) BGR tensor, got %s' % (tuple(x.shape),))
     n, _, h, w = x.shape
     y = torch.empty_like(x)
     if option == 'median':
