@@ -9,51 +9,22 @@
 // counter alone: every slot is a register, nothing lives in scratch.  Only rows y-2, y, y+2 enter row y; rows y-1 and y+1 wait
 // for their turn.
 //
-// Borders.  Reflection without the repeated edge keeps a column's parity, and the four columns behind a row's end are those of
-// the thread's own group: at x == 0 columns -2, -1 are columns 2, 1 and at x + 4 == W columns W, W+1 are W-2, W-3 - elements 2
-// and 1 of the group in both cases, W == 4 included.  So a border thread drops a pair load and selects, and no load ever leaves
-// the row.  A row index y0-2 .. y+2 with y <= H-1 reflects into 0 .. H-1 for every H >= 3 (-2 -> 2, H+1 -> H-3); it is clamped
-// behind the reflection all the same, and rows below the frame's last are neither loaded nor stored.
+// Borders.  The window, its reflected columns at a row's end and the reflected row index are risp_rawframe.h's (load_row,
+// reflect_row): no load ever leaves the frame.  Rows below the frame's last are neither loaded nor stored.
 #include "risp_common.h"
 #include "risp_defect.h"
-#include "risp_rawpack.h"
+#include "risp_rawframe.h"
 #include "risp_shade.h"
 
 namespace {
 
+using namespace risp_rawframe;
 using namespace risp_shade;
 
 #ifndef RISP_DEFECT_ROWS
 #define RISP_DEFECT_ROWS 8      // (make EXTRA=-DRISP_DEFECT_ROWS=4 | 16: the ablation builds of tools/bench_serve_defect_rows.py)
 #endif
 constexpr int ROWS = RISP_DEFECT_ROWS;          // rows per thread
-
-struct Row {
-    unsigned v[8];              // columns x-2 .. x+5
-};
-
-// BITS 16: rows of uint16 (WIDE: base and stride 8-byte aligned - the group is one 8-byte load, a pair one 4-byte load; otherwise
-// single samples); 10 / 12: the byte form of risp_rawpack.h
-template <int BITS, bool WIDE>
-__device__ __forceinline__ Row load_row(const uint8_t *row, int x, bool left, bool right) {
-    ushort4 c;
-    ushort2 l, r;
-    if constexpr (BITS != 16) {
-        c = risp_rawpack::ld4<BITS>(row, x);
-        l = left ? ushort2{c.z, c.y} : risp_rawpack::ld2<BITS>(row, x - 2);
-        r = right ? ushort2{c.z, c.y} : risp_rawpack::ld2<BITS>(row, x + 4);
-    } else if constexpr (WIDE) {
-        c = *reinterpret_cast<const ushort4 *>(row + 2 * (size_t)x);
-        l = left ? ushort2{c.z, c.y} : *reinterpret_cast<const ushort2 *>(row + 2 * (size_t)(x - 2));
-        r = right ? ushort2{c.z, c.y} : *reinterpret_cast<const ushort2 *>(row + 2 * (size_t)(x + 4));
-    } else {
-        const unsigned short *p = reinterpret_cast<const unsigned short *>(row) + x;
-        c = ushort4{p[0], p[1], p[2], p[3]};
-        l = left ? ushort2{c.z, c.y} : ushort2{p[-2], p[-1]};
-        r = right ? ushort2{c.z, c.y} : ushort2{p[4], p[5]};
-    }
-    return Row{{l.x, l.y, c.x, c.y, c.z, c.w, r.x, r.y}};
-}
 
 // pixel I of the group in row `mid`, rows `top` and `bot` two above and below
 template <int I>
@@ -79,9 +50,7 @@ __global__ __launch_bounds__(256) void raw_defect_kernel(const uint8_t *__restri
         for (int r = 0; r < ROWS + 4; ++r) {
             const int y = y0 + r - 4;                   // the row this step completes, once r >= 4
             if (r >= 4 && y >= H) break;
-            int yy = y + 2;                             // the row this step loads: y0-2 .. y0+ROWS+1, at most H+1
-            yy = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
-            yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+            const int yy = reflect_row(y + 2, H);       // the row this step loads: y0-2 .. y0+ROWS+1, at most H+1
             win[r % 5] = load_row<BITS, WIDE>(img + (size_t)yy * (size_t)stride, x, left, right);
             if (r < 4) continue;
             const Row &top = win[(r - 4) % 5], &mid = win[(r - 2) % 5], &bot = win[r % 5];
@@ -111,15 +80,7 @@ extern "C" int risp_raw_defect(const void *raw, int bits, int stride, uint16_t *
     const char *name = "risp_raw_defect";
     RISP_CHECK_ARG(raw && out, "%s: null argument", name);
     RISP_CHECK_ARG(N >= 1 && H >= 3, "%s: bad shape N=%d H=%d (at least 3 rows: a reflected row stays inside the frame)", name, N, H);
-    RISP_CHECK_ARG(bits == 16 || bits == 10 || bits == 12, "%s: bits %d (16: uint16 rows, 10: RAW10, 12: RAW12)", name, bits);
-    if (bits == 16) {
-        RISP_CHECK_ARG(W >= 4 && W % 4 == 0, "%s: W %d (a multiple of 4)", name, W);
-        RISP_CHECK_ARG(stride % 2 == 0 && (long long)stride >= 2LL * W && reinterpret_cast<uintptr_t>(raw) % 2 == 0,
-                       "%s: stride %d (even, at least the %lld bytes of a row of W=%d) and raw %p (2-byte aligned)", name, stride, 2LL * W,
-                       W, raw);
-    } else if (int err = risp_rawpack::rawpack_check(name, bits, W, stride)) {
-        return err;
-    }
+    if (int err = frame_check(name, raw, bits, W, stride)) return err;
     RISP_CHECK_ARG(threshold >= -1 && threshold <= 65535, "%s: threshold %d outside 0 .. 65535 (-1: no dynamic test)", name, threshold);
     RISP_CHECK_ARG(slope >= 0 && slope <= 255, "%s: slope %d outside 0 .. 255", name, slope);
     RISP_CHECK_ARG(threshold >= 0 || defects, "%s: neither a threshold nor a defect map: nothing to correct", name);
@@ -130,29 +91,20 @@ extern "C" int risp_raw_defect(const void *raw, int bits, int stride, uint16_t *
         RISP_CHECK_ARG(cell_log2 == 0 && GH == 0 && GW == 0 && black_level == 0,
                        "%s: without gains cell_log2 %d, GH %d, GW %d and black_level %d must be 0", name, cell_log2, GH, GW, black_level);
     }
-    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(out) % 8 == 0, "%s: out %p must be 8-byte aligned", name, (void *)out);
+    if (int err = out_check(name, out)) return err;
     const int per_row = W / 4, strips = (H + ROWS - 1) / ROWS, words = (W + 31) / 32;
-    const size_t items = (size_t)N * strips * per_row, blocks = (items + 255) / 256;
-    const dim3 grid((unsigned)(blocks > 65536 ? 65536 : blocks));
-    hipStream_t s = (hipStream_t)stream;
+    const size_t items = (size_t)N * strips * per_row;
     const uint8_t *src = static_cast<const uint8_t *>(raw);
     const unsigned thr = threshold < 0 ? risp_defect::NO_THRESHOLD : (unsigned)threshold, slp = threshold < 0 ? 0u : (unsigned)slope;
-    const unsigned black = (unsigned)black_level;
-#define RISP_DEFECT_LAUNCH(BITS, WIDE, SHADE)                                                                                        \
-    hipLaunchKernelGGL((raw_defect_kernel<BITS, WIDE, SHADE>), grid, dim3(256), 0, s, src, out, defects, gains, items, H, W, stride, \
-                       per_row, strips, words, thr, slp, cell_log2, GW, black)
-#define RISP_DEFECT_FORMAT(SHADE)                                                                         \
-    if (bits == 10) RISP_DEFECT_LAUNCH(10, false, SHADE);                                                 \
-    else if (bits == 12) RISP_DEFECT_LAUNCH(12, false, SHADE);                                            \
-    else if (reinterpret_cast<uintptr_t>(raw) % 8 == 0 && stride % 8 == 0) RISP_DEFECT_LAUNCH(16, true, SHADE); \
-    else RISP_DEFECT_LAUNCH(16, false, SHADE)
-    if (gains) {
-        RISP_DEFECT_FORMAT(true);
-    } else {
-        RISP_DEFECT_FORMAT(false);
-    }
-#undef RISP_DEFECT_FORMAT
-#undef RISP_DEFECT_LAUNCH
+    dispatch(bits, raw, stride, [&](auto bits_c, auto wide_c) {
+        auto launch = [&](auto shade_c) {
+            hipLaunchKernelGGL((raw_defect_kernel<decltype(bits_c)::value, decltype(wide_c)::value, decltype(shade_c)::value>),
+                               capped_grid(items), dim3(256), 0, (hipStream_t)stream, src, out, defects, gains, items, H, W, stride,
+                               per_row, strips, words, thr, slp, cell_log2, GW, (unsigned)black_level);
+        };
+        if (gains) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
     RISP_LAUNCH_CHECK(name);
     return 0;
 }

@@ -7,6 +7,7 @@
 // a multiple of 20 / 24 bytes of an aligned row - and a row's last, shorter chunk takes the byte form.  Byte form (any base,
 // any stride): the 4-, 2- and 1-byte copies of risp_rawpack.h per four pixels.  Neither reads a byte behind W * bits / 8 of a row.
 #include "risp_common.h"
+#include "risp_rawframe.h"
 #include "risp_rawpack.h"
 
 namespace {
@@ -55,10 +56,10 @@ extern "C" int risp_raw_unpack(const uint8_t *packed, uint16_t *out, int bits, i
     RISP_CHECK_ARG(packed && out, "%s: null argument", name);
     RISP_CHECK_ARG(N >= 1 && H >= 1, "%s: bad shape N=%d H=%d", name, N, H);
     if (int err = rawpack_check(name, bits, W, stride)) return err;
-    RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(out) % 8 == 0, "%s: out %p must be 8-byte aligned", name, (void *)out);
+    if (int err = risp_rawframe::out_check(name, out)) return err;
     const int per_row = (W + CHUNK - 1) / CHUNK;
-    const size_t chunks = (size_t)N * H * per_row, blocks = (chunks + 255) / 256;
-    const dim3 grid((unsigned)(blocks > 65536 ? 65536 : blocks));
+    const size_t chunks = (size_t)N * H * per_row;
+    const dim3 grid = risp_rawframe::capped_grid(chunks);
     hipStream_t s = (hipStream_t)stream;
     const bool wide = reinterpret_cast<uintptr_t>(packed) % 4 == 0 && stride % 4 == 0;
     if (bits == 10) {

@@ -7,8 +7,8 @@
 // A workgroup of four waves owns one tile of TILE_W = 256 columns x TH rows (TH 64, 32 or 16, picked by the host).  A lane owns a
 // group of four columns x .. x+3 (x % 4 == 0), which lies in one zone column (zone_w % 4 == 0) and in one 5-byte or 3-byte group
 // pair; a wave owns TH / 4 consecutive rows and walks them in pairs, which lie in one zone row (zone_h even, H even).  Per row
-// the lane loads the group and the pairs left and right of it, columns x-2 .. x+5, as risp_raw_defect does; a pair outside the
-// row is not loaded and its two pixels add nothing to the focus term.
+// the lane loads the group and the pairs left and right of it, columns x-2 .. x+5, with risp_rawframe.h's load_row; a pair outside
+// the row is not loaded (it is 0 and unused: the form without the reflection) and its two pixels add nothing to the focus term.
 //
 // Accumulation.  The lane keeps [sum, count, sharp] of the four planes in twelve 32-bit registers while its zone row lasts.  At
 // a zone-row change and behind its last row they go to the tile's table in LDS, twelve LDS adds into the lane's copy of the
@@ -23,9 +23,11 @@
 // A histogram bin holds at most the pixels of one plane of one image, H * W / 4, which the host keeps below 2^31 (the output
 // is int32).
 #include "risp_common.h"
-#include "risp_rawpack.h"
+#include "risp_rawframe.h"
 
 namespace {
+
+using namespace risp_rawframe;
 
 constexpr int TILE_W = 256;                 // 64 lanes x 4 columns
 #ifndef RISP_STATS_MAX_TH
@@ -56,33 +58,6 @@ struct Stats {
     long long tiles;                        // all tiles: one workgroup each
     int table, copies;                      // entries of the zone table in LDS: 12 per zone a tile can touch and copy; copies of an entry
 };
-
-struct Row {
-    unsigned v[8];                          // columns x-2 .. x+5; a pair outside the row is 0 and unused
-};
-
-// BITS 16: rows of uint16 (WIDE: base and stride 8-byte aligned - the group is one 8-byte load, a pair one 4-byte load; otherwise
-// single samples); 10 / 12: the byte form of risp_rawpack.h
-template <int BITS, bool WIDE>
-__device__ __forceinline__ Row load_row(const uint8_t *row, int x, bool left, bool right) {
-    ushort4 c;
-    ushort2 l{0, 0}, r{0, 0};
-    if constexpr (BITS != 16) {
-        c = risp_rawpack::ld4<BITS>(row, x);
-        if (!left) l = risp_rawpack::ld2<BITS>(row, x - 2);
-        if (!right) r = risp_rawpack::ld2<BITS>(row, x + 4);
-    } else if constexpr (WIDE) {
-        c = *reinterpret_cast<const ushort4 *>(row + 2 * (size_t)x);
-        if (!left) l = *reinterpret_cast<const ushort2 *>(row + 2 * (size_t)(x - 2));
-        if (!right) r = *reinterpret_cast<const ushort2 *>(row + 2 * (size_t)(x + 4));
-    } else {
-        const unsigned short *p = reinterpret_cast<const unsigned short *>(row) + x;
-        c = ushort4{p[0], p[1], p[2], p[3]};
-        if (!left) l = ushort2{p[-2], p[-1]};
-        if (!right) r = ushort2{p[4], p[5]};
-    }
-    return Row{{l.x, l.y, c.x, c.y, c.z, c.w, r.x, r.y}};
-}
 
 // one row of the lane's group: YP is the row's parity, acc[3 * plane + (0 sum, 1 count, 2 sharp)]
 template <int YP>
@@ -150,8 +125,8 @@ __global__ __launch_bounds__(256) void raw_stats_kernel(const uint8_t *__restric
         }
         if (active) {
             const uint8_t *row = img + (size_t)y * (size_t)a.stride;
-            const Row r0 = load_row<BITS, WIDE>(row, x, left, right);
-            const Row r1 = load_row<BITS, WIDE>(row + a.stride, x, left, right);
+            const Row r0 = load_row<BITS, WIDE, false>(row, x, left, right);
+            const Row r1 = load_row<BITS, WIDE, false>(row + a.stride, x, left, right);
             add_row<0>(r0, a, left, right, hist, acc);
             add_row<1>(r1, a, left, right, hist, acc);
         }
@@ -186,15 +161,7 @@ extern "C" int risp_raw_stats(const void *raw, int bits, int stride, int black_l
     const char *name = "risp_raw_stats";
     RISP_CHECK_ARG(raw && zones && hist, "%s: null argument", name);
     RISP_CHECK_ARG(N >= 1 && H >= 2 && H % 2 == 0, "%s: bad shape N=%d H=%d (H even: a row pair lies in one zone row)", name, N, H);
-    RISP_CHECK_ARG(bits == 16 || bits == 10 || bits == 12, "%s: bits %d (16: uint16 rows, 10: RAW10, 12: RAW12)", name, bits);
-    if (bits == 16) {
-        RISP_CHECK_ARG(W >= 4 && W % 4 == 0, "%s: W %d (a multiple of 4)", name, W);
-        RISP_CHECK_ARG(stride % 2 == 0 && (long long)stride >= 2LL * W && reinterpret_cast<uintptr_t>(raw) % 2 == 0,
-                       "%s: stride %d (even, at least the %lld bytes of a row of W=%d) and raw %p (2-byte aligned)", name, stride, 2LL * W,
-                       W, raw);
-    } else if (int err = risp_rawpack::rawpack_check(name, bits, W, stride)) {
-        return err;
-    }
+    if (int err = frame_check(name, raw, bits, W, stride)) return err;
     RISP_CHECK_ARG(black_level >= 0 && black_level <= 65535, "%s: black_level %d outside 0 .. 65535", name, black_level);
     RISP_CHECK_ARG(zone_h >= 2 && zone_h % 2 == 0, "%s: zone_h %d (even, at least 2)", name, zone_h);
     RISP_CHECK_ARG(zone_w >= 4 && zone_w % 4 == 0, "%s: zone_w %d (a multiple of 4)", name, zone_w);
@@ -236,12 +203,9 @@ extern "C" int risp_raw_stats(const void *raw, int bits, int stride, int black_l
         return 2;
     }
     const uint8_t *src = static_cast<const uint8_t *>(raw);
-#define RISP_STATS_LAUNCH(BITS, WIDE) hipLaunchKernelGGL((raw_stats_kernel<BITS, WIDE>), grid, dim3(256), shared, s, src, a)
-    if (bits == 10) RISP_STATS_LAUNCH(10, false);
-    else if (bits == 12) RISP_STATS_LAUNCH(12, false);
-    else if (reinterpret_cast<uintptr_t>(raw) % 8 == 0 && stride % 8 == 0) RISP_STATS_LAUNCH(16, true);
-    else RISP_STATS_LAUNCH(16, false);
-#undef RISP_STATS_LAUNCH
+    dispatch(bits, raw, stride, [&](auto bits_c, auto wide_c) {
+        hipLaunchKernelGGL((raw_stats_kernel<decltype(bits_c)::value, decltype(wide_c)::value>), grid, dim3(256), shared, s, src, a);
+    });
     RISP_LAUNCH_CHECK(name);
     return 0;
 }

@@ -11,44 +11,21 @@
 // five rows live in registers, indexed by the unrolled loop counter alone: nothing lives in scratch.  A pixel's window sums are the
 // five rows' 5-sums added up.
 //
-// Borders as in risp_defect.hip: at x == 0 columns -2, -1 are columns 2, 1 and at x + 4 == W columns W, W+1 are W-2, W-3 -
-// elements 2 and 1 of the thread's own group in both cases, W == 4 included; a border thread drops a pair load and selects, and no
-// load ever leaves the row.  A row index y0-2 .. y+2 with y <= H-1 reflects into 0 .. H-1 for every H >= 3; it is clamped behind the
-// reflection all the same, and rows below the frame's last are neither loaded nor stored.
+// Borders as in risp_defect.hip, with risp_rawframe.h's load_row and reflect_row on uint16 rows 2 W bytes apart: no load ever leaves
+// the frame, and rows below the frame's last are neither loaded nor stored.
 #include "risp_common.h"
+#include "risp_rawframe.h"
 #include "risp_temporal.h"
 
 namespace {
 
+using namespace risp_rawframe;
 using risp_temporal::Params;
 
 #ifndef RISP_TEMPORAL_ROWS
 #define RISP_TEMPORAL_ROWS 8
 #endif
 constexpr int ROWS = RISP_TEMPORAL_ROWS;        // rows per thread
-
-struct Row {
-    unsigned v[8];              // columns x-2 .. x+5
-};
-
-// WIDE: the base is 8-byte aligned (the row pitch 2 W always is) - the group is one 8-byte load, a pair one 4-byte load; otherwise
-// single samples
-template <bool WIDE>
-__device__ __forceinline__ Row load_row(const uint16_t *row, int x, bool left, bool right) {
-    ushort4 c;
-    ushort2 l, r;
-    if constexpr (WIDE) {
-        c = *reinterpret_cast<const ushort4 *>(row + x);
-        l = left ? ushort2{c.z, c.y} : *reinterpret_cast<const ushort2 *>(row + x - 2);
-        r = right ? ushort2{c.z, c.y} : *reinterpret_cast<const ushort2 *>(row + x + 4);
-    } else {
-        const uint16_t *p = row + x;
-        c = ushort4{p[0], p[1], p[2], p[3]};
-        l = left ? ushort2{c.z, c.y} : ushort2{p[-2], p[-1]};
-        r = right ? ushort2{c.z, c.y} : ushort2{p[4], p[5]};
-    }
-    return Row{{l.x, l.y, c.x, c.y, c.z, c.w, r.x, r.y}};
-}
 
 // what a row leaves behind for the five steps it is part of a window: per pixel of the group the horizontal 5-sums and the samples
 struct Sums {
@@ -74,6 +51,7 @@ __device__ __forceinline__ Sums fold(const Row &c, const Row &p) {
     return s;
 }
 
+// WIDE: both frames are 8-byte aligned (the row pitch 2 W always is)
 template <bool WIDE>
 __global__ __launch_bounds__(256) void raw_temporal_kernel(const uint16_t *__restrict__ cur, const uint16_t *__restrict__ state,
                                                            uint16_t *__restrict__ out, size_t items, int H, int W, int per_row,
@@ -88,11 +66,10 @@ __global__ __launch_bounds__(256) void raw_temporal_kernel(const uint16_t *__res
         for (int r = 0; r < ROWS + 4; ++r) {
             const int y = y0 + r - 4;                   // the row this step completes, once r >= 4
             if (r >= 4 && y >= H) break;
-            int yy = y + 2;                             // the row this step loads: y0-2 .. y0+ROWS+1, at most H+1
-            yy = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
-            yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+            const int yy = reflect_row(y + 2, H);       // the row this step loads: y0-2 .. y0+ROWS+1, at most H+1
             const size_t at = img + (size_t)yy * (size_t)W;
-            win[r % 5] = fold(load_row<WIDE>(cur + at, x, left, right), load_row<WIDE>(state + at, x, left, right));
+            win[r % 5] = fold(load_row<16, WIDE>(reinterpret_cast<const uint8_t *>(cur + at), x, left, right),
+                              load_row<16, WIDE>(reinterpret_cast<const uint8_t *>(state + at), x, left, right));
             if (r < 4) continue;
             const Sums &mid = win[(r - 2) % 5];         // row y itself
             unsigned o[4];
@@ -123,7 +100,7 @@ extern "C" int risp_raw_temporal(const uint16_t *cur, uint16_t *state, uint16_t 
     RISP_CHECK_ARG(black_level >= 0 && black_level <= 65535, "%s: black_level %d outside 0 .. 65535", name, black_level);
     const uintptr_t c0 = reinterpret_cast<uintptr_t>(cur), s0 = reinterpret_cast<uintptr_t>(state), o0 = reinterpret_cast<uintptr_t>(out);
     RISP_CHECK_ARG(c0 % 2 == 0 && s0 % 2 == 0, "%s: cur %p and state %p must be 2-byte aligned", name, (const void *)cur, (void *)state);
-    RISP_CHECK_ARG(o0 % 8 == 0, "%s: out %p must be 8-byte aligned", name, (void *)out);
+    if (int err = out_check(name, out)) return err;
     const size_t bytes = (size_t)N * (size_t)H * (size_t)W * sizeof(uint16_t);
     RISP_CHECK_ARG((o0 + bytes <= c0 || c0 + bytes <= o0) && (o0 + bytes <= s0 || s0 + bytes <= o0),
                    "%s: out %p overlaps cur %p or state %p: a thread reads rows other threads write", name, (void *)out,
@@ -136,8 +113,8 @@ extern "C" int risp_raw_temporal(const uint16_t *cur, uint16_t *state, uint16_t 
         }
     } else {
         const int per_row = W / 4, strips = (H + ROWS - 1) / ROWS;
-        const size_t items = (size_t)N * strips * per_row, blocks = (items + 255) / 256;
-        const dim3 grid((unsigned)(blocks > 65536 ? 65536 : blocks));
+        const size_t items = (size_t)N * strips * per_row;
+        const dim3 grid = capped_grid(items);
         const Params q{(unsigned)strength, 25u * (unsigned)threshold, (unsigned)slope, (unsigned)ramp, 25u * (unsigned)black_level};
         if (c0 % 8 == 0 && s0 % 8 == 0)
             hipLaunchKernelGGL((raw_temporal_kernel<true>), grid, dim3(256), 0, s, cur, state, out, items, H, W, per_row, strips, q);

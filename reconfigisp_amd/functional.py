@@ -526,6 +526,20 @@ def _u8_out(out, shape, device, align):
     return out
 
 
+def _u16_out(out, shape, device, apart=(), reader=None):
+    """``_u8_out`` for the uint16 frames of a sensor pre-pass (8-byte aligned).  ``apart``: (tensor, what) pairs whose memory
+    the caller's ``out`` must not share, because the ``reader`` reads neighbours that other threads write."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.uint16)
+    if out.dtype != torch.uint16 or out.device != device or tuple(out.shape) != shape or not out.is_contiguous() or out.data_ptr() % 8:
+        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
+                         % (shape, device, out.dtype, tuple(out.shape)))
+    for t, what in apart:
+        if out.data_ptr() < t.data_ptr() + t.numel() * t.element_size() and t.data_ptr() < out.data_ptr() + out.numel() * 2:
+            raise ValueError('out shares memory with %s: the %s reads neighbours other threads would have overwritten' % (what, reader))
+    return out
+
+
 # Bayer phase of a sensor, by the mirror that makes its mosaic an RGGB one (RISP_CFA_*): bit 0 mirrors x, bit 1 mirrors y
 CFA = {'rggb': 0, 'grbg': 1, 'gbrg': 2, 'bggr': 3}
 
@@ -574,14 +588,20 @@ def _demosaic_code(demosaic):
     return kind
 
 
+def _black_level(black_level):
+    """a sensor's black level -> the int"""
+    if black_level != int(black_level) or not 0 <= black_level <= 65535:
+        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    return int(black_level)
+
+
 def _sensor(black_level, cfa, h=None, w=None):
     """-> (black level as an int, RISP_CFA_* code); with ``h`` and ``w`` the mirror the phase asks for is checked against them"""
     code = cfa_code(cfa)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    black = _black_level(black_level)
     if h is not None:
         _check_mirror(code, h, w)
-    return int(black_level), code
+    return black, code
 
 
 def _stage_args(ops, params):
@@ -1332,6 +1352,22 @@ def _packed_frames(packed_u8, bits, width, what='raw'):
     return n, h, packed_width(bits, stride, width), stride
 
 
+def _raw_frames(frames, bits, width, what, u16=True):
+    """The sensor frames of a pre-pass -> (n, h, w, stride, single): contiguous (N,H,W) uint16 with ``bits`` 16 (``u16`` False:
+    the caller takes no such frames), else (N,H,stride) uint8 MIPI-packed RAW10 / RAW12 with ``width`` as in ``packed_width``;
+    ``single``: the batch dimension is absent and n is 1."""
+    _need_gpu(frames, what)
+    single = frames.dim() == 2
+    if u16 and bits == 16:
+        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
+        if width is not None and width != frames.shape[-1]:
+            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
+        n, h, w = (1,) + tuple(frames.shape) if single else tuple(frames.shape)
+        return n, h, w, 2 * w, single
+    return _packed_frames(frames[None] if single else frames, bits, width, what) + (single,)
+
+
 def raw_unpack(packed_u8, bits, width=None, out=None):
     """MIPI-packed RAW10 / RAW12 frames to one sample per word in ONE launch (``risp_raw_unpack``): (N,H,stride) or
     (H,stride) ``torch.uint8`` on the device, ``bits`` 10 or 12 -> (N,H,W) or (H,W) ``torch.uint16``.  RAW10 keeps four
@@ -1339,16 +1375,8 @@ def raw_unpack(packed_u8, bits, width=None, out=None):
     hold, ``stride * 8 // bits``, which must then be a multiple of 4, and the bytes of a row behind ``width * bits / 8`` are
     padding that is never read.  The frames may start at any byte.  With ``out`` (contiguous, 8-byte aligned) given nothing
     is allocated and the host does not wait."""
-    _need_gpu(packed_u8, 'packed')
-    single = packed_u8.dim() == 2
-    n, h, w, stride = _packed_frames(packed_u8[None] if single else packed_u8, bits, width, 'packed')
-    shape = (h, w) if single else (n, h, w)
-    if out is None:
-        out = torch.empty(shape, device=packed_u8.device, dtype=torch.uint16)
-    elif (out.dtype != torch.uint16 or out.device != packed_u8.device or tuple(out.shape) != shape or not out.is_contiguous()
-            or out.data_ptr() % 8):
-        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
-                         % (shape, packed_u8.device, out.dtype, tuple(out.shape)))
+    n, h, w, stride, single = _raw_frames(packed_u8, bits, width, 'packed', u16=False)
+    out = _u16_out(out, (h, w) if single else (n, h, w), packed_u8.device)
     L.call('risp_raw_unpack', _p(packed_u8), _p(out), bits, n, h, w, stride, _stream())
     return out
 
@@ -1400,6 +1428,19 @@ def serve_classical_packed(packed_u8, bits, width, divisor, demosaic, ops, param
     return out
 
 
+def _on_frames_device(t, device, what):
+    """``t`` (``what`` names it, with its verb) lives where the frames do; ``device`` None: not asked"""
+    if device is not None and t.device != device and t.device != torch.device(device):
+        raise ValueError('%s on %s, the frames on %s' % (what, t.device, device))
+
+
+def _shading_cell(cell):
+    """the cell size of a lens shading -> k with cell = 1 << k"""
+    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
+        raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
+    return cell.bit_length() - 1
+
+
 def shading_check(shading, h, w, device=None):
     """A lens shading ``(gains, cell)`` for H x W frames, checked on the host before anything is launched -> (gains, k, GH, GW)
     with cell = 1 << k.  ``gains``: a contiguous (GH,GW,4) ``torch.uint16`` device tensor, Q12 (4096 is gain 1.0; every value
@@ -1410,9 +1451,7 @@ def shading_check(shading, h, w, device=None):
         gains, cell = shading
     except (TypeError, ValueError):
         raise ValueError('a lens shading is (gains, cell): a (GH,GW,4) uint16 device tensor and the cell size in pixels') from None
-    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
-        raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
-    k = cell.bit_length() - 1
+    k = _shading_cell(cell)
     if not isinstance(gains, torch.Tensor) or gains.dtype != torch.uint16:
         raise ValueError('lens shading gains must be a uint16 tensor (Q12), got %s' % (getattr(gains, 'dtype', type(gains)),))
     gh, gw = ((int(h) - 1) >> k) + 2, ((int(w) - 1) >> k) + 2
@@ -1420,8 +1459,7 @@ def shading_check(shading, h, w, device=None):
         raise ValueError('lens shading gains of a %d x %d frame with cell %d must be contiguous (%d,%d,4): (H-1) // cell + 2 by '
                          '(W-1) // cell + 2 nodes of four planes; got %s' % (h, w, cell, gh, gw, tuple(gains.shape)))
     _need_gpu(gains, 'lens shading gains')
-    if device is not None and gains.device != device:
-        raise ValueError('lens shading gains live on %s, the frames on %s' % (gains.device, device))
+    _on_frames_device(gains, device, 'lens shading gains live')
     if gains.data_ptr() % 8:
         raise ValueError('lens shading gains must be 8-byte aligned')
     return gains, k, gh, gw
@@ -1434,8 +1472,7 @@ def shading_map(gain, H, W, cell):
     resampled bilinearly in float64 at the nodes (i * cell, j * cell) - the nodes behind the last pixel take the image's linear
     continuation - and rounded to Q12.  A resampled value outside 0 .. 65535 / 4096 or not finite is refused."""
     import numpy as np
-    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
-        raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
+    k = _shading_cell(cell)
     if H != int(H) or W != int(W) or H < 1 or W < 1:
         raise ValueError('frame size %r x %r' % (H, W))
     g = np.asarray(gain.detach().cpu().numpy() if isinstance(gain, torch.Tensor) else gain, dtype=np.float64)
@@ -1445,7 +1482,6 @@ def shading_map(gain, H, W, cell):
         raise ValueError('a gain image is (4,h,w) or (h,w), got %s' % (tuple(g.shape),))
     if not np.isfinite(g).all():
         raise ValueError('the gain image has values that are not finite')
-    k = cell.bit_length() - 1
     gh, gw = ((int(H) - 1) >> k) + 2, ((int(W) - 1) >> k) + 2
 
     def axis(nodes, full, size):
@@ -1476,30 +1512,13 @@ def raw_shade(frames, shading, black_level=0, bits=16, width=None, out=None):
     (``shading_check``; include/risp.h has the definition to the bit).  The black level leaves here: what comes out has black
     level 0 and the divisor white_level - black_level.  W % 4 == 0.  With ``out`` (contiguous, 8-byte aligned) given nothing
     is allocated and the host does not wait."""
-    _need_gpu(frames, 'frames')
-    if bits == 16:
-        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
-            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
-        if width is not None and width != frames.shape[-1]:
-            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
-        single = frames.dim() == 2
-        (n, h, w), stride = ((1,) + tuple(frames.shape) if single else tuple(frames.shape)), 2 * frames.shape[-1]
-        if w < 4 or w % 4:
-            raise ValueError('frames %d wide: W must be a multiple of 4' % w)
-    else:
-        single = frames.dim() == 2
-        n, h, w, stride = _packed_frames(frames[None] if single else frames, bits, width, 'frames')
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w, stride, single = _raw_frames(frames, bits, width, 'frames')
+    if w < 4 or w % 4:                          # (uint16 frames: a packed width is a multiple of 4 already)
+        raise ValueError('frames %d wide: W must be a multiple of 4' % w)
+    black = _black_level(black_level)
     gains, k, gh, gw = shading_check(shading, h, w, frames.device)
-    shape = (h, w) if single else (n, h, w)
-    if out is None:
-        out = torch.empty(shape, device=frames.device, dtype=torch.uint16)
-    elif (out.dtype != torch.uint16 or out.device != frames.device or tuple(out.shape) != shape or not out.is_contiguous()
-            or out.data_ptr() % 8):
-        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
-                         % (shape, frames.device, out.dtype, tuple(out.shape)))
-    L.call('risp_raw_shade', _p(frames), int(bits), stride, _p(out), _p(gains), k, gh, gw, int(black_level), n, h, w, _stream())
+    out = _u16_out(out, (h, w) if single else (n, h, w), frames.device)
+    L.call('risp_raw_shade', _p(frames), int(bits), stride, _p(out), _p(gains), k, gh, gw, black, n, h, w, _stream())
     return out
 
 
@@ -1543,8 +1562,7 @@ def defect_check(dc, h, w, device=None):
         raise ValueError('the defect map of a %d x %d frame must be contiguous (%d,%d): a word per 32 pixels of a row; got %s'
                          % (h, w, h, words, tuple(defects.shape)))
     _need_gpu(defects, 'defect map')
-    if device is not None and defects.device != device:
-        raise ValueError('the defect map lives on %s, the frames on %s' % (defects.device, device))
+    _on_frames_device(defects, device, 'the defect map lives')
     return thr, slp, defects
 
 
@@ -1585,37 +1603,17 @@ def raw_defect(frames, defect, bits=16, width=None, shading=None, black_level=0,
     corrected sample: word for word ``raw_shade(raw_defect(frames, defect, bits, width), shading, black_level)``.  H >= 3,
     W % 4 == 0.  ``out`` (contiguous, 8-byte aligned) must not share memory with the frames - the launch reads rows other
     threads write; with it nothing is allocated and the host does not wait."""
-    _need_gpu(frames, 'frames')
-    if bits == 16:
-        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
-            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
-        if width is not None and width != frames.shape[-1]:
-            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
-        single = frames.dim() == 2
-        (n, h, w), stride = ((1,) + tuple(frames.shape) if single else tuple(frames.shape)), 2 * frames.shape[-1]
-    else:
-        single = frames.dim() == 2
-        n, h, w, stride = _packed_frames(frames[None] if single else frames, bits, width, 'frames')
+    n, h, w, stride, single = _raw_frames(frames, bits, width, 'frames')
     thr, slp, defects = defect_check(defect, h, w, frames.device)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    black = _black_level(black_level)
     if shading is None:
-        if black_level:
+        if black:
             raise ValueError('black_level %r without a shading: the corrected codes keep their black level' % (black_level,))
         gains, k, gh, gw = None, 0, 0, 0
     else:
         gains, k, gh, gw = shading_check(shading, h, w, frames.device)
-    shape = (h, w) if single else (n, h, w)
-    if out is None:
-        out = torch.empty(shape, device=frames.device, dtype=torch.uint16)
-    elif (out.dtype != torch.uint16 or out.device != frames.device or tuple(out.shape) != shape or not out.is_contiguous()
-            or out.data_ptr() % 8):
-        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
-                         % (shape, frames.device, out.dtype, tuple(out.shape)))
-    elif (out.data_ptr() < frames.data_ptr() + frames.numel() * frames.element_size()
-            and frames.data_ptr() < out.data_ptr() + out.numel() * 2):
-        raise ValueError('out shares memory with the frames: the correction reads neighbours other threads would have overwritten')
-    L.call('risp_raw_defect', _p(frames), int(bits), stride, _p(out), thr, slp, _p(defects), _p(gains), k, gh, gw, int(black_level),
+    out = _u16_out(out, (h, w) if single else (n, h, w), frames.device, ((frames, 'the frames'),), 'correction')
+    L.call('risp_raw_defect', _p(frames), int(bits), stride, _p(out), thr, slp, _p(defects), _p(gains), k, gh, gw, black,
            n, h, w, _stream())
     return out
 
@@ -1685,8 +1683,7 @@ def temporal_check(td, n, h, w, device=None):
         raise ValueError('the temporal state of %d frames of %d x %d must hold contiguous (%d,%d,%d) uint16 frames, got %s %s'
                          % (n, h, w, n, h, w, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
     _need_gpu(t, 'temporal state')
-    if device is not None and t.device != torch.device(device):
-        raise ValueError('the temporal state lives on %s, the frames on %s' % (t.device, device))
+    _on_frames_device(t, device, 'the temporal state lives')
     if t.data_ptr() % 8:
         raise ValueError('the temporal state must be 8-byte aligned')
     return state, stg, thr, slp, rmp
@@ -1715,28 +1712,13 @@ def raw_temporal(frames, td, black_level=0, out=None):
     call, then capture, and every replay advances the state.  Packed frames are not taken: they come through ``raw_unpack`` or a
     pre-pass first.  H >= 3, W % 4 == 0.  ``out`` (contiguous, 8-byte aligned) must share memory with neither the frames nor
     the state - the launch reads rows other threads write; with it nothing is allocated and the host does not wait."""
-    _need_gpu(frames, 'frames')
-    if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
-        raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
-    single = frames.dim() == 2
-    n, h, w = (1,) + tuple(frames.shape) if single else tuple(frames.shape)
+    n, h, w, _, single = _raw_frames(frames, 16, None, 'frames')
     state, stg, thr, slp, rmp = temporal_check(td, n, h, w, frames.device)
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
-    shape = (h, w) if single else (n, h, w)
-    if out is None:
-        out = torch.empty(shape, device=frames.device, dtype=torch.uint16)
-    elif (out.dtype != torch.uint16 or out.device != frames.device or tuple(out.shape) != shape or not out.is_contiguous()
-            or out.data_ptr() % 8):
-        raise ValueError('out must be a contiguous uint16 %s tensor on %s, 8-byte aligned; got %s %s'
-                         % (shape, frames.device, out.dtype, tuple(out.shape)))
-    else:
-        for t, what in ((frames, 'the frames'), (state.frames, 'the temporal state')):
-            if out.data_ptr() < t.data_ptr() + t.numel() * 2 and t.data_ptr() < out.data_ptr() + out.numel() * 2:
-                raise ValueError('out shares memory with %s: the filter reads neighbours other threads would have overwritten' % what)
+    black = _black_level(black_level)
+    out = _u16_out(out, (h, w) if single else (n, h, w), frames.device,
+                   ((frames, 'the frames'), (state.frames, 'the temporal state')), 'filter')
     prime = _temporal_prime(state, torch.cuda.is_current_stream_capturing())
-    L.call('risp_raw_temporal', _p(frames), _p(state.frames), _p(out), prime, stg, thr, slp, rmp, int(black_level), n, h, w,
-           _stream())
+    L.call('risp_raw_temporal', _p(frames), _p(state.frames), _p(out), prime, stg, thr, slp, rmp, black, n, h, w, _stream())
     state.primed = True
     return out
 
@@ -1829,8 +1811,7 @@ def stats_check(st, n, h, w, device=None):
             raise ValueError('statistics.%s for %d frames of %d x %d must be a contiguous %s %s tensor, got %s %s'
                              % (name, n, h, w, shape, str(dtype).replace('torch.', ''), getattr(t, 'dtype', type(t)),
                                 tuple(getattr(t, 'shape', ()))))
-        if device is not None and t.device != torch.device(device):
-            raise ValueError('statistics.%s lives on %s, the frames on %s' % (name, t.device, device))
+        _on_frames_device(t, device, 'statistics.zones lives' if name == 'zones' else 'statistics.hist lives')
     return spec
 
 
@@ -1849,19 +1830,10 @@ def raw_stats(frames, st, black_level=0, bits=16, width=None):
     samples in lo .. hi and the focus measure sum |2 s(y,x) - s(y,x-2) - s(y,x+2)|, per image and plane the histogram
     (include/risp.h has the definition to the bit).  Integers throughout: the result is exact and has no summation order.
     H even, W % 4 == 0.  Nothing is allocated and the host does not wait."""
-    _need_gpu(frames, 'frames')
-    if bits == 16:
-        if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
-            raise ValueError('expected contiguous (N,H,W) or (H,W) uint16 frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
-        if width is not None and width != frames.shape[-1]:
-            raise ValueError('width %r of uint16 frames %d wide' % (width, frames.shape[-1]))
-        (n, h, w), stride = ((1,) + tuple(frames.shape) if frames.dim() == 2 else tuple(frames.shape)), 2 * frames.shape[-1]
-    else:
-        n, h, w, stride = _packed_frames(frames[None] if frames.dim() == 2 else frames, bits, width, 'frames')
-    if black_level != int(black_level) or not 0 <= black_level <= 65535:
-        raise ValueError('black_level %r: an integer in 0 .. 65535' % (black_level,))
+    n, h, w, stride, _ = _raw_frames(frames, bits, width, 'frames')
+    black = _black_level(black_level)
     zh, zw, nb, shift, lo, hi = stats_check(st, n, h, w, frames.device)
-    L.call('risp_raw_stats', _p(frames), int(bits), stride, int(black_level), _p(st.zones), _p(st.hist), zh, zw, nb, shift, lo, hi,
+    L.call('risp_raw_stats', _p(frames), int(bits), stride, black, _p(st.zones), _p(st.hist), zh, zw, nb, shift, lo, hi,
            n, h, w, _stream())
     return st
 
@@ -1919,8 +1891,7 @@ class GainControl:
         zh, zw, bins, shift, _, _ = stats_check(st, st.n, st.h, st.w)
         self.spec = control_spec(**fields)
         self.cfa = cfa_code(cfa)
-        if isinstance(cell, bool) or not isinstance(cell, int) or cell not in (4, 8, 16, 32, 64, 128, 256):
-            raise ValueError('lens shading cell %r: a power of two from 4 to 256' % (cell,))
+        _shading_cell(cell)
         self.n, self.h, self.w, self.grid, self.cell = st.n, st.h, st.w, st.grid, cell
         self.geometry = (zh, zw, bins, shift)
         if self.n * self.grid[0] * self.grid[1] > 1 << 24:

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import raw_packed_reference as PR
+from raw_placement import _place
 
 pytestmark = pytest.mark.gpu
 
@@ -31,16 +32,6 @@ PHASES = ['rggb', 'grbg', 'gbrg', 'bggr']
 def _strides(w, bits):
     used = w * bits // 8
     return [used, used + 3, (used + 63) // 64 * 64]
-
-
-def _place(data, offset):
-    """the packed (N,H,stride) numpy frames as a contiguous device view ``offset`` bytes into an allocation of 0xFF bytes"""
-    size = data.size
-    big = torch.full((size + 16,), 0xFF, dtype=torch.uint8, device='cuda')
-    view = big[offset:offset + size].view(data.shape)
-    view.copy_(torch.from_numpy(data))
-    assert view.is_contiguous() and view.data_ptr() % 2 == offset % 2
-    return view
 
 
 def _layouts(w, bits):

@@ -24,6 +24,7 @@ import torch
 
 import lens_shading_reference as LS
 import raw_packed_reference as PR
+from raw_placement import _place16, _place_packed
 
 pytestmark = pytest.mark.gpu
 
@@ -87,10 +88,8 @@ def test_raw_shade_equals_the_reference(cell, h, w):
         # uint16 in: an 8-byte aligned base (the vector load) and one a word into a larger allocation (single loads)
         x = _frames16(n, h, w, seed=k)
         want = LS.shade_ref(x, black, gains, _log2(cell))
-        big = torch.full((x.size + 8,), 0xFFFF, dtype=torch.uint16).cuda()
         for at in (0, 4, 1):
-            dev = big[at:at + x.size].view(x.shape)
-            dev.copy_(torch.from_numpy(x))
+            dev = _place16(x, at)
             got, calls = _counted(lambda: F.raw_shade(dev, shading, black))
             assert calls == {'risp_raw_shade': 1}
             assert got.dtype == torch.uint16 and tuple(got.shape) == (n, h, w)
@@ -100,10 +99,7 @@ def test_raw_shade_equals_the_reference(cell, h, w):
             xp = PR.full_range_frame(n, h, w, bits, seed=k + bits)
             used = w * bits // 8
             for stride, offset in ((used, 0), (used + 3, 1), ((used + 63) // 64 * 64, 1)):
-                data = PR.pack(xp, bits, stride, None)
-                bigb = torch.full((data.size + 16,), 0xFF, dtype=torch.uint8, device='cuda')
-                pk = bigb[offset:offset + data.size].view(data.shape)
-                pk.copy_(torch.from_numpy(data))
+                pk = _place_packed(xp, bits, stride, offset)
                 got, calls = _counted(lambda: F.raw_shade(pk, shading, black, bits, w))
                 assert calls == {'risp_raw_shade': 1}
                 assert np.array_equal(got.cpu().numpy(), LS.shade_ref(xp, black, gains, _log2(cell))), \
@@ -214,10 +210,7 @@ def test_serve_takes_a_lens_shading_on_every_route(fmt, what):
     if fmt == 'u16':
         src, fkw = torch.from_numpy(x).cuda(), {}
     else:
-        data = PR.pack(x, 10, w * 10 // 8 + 3, None)
-        big = torch.full((data.size + 16,), 0xFF, dtype=torch.uint8, device='cuda')
-        src = big[1:1 + data.size].view(data.shape)
-        src.copy_(torch.from_numpy(data))
+        src = _place_packed(x, 10, w * 10 // 8 + 3, 1)
         fkw = dict(raw_format=fmt, raw_width=w)
     want = net.serve(ref, white - black, black_level=0, cfa='grbg', **kw).clone()
     assert net.last_serve_route == route and net.last_serve_shade is None

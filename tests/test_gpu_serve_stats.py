@@ -18,6 +18,7 @@ import torch
 
 import raw_packed_reference as PR
 import stats_reference as SR
+from raw_placement import _place16, _place_packed
 
 pytestmark = pytest.mark.gpu
 
@@ -30,22 +31,6 @@ def _counted(fn):
         return out, dict(L.CALLS)
     finally:
         L.CALLS = None
-
-
-def _place16(x, at):
-    """the numpy uint16 frames as a contiguous device view ``at`` words into an allocation of 0xFF bytes"""
-    big = torch.full((x.size + 8,), 0xFFFF, dtype=torch.uint16).cuda()
-    dev = big[at:at + x.size].view(x.shape)
-    dev.copy_(torch.from_numpy(x))
-    return dev
-
-
-def _place_packed(x, bits, stride, offset):
-    data = PR.pack(x, bits, stride, None)                   # pseudo-random bytes in the padding
-    big = torch.full((data.size + 16,), 0xFF, dtype=torch.uint8, device='cuda')
-    pk = big[offset:offset + data.size].view(data.shape)
-    pk.copy_(torch.from_numpy(data))
-    return pk
 
 
 PATTERN64, PATTERN32 = 0x5A5A5A5A5A5A5A5A, 0x5A5A5A5A

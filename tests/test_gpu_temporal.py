@@ -16,6 +16,7 @@ import torch
 
 import temporal_reference as TR
 from guarded import Guarded
+from raw_placement import _place16
 
 pytestmark = pytest.mark.gpu
 
@@ -43,14 +44,6 @@ def _state(shape):
     st = F.temporal_state(*shape)
     st.frames = frames
     return g, st
-
-
-def _place16(x, at):
-    """the numpy uint16 frames as a contiguous device view ``at`` words into an allocation of 0xFF bytes"""
-    big = torch.full((x.size + 8,), 0xFFFF, dtype=torch.uint16).cuda()
-    dev = big[at:at + x.size].view(x.shape)
-    dev.copy_(torch.from_numpy(x))
-    return dev
 
 
 _REF = {}
