@@ -4,13 +4,12 @@
 //
 // Vector form (W % 4 == 0, both buffers 4-byte aligned): a thread owns a 2 x 4 pixel patch - two chroma quads -, loads the three
 // dwords of each of its two rows (the row offset is a multiple of 12 bytes) and stores one Y dword per row and one UV dword.
-// Scalar form (any even W, any alignment): a thread owns one quad and moves bytes.
-#include "risp_common.h"
-#include "risp_nv12.h"
+// Scalar form (any even W, any alignment): a thread owns one quad and moves bytes.  unpack4 is risp_bgr8tile.h's.
+#include "risp_bgr8tile.h"
 
 namespace {
 
-using namespace risp_nv12;
+using namespace risp_bgr8tile;
 
 __global__ __launch_bounds__(256) void bgr8_to_nv12_vec_kernel(const uint8_t *__restrict__ img, uint8_t *__restrict__ out, const Coef m,
                                                                int rgb_in, size_t patches, int H, int w4) {
@@ -22,12 +21,7 @@ __global__ __launch_bounds__(256) void bgr8_to_nv12_vec_kernel(const uint8_t *__
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const unsigned *src = reinterpret_cast<const unsigned *>(img + (((size_t)n * H + py + p) * W + px) * 3);
-            const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
-            const unsigned c0[4] = {d0 & 255u, d0 >> 24, d1 >> 16 & 255u, d2 >> 8 & 255u};         // first byte of each pixel
-            const unsigned c2[4] = {d0 >> 16 & 255u, d1 >> 8 & 255u, d2 & 255u, d2 >> 24};         // third byte
-            g[p][0] = d0 >> 8 & 255u, g[p][1] = d1 & 255u, g[p][2] = d1 >> 24, g[p][3] = d2 >> 16 & 255u;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) r[p][c] = rgb_in ? c0[c] : c2[c], b[p][c] = rgb_in ? c2[c] : c0[c];
+            unpack4(src[0], src[1], src[2], rgb_in, r[p], g[p], b[p]);
         }
         nv12_store_patch(out + n * ((size_t)(H + h2) * W), m, r, g, b, H, W, py, px, 0);
     }

@@ -8,20 +8,18 @@
 //            bytes: a thread makes one dword (4 of a row's 192 bytes) per step, its source bytes come from global memory
 //            (neighbouring lanes read neighbouring and overlapping taps, which the vector cache serves).
 //   phase 2  vertical sums from LDS, one dword per LDS row and tap.  BGR: a thread makes one dword of an output row and stores
-//            it whole where its address is 4-byte aligned and inside the row, byte by byte otherwise (a packed row starts at any
-//            byte).  NV12: a thread makes a 2 x 4 pixel patch - two Y dwords and one UV dword through nv12_dot / nv12_uv - and
-//            stores dwords where OW % 4 == 0, byte pairs otherwise.
+//            it by the policy of a packed row (store_dword of risp_bgr8tile.h, which owns every store here).  NV12: a thread
+//            makes a 2 x 4 pixel patch - two Y dwords and one UV dword - and stores dwords where OW % 4 == 0, byte pairs otherwise.
 // LDS: span x 192 bytes of rows plus the table slices (at most 6.4 KB), dynamic, at most RISP_RESIZE_LDS_BYTES.  The span is the
 // caller's, since only the caller has read ystart; every LDS row index is clamped into the rows phase 1 wrote and every source
 // index into the image, so no table can make an access leave either.
-#include "risp_common.h"
-#include "risp_nv12.h"
+#include "risp_bgr8tile.h"
 
 namespace {
 
-using namespace risp_nv12;
+using namespace risp_bgr8tile;
 
-constexpr int TW = RISP_RESIZE_TILE_W, ROWB = TW * 3, ROWD = ROWB / 4;
+static_assert(TW == RISP_RESIZE_TILE_W, "the tile of risp_bgr8tile.h");
 
 struct Geo {
     int H, W, OH, OW, tx, ty, rows, span;
@@ -31,7 +29,6 @@ __host__ __device__ inline size_t resize_lds_bytes(int span, int rows, int tx, i
     return (size_t)span * ROWB + (size_t)(TW + rows) * 4 + ((size_t)TW * tx + (size_t)rows * ty) * 2;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 // a Q14 sum -> a code: rounded, floored by the arithmetic shift, clamped
 __device__ __forceinline__ unsigned q14_code(int s) { return (unsigned)clampi((s + 8192) >> 14, 0, 255); }
 
@@ -93,14 +90,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const uint8_t *__restrict__
                     s[3] += wk * (int)(v >> 24);
             }
             const unsigned pack = q14_code(s[0]) | q14_code(s[1]) << 8 | q14_code(s[2]) << 16 | q14_code(s[3]) << 24;
-            uint8_t *p = dst + (size_t)(i0 + i) * g.OW * 3 + d * 4;
-            if (d * 4 + 4 <= valid && reinterpret_cast<uintptr_t>(p) % 4 == 0) {
-                *reinterpret_cast<unsigned *>(p) = pack;
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    if (d * 4 + b < valid) p[b] = (uint8_t)(pack >> (8 * b));
-            }
+            store_dword(dst + (size_t)(i0 + i) * g.OW * 3 + d * 4, pack, d * 4, valid);
         }
     } else {
         // OH, OW, g.rows even: i0 and rows are even, a patch has two whole rows and one or two whole quads
@@ -131,28 +121,9 @@ __global__ __launch_bounds__(256) void resize_kernel(const uint8_t *__restrict__
                 }
             }
             unsigned y[2], uv[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-                y[a] = nv12_dot(m.k, R[a][0], G[a][0], B[a][0]) | nv12_dot(m.k, R[a][1], G[a][1], B[a][1]) << 8 |
-                       nv12_dot(m.k, R[a][2], G[a][2], B[a][2]) << 16 | nv12_dot(m.k, R[a][3], G[a][3], B[a][3]) << 24;
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                uv[h] = nv12_uv(m, R[0][2 * h] + R[0][2 * h + 1] + R[1][2 * h] + R[1][2 * h + 1],
-                                G[0][2 * h] + G[0][2 * h + 1] + G[1][2 * h] + G[1][2 * h + 1],
-                                B[0][2 * h] + B[0][2 * h + 1] + B[1][2 * h] + B[1][2 * h + 1]);
+            nv12_patch(m, R, G, B, y, uv);
             uint8_t *py = dst + (size_t)(i0 + 2 * p) * g.OW + j0 + col, *pc = dst + (size_t)(g.OH + i0 / 2 + p) * g.OW + j0 + col;
-            if (wide) {
-                *reinterpret_cast<unsigned *>(py) = y[0];
-                *reinterpret_cast<unsigned *>(py + g.OW) = y[1];
-                *reinterpret_cast<unsigned *>(pc) = uv[0] | uv[1] << 16;
-            } else {
-                const int pairs = col + 4 <= cols ? 2 : 1;
-                for (int h = 0; h < pairs; ++h) {
-                    *reinterpret_cast<unsigned short *>(py + 2 * h) = (unsigned short)(y[0] >> (16 * h));
-                    *reinterpret_cast<unsigned short *>(py + g.OW + 2 * h) = (unsigned short)(y[1] >> (16 * h));
-                    *reinterpret_cast<unsigned short *>(pc + 2 * h) = (unsigned short)uv[h];
-                }
-            }
+            nv12_store_patch_at<true>(py, pc, g.OW, wide, col + 4 <= cols ? 2 : 1, y, uv);   // OW even, out aligned: byte pairs
         }
     }
 }
@@ -163,10 +134,9 @@ extern "C" int risp_bgr8_resize(const uint8_t *img, uint8_t *out, const int32_t 
                                 const int32_t *ystart, const int16_t *yweight, int ty, int tile_rows, int span, const int32_t *coef,
                                 int rgb_in, int N, int H, int W, int OH, int OW, void *stream) {
     const char *name = "risp_bgr8_resize";
-    const int lim = 1 << 24;
     RISP_CHECK_ARG(img && out && xstart && xweight && ystart && yweight, "%s: null argument", name);
-    RISP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= lim && W >= 1 && W <= lim && OH >= 1 && OH <= lim && OW >= 1 && OW <= lim,
-                   "%s: bad shape N=%d H=%d W=%d OH=%d OW=%d (N <= 65535, sizes 1 .. 2^24)", name, N, H, W, OH, OW);
+    RISP_CHECK_ARG(sizes_ok(1 << 24, N, H, W, OH, OW), "%s: bad shape N=%d H=%d W=%d OH=%d OW=%d (N <= 65535, sizes 1 .. 2^24)", name, N,
+                   H, W, OH, OW);
     RISP_CHECK_ARG(tx >= 1 && tx <= RISP_RESIZE_MAX_TAPS && ty >= 1 && ty <= RISP_RESIZE_MAX_TAPS,
                    "%s: %d x %d taps: at most RISP_RESIZE_MAX_TAPS = %d per axis (the largest served reductions are about 32:1 box, "
                    "16:1 triangle, 8:1 bicubic)",
@@ -178,7 +148,7 @@ extern "C" int risp_bgr8_resize(const uint8_t *img, uint8_t *out, const int32_t 
                    "%s: a span of %d source rows with %d tile rows needs %zu bytes of LDS, at most %d: take fewer tile rows", name, span,
                    tile_rows, lds, RISP_RESIZE_LDS_BYTES);
     const size_t in_bytes = (size_t)N * H * W * 3, out_bytes = coef ? (size_t)N * (OH + OH / 2) * OW : (size_t)N * OH * OW * 3;
-    RISP_CHECK_ARG(out + out_bytes <= img || img + in_bytes <= out, "%s: out overlaps img: a tile reads rows other tiles write", name);
+    if (int err = apart_check(name, img, in_bytes, out, out_bytes, "rows")) return err;
     Coef m = {};
     if (coef) {
         RISP_CHECK_ARG(OH % 2 == 0 && OW % 2 == 0 && tile_rows % 2 == 0, "%s: NV12 out needs OH, OW and tile_rows even, got %d x %d, %d",

@@ -4,34 +4,28 @@
 // integer definition; tests/sharpen_reference.py restates it in numpy.
 //
 // A workgroup of 256 threads owns RISP_SHARPEN_TILE_W x RISP_SHARPEN_TILE_H = 64 x 16 pixels.
-//   phase 0  the tile's source box - the tile widened by the radius, clamped into the image - goes to LDS, a dword per thread
-//            and step.  A box row is read from the 4-byte aligned address at or below its first byte (a packed row starts at any
-//            byte), so lanes read consecutive aligned dwords; a dword that is not wholly inside img - at most the first and the
-//            last of the whole buffer - is put together from guarded byte loads.
+//   phase 0  the tile's source box - the tile widened by the radius, clamped into the image - goes to LDS (stage_box of
+//            risp_bgr8tile.h, which owns the loads of an image that starts at any byte and every store below).
 //   phase 1  the luma byte of every pixel of the (64 + 2R) x (16 + 2R) halo, its indices clamped into the image (they stay
 //            inside the box by construction).
 //   phase 2  the horizontal binomial sums of the 64 columns for the 16 + 2R halo rows, 16 bits each.
 //   phase 3  a thread owns one column and four consecutive rows: 4 + 2R horizontal sums from LDS give its four blurs; detail,
 //            coring, gain, limit, and the three clamped channels go to a 16 x 192 byte image of the tile in LDS.
-//   phase 4  BGR: the tile is stored, a dword per thread where its address is 4-byte aligned and wholly inside the row, bytes
-//            otherwise.  NV12: a thread makes a 2 x 4 pixel patch - two Y dwords and one UV dword through nv12_dot / nv12_uv -
+//   phase 4  BGR: the tile is stored (store_tile).  NV12: a thread makes a 2 x 4 pixel patch - two Y dwords and one UV dword -
 //            and stores dwords where W % 4 == 0 and out is 4-byte aligned, bytes otherwise.
 // LDS: static, 11.2 KB (radius 2) or 10.1 KB (radius 1).  No scratch.
-#include "risp_common.h"
-#include "risp_nv12.h"
+#include "risp_bgr8tile.h"
 
 namespace {
 
-using namespace risp_nv12;
+using namespace risp_bgr8tile;
 
-constexpr int TW = RISP_SHARPEN_TILE_W, TH = RISP_SHARPEN_TILE_H, ROWB = TW * 3, ROWD = ROWB / 4, PIX = TW * TH / 256;
-static_assert(TW == 64 && TH == 4 * PIX && PIX == 4 && ROWB % 4 == 0, "a wave owns one 64-pixel row at a time, a thread four consecutive rows");
+constexpr int TH = RISP_SHARPEN_TILE_H, PIX = TW * TH / 256;
+static_assert(TW == RISP_SHARPEN_TILE_W && TH == 4 * PIX && PIX == 4, "a wave owns one 64-pixel row at a time, a thread four consecutive rows");
 
 struct Par {
     int rgb_in, amount, thr256, limit;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 template <int R, bool NV12>
 __global__ __launch_bounds__(256) void sharpen_kernel(const uint8_t *__restrict__ img, uint8_t *__restrict__ out, const Coef m,
@@ -43,43 +37,18 @@ __global__ __launch_bounds__(256) void sharpen_kernel(const uint8_t *__restrict_
     __shared__ unsigned short s_h[HH * TW];                         // horizontal binomial sums of luma
     __shared__ uint8_t s_l[HH * HW];                                // luma of the halo
     uint8_t *s_out = reinterpret_cast<uint8_t *>(s_outd);
-    const uint8_t *box = reinterpret_cast<const uint8_t *>(s_box);
     const int tid = threadIdx.x, j0 = blockIdx.x * TW, i0 = blockIdx.y * TH, n = blockIdx.z;
     const int cols = min(TW, W - j0), rows = min(TH, H - i0);
 
-    // phase 0: rows by0 .. by1 and columns bx0 .. bx1 of image n
+    // phase 0
     const int by0 = max(i0 - R, 0), by1 = min(i0 + rows - 1 + R, H - 1), bx0 = max(j0 - R, 0), bx1 = min(j0 + cols - 1 + R, W - 1);
-    const int brows = by1 - by0 + 1, bbytes = (bx1 - bx0 + 1) * 3, rw3 = (W * 3) & 3;
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(img);
-    const uintptr_t first = lo + (((size_t)n * H + by0) * W + bx0) * 3;
-    const int a0 = (int)(first & 3);
-    const long long total = (long long)N * H * W * 3;
-    for (int t = tid; t < brows * PD; t += 256) {
-        const int r = t / PD, d = t - r * PD;
-        const uintptr_t begin = first + (size_t)r * W * 3, a = (begin & ~(uintptr_t)3) + (size_t)d * 4;
-        if (a >= begin + bbytes) continue;                          // a dword behind the row's last byte: never read below
-        const long long off = (long long)(a - lo);                  // from img's first byte: -3 at the least
-        unsigned v = 0;
-        if (off >= 0 && off + 4 <= total) {
-            v = *reinterpret_cast<const unsigned *>(img + off);
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (off + b >= 0 && off + b < total) v |= (unsigned)img[off + b] << (8 * b);
-        }
-        s_box[t] = v;
-    }
+    const Box box = stage_box<PITCH>(img, N, H, W, img + (((size_t)n * H + by0) * W + bx0) * 3, by0, by1, bx0, bx1, s_box, tid);
     __syncthreads();
-    // the bytes of pixel (y, x) of the image, by0 <= y <= by1 and bx0 <= x <= bx1
-    auto at = [&](int y, int x) -> const uint8_t * {
-        const int r = y - by0;
-        return box + r * PITCH + ((a0 + r * rw3) & 3) + (x - bx0) * 3;
-    };
 
-    // phase 1: the clamped indices lie inside the box - by1 is the clamp of the halo's last row, bx1 of its last column
+    // phase 1: the clamped indices lie inside the box - its last row is the clamp of the halo's last row, its last column likewise
     for (int t = tid; t < HH * HW; t += 256) {
         const int r = t / HW, c = t - r * HW;
-        const uint8_t *p = at(clampi(i0 - R + r, 0, H - 1), clampi(j0 - R + c, 0, W - 1));
+        const uint8_t *p = box.at(clampi(i0 - R + r, 0, H - 1), clampi(j0 - R + c, 0, W - 1));
         const unsigned c0 = p[0], g = p[1], c2 = p[2], rr = par.rgb_in ? c0 : c2, bb = par.rgb_in ? c2 : c0;
         s_l[t] = (uint8_t)((77u * rr + 150u * g + 29u * bb + 128u) >> 8);
     }
@@ -107,7 +76,7 @@ __global__ __launch_bounds__(256) void sharpen_kernel(const uint8_t *__restrict_
             const int D = 256 * (int)s_l[(py + R) * HW + px + R] - S;
             const unsigned A = (unsigned)max((D < 0 ? -D : D) - par.thr256, 0);
             const int E = (int)min((A * (unsigned)par.amount + 32768u) >> 16, (unsigned)par.limit), step = D < 0 ? -E : E;
-            const uint8_t *p = at(i0 + py, j0 + px);
+            const uint8_t *p = box.at(i0 + py, j0 + px);
             uint8_t *dst = s_out + py * ROWB + px * 3;
 #pragma unroll
             for (int c = 0; c < 3; ++c) dst[c] = (uint8_t)clampi((int)p[c] + step, 0, 255);
@@ -117,20 +86,7 @@ __global__ __launch_bounds__(256) void sharpen_kernel(const uint8_t *__restrict_
 
     // phase 4
     if (!NV12) {
-        uint8_t *dst = out + ((size_t)n * H * W + j0) * 3;
-        const int valid = cols * 3;
-        for (int t = tid; t < rows * ROWD; t += 256) {
-            const int i = t / ROWD, d = t - i * ROWD;
-            if (d * 4 >= valid) continue;
-            uint8_t *p = dst + (size_t)(i0 + i) * W * 3 + d * 4;
-            if (d * 4 + 4 <= valid && reinterpret_cast<uintptr_t>(p) % 4 == 0) {
-                *reinterpret_cast<unsigned *>(p) = s_outd[t];
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    if (d * 4 + b < valid) p[b] = s_out[t * 4 + b];
-            }
-        }
+        store_tile(out + (((size_t)n * H + i0) * W + j0) * 3, (size_t)W * 3, s_outd, rows, cols, tid);
     } else {
         // H and W even: i0 and rows are even, a patch has two whole rows and one or two whole quads
         uint8_t *dst = out + (size_t)n * (H + H / 2) * W;
@@ -138,41 +94,15 @@ __global__ __launch_bounds__(256) void sharpen_kernel(const uint8_t *__restrict_
         for (int t = tid; t < (rows / 2) * (TW / 4); t += 256) {
             const int p = t / (TW / 4), q = t - p * (TW / 4), col = q * 4;
             if (col >= cols) continue;
-            unsigned r[2][4], g[2][4], b[2][4];
+            unsigned r[2][4], g[2][4], b[2][4], y[2], uv[2];
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const unsigned *src = s_outd + (2 * p + a) * ROWD + q * 3;
-                const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
-                const unsigned c0[4] = {d0 & 255u, d0 >> 24, d1 >> 16 & 255u, d2 >> 8 & 255u};         // first byte of each pixel
-                const unsigned c2[4] = {d0 >> 16 & 255u, d1 >> 8 & 255u, d2 & 255u, d2 >> 24};         // third byte
-                g[a][0] = d0 >> 8 & 255u, g[a][1] = d1 & 255u, g[a][2] = d1 >> 24, g[a][3] = d2 >> 16 & 255u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) r[a][c] = par.rgb_in ? c0[c] : c2[c], b[a][c] = par.rgb_in ? c2[c] : c0[c];
+                unpack4(src[0], src[1], src[2], par.rgb_in, r[a], g[a], b[a]);
             }
-            unsigned y[2], uv[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-                y[a] = nv12_dot(m.k, r[a][0], g[a][0], b[a][0]) | nv12_dot(m.k, r[a][1], g[a][1], b[a][1]) << 8 |
-                       nv12_dot(m.k, r[a][2], g[a][2], b[a][2]) << 16 | nv12_dot(m.k, r[a][3], g[a][3], b[a][3]) << 24;
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                uv[h] = nv12_uv(m, r[0][2 * h] + r[0][2 * h + 1] + r[1][2 * h] + r[1][2 * h + 1],
-                                g[0][2 * h] + g[0][2 * h + 1] + g[1][2 * h] + g[1][2 * h + 1],
-                                b[0][2 * h] + b[0][2 * h + 1] + b[1][2 * h] + b[1][2 * h + 1]);
+            nv12_patch(m, r, g, b, y, uv);
             uint8_t *py = dst + (size_t)(i0 + 2 * p) * W + j0 + col, *pc = dst + (size_t)(H + i0 / 2 + p) * W + j0 + col;
-            if (wide) {
-                *reinterpret_cast<unsigned *>(py) = y[0];
-                *reinterpret_cast<unsigned *>(py + W) = y[1];
-                *reinterpret_cast<unsigned *>(pc) = uv[0] | uv[1] << 16;
-            } else {
-                const int bytes = col + 4 <= cols ? 4 : 2;          // (a packed NV12 image starts at any byte too)
-                const unsigned c = uv[0] | uv[1] << 16;
-                for (int k = 0; k < bytes; ++k) {
-                    py[k] = (uint8_t)(y[0] >> (8 * k));
-                    py[W + k] = (uint8_t)(y[1] >> (8 * k));
-                    pc[k] = (uint8_t)(c >> (8 * k));
-                }
-            }
+            nv12_store_patch_at(py, pc, W, wide, col + 4 <= cols ? 2 : 1, y, uv);   // (a packed NV12 image starts at any byte too)
         }
     }
 }
@@ -182,19 +112,17 @@ __global__ __launch_bounds__(256) void sharpen_kernel(const uint8_t *__restrict_
 extern "C" int risp_bgr8_sharpen(const uint8_t *img, uint8_t *out, const int32_t *coef, int rgb_in, int radius, int amount,
                                  int threshold, int limit, int N, int H, int W, void *stream) {
     const char *name = "risp_bgr8_sharpen";
-    const int lim = 1 << 24;
     RISP_CHECK_ARG(img && out, "%s: null argument (img %p, out %p)", name, (const void *)img, (void *)out);
-    RISP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= lim && W >= 1 && W <= lim,
-                   "%s: bad shape N=%d H=%d W=%d (N <= 65535, sizes 1 .. 2^24)", name, N, H, W);
+    RISP_CHECK_ARG(sizes_ok(1 << 24, N, H, W), "%s: bad shape N=%d H=%d W=%d (N <= 65535, sizes 1 .. 2^24)", name, N, H, W);
     RISP_CHECK_ARG(radius == 1 || radius == 2, "%s: radius %d: 1 (3 x 3 binomial blur) or 2 (5 x 5)", name, radius);
     RISP_CHECK_ARG(amount >= 0 && amount <= RISP_SHARPEN_MAX_AMOUNT, "%s: amount %d: 0 .. %d (Q8: 256 is 1.0)", name, amount,
                    RISP_SHARPEN_MAX_AMOUNT);
     RISP_CHECK_ARG(threshold >= 0 && threshold <= 255, "%s: threshold %d: 0 .. 255 codes", name, threshold);
     RISP_CHECK_ARG(limit >= 0 && limit <= 255, "%s: limit %d: 0 .. 255 codes", name, limit);
-    const unsigned gy = (unsigned)((H + TH - 1) / TH);
-    RISP_CHECK_ARG(gy <= 65535, "%s: %u row tiles for H=%d, at most 65535", name, gy, H);
+    unsigned gy;
+    if (int err = row_tiles(name, "H", H, TH, gy)) return err;
     const size_t in_bytes = (size_t)N * H * W * 3, out_bytes = coef ? (size_t)N * (H + H / 2) * W : in_bytes;
-    RISP_CHECK_ARG(out + out_bytes <= img || img + in_bytes <= out, "%s: out overlaps img: a tile reads pixels other tiles write", name);
+    if (int err = apart_check(name, img, in_bytes, out, out_bytes, "pixels")) return err;
     Coef m = {};
     if (coef) {
         RISP_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "%s: NV12 out needs H and W even, got %d x %d", name, H, W);

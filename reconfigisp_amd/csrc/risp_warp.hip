@@ -8,21 +8,21 @@
 //            clamped Q8 coordinates of its four pixels from the four mesh nodes of their cell (64-bit products) and keeps them.
 //   phase 1  the smallest and largest integer source row and column of the tile (LDS atomics), widened by the kernel's taps and
 //            clamped into the image: the tile's source box.
-//   phase 2  stage = 1 and the box fits: the box goes to LDS, a dword per thread and step.  A box row is read from the 4-byte
-//            aligned address at or below its first byte (a packed row starts at any byte), so lanes read consecutive aligned
-//            dwords; a dword that is not wholly inside img - at most the first and the last of the whole buffer - is put together
-//            from guarded byte loads.  Otherwise (stage = 0, or a strong reduction, a twisted cell, a meaningless mesh) the tile
-//            samples global memory.  The decision is the same for every thread of the workgroup.
+//   phase 2  stage = 1 and the box fits: the box goes to LDS (stage_box of risp_bgr8tile.h, which owns the loads of an image that
+//            starts at any byte and the store of phase 4).  Otherwise (stage = 0, or a strong reduction, a twisted cell, a
+//            meaningless mesh) the tile samples global memory.  The decision is the same for every thread of the workgroup.
 //   phase 3  the taps, from LDS bytes or global bytes - the same integer function -, into a 16 x 192 byte image of the tile in LDS.
-//   phase 4  the tile is stored: a dword per thread where its address is 4-byte aligned and wholly inside the row, bytes otherwise.
+//   phase 4  the tile is stored (store_tile).
 // LDS: dynamic; 2048 bytes of weights, 16 of box corners, 3072 of output tile, then the box (stage = 1: RISP_WARP_LDS_BYTES in
 // all, stage = 0 the fixed part only).  Every coordinate is clamped into the image before it is used, so no mesh can make an
 // access leave img, and every LDS index derives from coordinates inside the box by construction.
-#include "risp_common.h"
+#include "risp_bgr8tile.h"
 
 namespace {
 
-constexpr int TW = RISP_WARP_TILE_W, TH = RISP_WARP_TILE_H, ROWB = TW * 3, ROWD = ROWB / 4, PIX = TW * TH / 256;
+using namespace risp_bgr8tile;
+
+constexpr int TH = RISP_WARP_TILE_H, PIX = TW * TH / 256;
 constexpr int FIXED_LDS = 256 * 4 * 2 + 16 + TH * ROWB;
 // what a stage = 1 launch asks for and a tile's box has to fit beside the fixed part.  RISP_WARP_AB_LDS: the ablation builds of
 // profiles/serve_warp_lds.txt (make EXTRA=-DRISP_WARP_AB_LDS=16384), never the library's
@@ -31,14 +31,12 @@ constexpr int LDS_BYTES = RISP_WARP_AB_LDS;
 #else
 constexpr int LDS_BYTES = RISP_WARP_LDS_BYTES;
 #endif
-static_assert(TW == 64 && (TW * TH) % 256 == 0 && ROWB % 4 == 0, "a wave owns one 64-pixel row of the tile at a time");
+static_assert(TW == RISP_WARP_TILE_W && (TW * TH) % 256 == 0, "a wave owns one 64-pixel row of the tile at a time");
 static_assert(FIXED_LDS % 4 == 0 && FIXED_LDS < LDS_BYTES && LDS_BYTES <= 65536, "the box begins on a dword");
 
 struct Geo {
     int H, W, WH, WW, k, MW;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // row f of the Catmull-Rom table: Q11, the four weights sum to exactly 2048
 __device__ __forceinline__ void cubic_row(int f, short *q) {
@@ -67,15 +65,7 @@ __device__ __forceinline__ int patch_coord(int m00, int m01, int m10, int m11, i
     return (int)(u < 0 ? 0 : (u > hi ? hi : u));
 }
 
-// the bytes of a pixel: from the staged box (row pitch `pitch`, box row r begins `shift(r)` bytes into its LDS row) or from img
-struct BoxFetch {
-    const uint8_t *box;
-    int by0, bx0, pitch, a0, rw3;
-    __device__ __forceinline__ const uint8_t *at(int y, int x) const {
-        const int r = y - by0;
-        return box + r * pitch + ((a0 + r * rw3) & 3) + (x - bx0) * 3;
-    }
-};
+// the bytes of a pixel: from the staged Box or from img
 struct ImgFetch {
     const uint8_t *src;
     int W;
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t *__restrict__ i
     __syncthreads();
     const uint8_t *src = img + (size_t)n * H * W * 3;
     bool staged = false;
-    BoxFetch bf = {};
+    Box bf = {};
     if (stage) {                                                        // (the same in every thread)
         int y_lo = uy[0] >> 8, y_hi = y_lo, x_lo = ux[0] >> 8, x_hi = x_lo;
 #pragma unroll
@@ -158,31 +148,10 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t *__restrict__ i
         // the taps: bilinear rows y0 .. y0+1, bicubic y0-1 .. y0+2, every index clamped into the image
         const int by0 = max(s_box[0] - (CUBIC ? 1 : 0), 0), by1 = min(s_box[1] + (CUBIC ? 2 : 1), H - 1);
         const int bx0 = max(s_box[2] - (CUBIC ? 1 : 0), 0), bx1 = min(s_box[3] + (CUBIC ? 2 : 1), W - 1);
-        const long long brows = by1 - by0 + 1, bbytes = (long long)(bx1 - bx0 + 1) * 3;
-        const long long pitch = (bbytes + 3 + 3) & ~3LL;               // up to 3 bytes in front of the row's first, whole dwords
-        staged = brows * pitch <= LDS_BYTES - FIXED_LDS;
+        const long long pitch = ((long long)(bx1 - bx0 + 1) * 3 + 3 + 3) & ~3LL;   // up to 3 bytes in front of the row's first, whole dwords
+        staged = (by1 - by0 + 1) * pitch <= LDS_BYTES - FIXED_LDS;
         if (staged) {
-            const int pd = (int)pitch / 4, rw3 = (W * 3) & 3;
-            const uintptr_t first = reinterpret_cast<uintptr_t>(src) + ((size_t)by0 * W + bx0) * 3;
-            const uintptr_t lo = reinterpret_cast<uintptr_t>(img);
-            const long long total = (long long)N * H * W * 3;
-            bf.box = reinterpret_cast<const uint8_t *>(s_src), bf.by0 = by0, bf.bx0 = bx0, bf.pitch = (int)pitch;
-            bf.a0 = (int)(first & 3), bf.rw3 = rw3;
-            for (int t = tid; t < (int)brows * pd; t += 256) {
-                const int r = t / pd, d = t - r * pd;
-                const uintptr_t begin = first + (size_t)r * W * 3, a = (begin & ~(uintptr_t)3) + (size_t)d * 4;
-                if (a >= begin + bbytes) continue;                      // a dword behind the row's last byte: never sampled
-                const long long off = (long long)(a - lo);             // from img's first byte: -3 at the least
-                unsigned v = 0;
-                if (off >= 0 && off + 4 <= total) {
-                    v = *reinterpret_cast<const unsigned *>(img + off);
-                } else {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        if (off + b >= 0 && off + b < total) v |= (unsigned)img[off + b] << (8 * b);
-                }
-                s_src[t] = v;
-            }
+            bf = stage_box(img, N, H, W, src + ((size_t)by0 * W + bx0) * 3, by0, by1, bx0, bx1, s_src, tid, (int)pitch);
             __syncthreads();
         }
     }
@@ -201,21 +170,8 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t *__restrict__ i
         }
     }
     __syncthreads();
-    uint8_t *dst = out + ((size_t)n * g.WH * g.WW + j0) * 3;
-    const int valid = cols * 3;
-    const unsigned *s_outd = reinterpret_cast<const unsigned *>(s_out);
-    for (int t = tid; t < rows * ROWD; t += 256) {
-        const int i = t / ROWD, d = t - i * ROWD;
-        if (d * 4 >= valid) continue;
-        uint8_t *p = dst + (size_t)(i0 + i) * g.WW * 3 + d * 4;
-        if (d * 4 + 4 <= valid && reinterpret_cast<uintptr_t>(p) % 4 == 0) {
-            *reinterpret_cast<unsigned *>(p) = s_outd[t];
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (d * 4 + b < valid) p[b] = s_out[t * 4 + b];
-        }
-    }
+    store_tile(out + (((size_t)n * g.WH + i0) * g.WW + j0) * 3, (size_t)g.WW * 3, reinterpret_cast<const unsigned *>(s_out), rows, cols,
+               tid);
 }
 
 }  // namespace
@@ -223,10 +179,9 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t *__restrict__ i
 extern "C" int risp_bgr8_warp(const uint8_t *img, uint8_t *out, const int32_t *mesh, int cell_log2, int MH, int MW, int kernel,
                               int stage, int N, int H, int W, int WH, int WW, void *stream) {
     const char *name = "risp_bgr8_warp";
-    const int lim = 1 << 23;
     RISP_CHECK_ARG(img && out && mesh, "%s: null argument (img %p, out %p, mesh %p)", name, (const void *)img, (void *)out,
                    (const void *)mesh);
-    RISP_CHECK_ARG(N >= 1 && N <= 65535 && H >= 1 && H <= lim && W >= 1 && W <= lim && WH >= 1 && WH <= lim && WW >= 1 && WW <= lim,
+    RISP_CHECK_ARG(sizes_ok(1 << 23, N, H, W, WH, WW),
                    "%s: bad shape N=%d H=%d W=%d WH=%d WW=%d (N <= 65535, sizes 1 .. 2^23: a Q8 coordinate fits int32)", name, N, H, W,
                    WH, WW);
     RISP_CHECK_ARG(cell_log2 >= 2 && cell_log2 <= 8, "%s: cell_log2 %d: 2 .. 8 (cells of 4 .. 256 pixels)", name, cell_log2);
@@ -235,10 +190,9 @@ extern "C" int risp_bgr8_warp(const uint8_t *img, uint8_t *out, const int32_t *m
                    MW, WH, WW, cell_log2, mh, mw);
     RISP_CHECK_ARG(kernel == 0 || kernel == 1, "%s: kernel %d: 0 (bilinear) or 1 (bicubic)", name, kernel);
     RISP_CHECK_ARG(stage == 0 || stage == 1, "%s: stage %d: 0 (sample global memory) or 1 (stage the source box in LDS)", name, stage);
-    const unsigned gy = (unsigned)((WH + TH - 1) / TH);
-    RISP_CHECK_ARG(gy <= 65535, "%s: %u row tiles for WH=%d, at most 65535", name, gy, WH);
-    const size_t in_bytes = (size_t)N * H * W * 3, out_bytes = (size_t)N * WH * WW * 3;
-    RISP_CHECK_ARG(out + out_bytes <= img || img + in_bytes <= out, "%s: out overlaps img: a tile reads pixels other tiles write", name);
+    unsigned gy;
+    if (int err = row_tiles(name, "WH", WH, TH, gy)) return err;
+    if (int err = apart_check(name, img, (size_t)N * H * W * 3, out, (size_t)N * WH * WW * 3, "pixels")) return err;
     RISP_CHECK_ARG(reinterpret_cast<uintptr_t>(mesh) % 8 == 0, "%s: mesh %p must be 8-byte aligned", name, (const void *)mesh);
     const Geo g = {H, W, WH, WW, cell_log2, MW};
     const dim3 grid((unsigned)((WW + TW - 1) / TW), gy, (unsigned)N);

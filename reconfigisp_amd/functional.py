@@ -515,14 +515,17 @@ class BilateralChainPlan:
         return self.outs
 
 
-def _u8_out(out, shape, device, align):
-    """the caller's byte buffer when it fits (uint8, contiguous, on the device, ``align``-byte aligned), else a new one"""
+def _u8_out(out, shape, device, align, apart=None, what=None):
+    """the caller's byte buffer when it fits (uint8, contiguous, on the device, ``align``-byte aligned), else a new one.  ``apart``:
+    uint8 images whose memory the caller's ``out`` must not share - a tile reads ``what`` ('rows', 'pixels') other tiles write"""
     if out is None:
         return torch.empty(shape, device=device, dtype=torch.uint8)
     if (out.dtype != torch.uint8 or out.device != device or tuple(out.shape) != tuple(shape) or not out.is_contiguous()
             or out.data_ptr() % align):
         raise ValueError('out must be a contiguous uint8 %s tensor on %s, %d-byte aligned; got %s %s'
                          % (tuple(shape), device, align, out.dtype, tuple(out.shape)))
+    if apart is not None and out.data_ptr() < apart.data_ptr() + apart.numel() and apart.data_ptr() < out.data_ptr() + out.numel():
+        raise ValueError('out shares memory with the images: a tile reads %s other tiles would have overwritten' % what)
     return out
 
 
@@ -750,24 +753,54 @@ def nv12_matrix(matrix):
     return coef
 
 
+# ---- what the bgr8_* wrappers share: each check stated once; a wrapper keeps the order in which it applies them
+def _bgr8_images(img_u8):
+    """(N,H,W,3) or (H,W,3) uint8 images, on any device -> (n, h, w, the shape in front of H: (N,) or ())"""
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
+        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
+                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
+    return img_u8.shape[0] if img_u8.dim() == 4 else 1, img_u8.shape[-3], img_u8.shape[-2], tuple(img_u8.shape[:-3])
+
+
+def _bgr8_batch(img_u8, n):
+    """the ``n`` images of one tiled launch: on the device, at most 65535 (the grid's z), contiguous - a copy where they are not"""
+    _need_gpu(img_u8, 'img')
+    if n > 65535:
+        raise ValueError('%d images in one call: at most 65535' % n)
+    return img_u8.contiguous()
+
+
+def _channels(channels):
+    """'bgr' | 'rgb' -> the ``rgb_in`` argument, 0 | 1"""
+    if channels not in ('bgr', 'rgb'):
+        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    return int(channels == 'rgb')
+
+
+def _check_420(h, w, what='image', names='H and W', least=0):
+    """4:2:0 has one chroma sample per 2 x 2 quad: both sizes even (and at least ``least``)"""
+    if h % 2 or w % 2 or h < least or w < least:
+        raise ValueError('a %d x %d %s has no 4:2:0 form: %s must be even' % (h, w, what, names))
+
+
+def _coef12(coef):
+    """the twelve integers of ``nv12_matrix`` as the C array of the entry points, None as None"""
+    return None if coef is None else (C.c_int * 12)(*coef)
+
+
 def bgr8_to_nv12(img_u8, matrix='bt601_full', channels='bgr', out=None):
     """Packed 8-bit images to YUV 4:2:0 in ONE launch (``risp_bgr8_to_nv12``): (N,H,W,3) or (H,W,3) ``torch.uint8`` on the
     device, ``channels`` 'bgr' or 'rgb', H and W even -> (N,3H/2,W) or (3H/2,W) ``torch.uint8``: H rows of Y, then H/2 rows
     of U V U V ..., chroma the matrix of the rounded mean of a 2 x 2 quad's codes (``nv12_matrix``; the integer definition
     is in include/risp.h).  With ``out`` given nothing is allocated and the host does not wait."""
-    _need_gpu(img_u8, 'img')
-    if img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
-        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s' % (img_u8.dtype, tuple(img_u8.shape)))
-    if channels not in ('bgr', 'rgb'):
-        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    _need_gpu(img_u8, 'img')                            # (first here, and no limit on N: a grid-stride launch, not a tiled one)
+    n, h, w, lead = _bgr8_images(img_u8)
+    rgb = _channels(channels)
     coef = nv12_matrix(matrix)
-    h, w = img_u8.shape[-3], img_u8.shape[-2]
-    if h % 2 or w % 2 or h < 2 or w < 2:
-        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
-    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
+    _check_420(h, w, least=2)
     img_u8 = img_u8.contiguous()
-    out = _u8_out(out, tuple(img_u8.shape[:-3]) + (h + h // 2, w), img_u8.device, 1)
-    L.call('risp_bgr8_to_nv12', _p(img_u8), _p(out), (C.c_int * 12)(*coef), int(channels == 'rgb'), n, h, w, _stream())
+    out = _u8_out(out, lead + (h + h // 2, w), img_u8.device, 1)
+    L.call('risp_bgr8_to_nv12', _p(img_u8), _p(out), _coef12(coef), rgb, n, h, w, _stream())
     return out
 
 
@@ -913,8 +946,8 @@ def resize_check(out_size, out_window, resample, H, W, nv12=False):
             size = ()
         if len(size) != 2 or None in size:
             raise ValueError('out_size %r: (OH, OW) as integers >= 1' % (out_size,))
-    if nv12 and (size[0] % 2 or size[1] % 2):
-        raise ValueError('a %d x %d output has no 4:2:0 form: OH and OW must be even' % size)
+    if nv12:
+        _check_420(size[0], size[1], 'output', 'OH and OW')
     resample_taps(win[2], size[0], resample, win[0])
     resample_taps(win[3], size[1], resample, win[1])
     rows = resize_tile_rows(win[2], size[0], resample, win[0])[0]
@@ -985,28 +1018,18 @@ def bgr8_resize(img_u8, out_size=None, out_window=None, resample='triangle', nv1
     packed ``out``; ``out`` must not share memory with the images.  The tap tables live on the device per (axis geometry,
     kernel, device) until ``release_resize_tables``: a warm call on contiguous images uploads nothing, with ``out`` given
     allocates nothing, and the host never waits; images that are not contiguous are copied first, which allocates."""
-    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
-        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
-                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
-    if channels not in ('bgr', 'rgb'):
-        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    n, h, w, lead = _bgr8_images(img_u8)
+    rgb = _channels(channels)
     coef = None if nv12 is None else nv12_matrix(nv12)
-    h, w = img_u8.shape[-3], img_u8.shape[-2]
     (oh, ow), (y0, x0, wh, ww) = resize_check(out_size, out_window, resample, h, w, coef is not None)
-    _need_gpu(img_u8, 'img')
-    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
-    if n > 65535:
-        raise ValueError('%d images in one call: at most 65535' % n)
-    img_u8 = img_u8.contiguous()
-    shape = tuple(img_u8.shape[:-3]) + ((oh, ow, 3) if coef is None else (oh + oh // 2, ow))
-    out = _u8_out(out, shape, img_u8.device, 1 if coef is None else 4)
-    if (out.data_ptr() < img_u8.data_ptr() + img_u8.numel() and img_u8.data_ptr() < out.data_ptr() + out.numel()):
-        raise ValueError('out shares memory with the images: a tile reads rows other tiles would have overwritten')
+    img_u8 = _bgr8_batch(img_u8, n)
+    shape = lead + ((oh, ow, 3) if coef is None else (oh + oh // 2, ow))
+    out = _u8_out(out, shape, img_u8.device, 1 if coef is None else 4, img_u8, 'rows')
     xs, xw, tx, _ = _resize_axis(ww, ow, resample, x0, img_u8.device)
     ys, yw, ty, _ = _resize_axis(wh, oh, resample, y0, img_u8.device)
     rows, span = resize_tile_rows(wh, oh, resample, y0)
-    L.call('risp_bgr8_resize', _p(img_u8), _p(out), _p(xs), _p(xw), tx, _p(ys), _p(yw), ty, rows, span,
-           None if coef is None else (C.c_int * 12)(*coef), int(channels == 'rgb'), n, h, w, oh, ow, _stream())
+    L.call('risp_bgr8_resize', _p(img_u8), _p(out), _p(xs), _p(xw), tx, _p(ys), _p(yw), ty, rows, span, _coef12(coef), rgb,
+           n, h, w, oh, ow, _stream())
     return out
 
 
@@ -1066,8 +1089,8 @@ def warp_check(warp, H, W, device=None, nv12=False):
         raise ValueError('warp of %r x %r images: H and W in 1 .. 2^23' % (H, W))
     if (wh + WARP_TILE_H - 1) // WARP_TILE_H > 65535:
         raise ValueError('warp size %r: %d output rows in tiles of %d are more than 65535 row tiles' % (size, wh, WARP_TILE_H))
-    if nv12 and (wh % 2 or ww % 2):
-        raise ValueError('a %d x %d warp output has no 4:2:0 form: WH and WW must be even' % (wh, ww))
+    if nv12:
+        _check_420(wh, ww, 'warp output', 'WH and WW')
     if kernel not in WARP_KERNELS:
         raise ValueError('unknown warp kernel %r: one of %s' % (kernel, ', '.join(WARP_KERNELS)))
     if not isinstance(mesh, torch.Tensor) or mesh.dtype != torch.int32:
@@ -1093,24 +1116,15 @@ def bgr8_warp(img_u8, warp, out=None, stage=None):
     takes what ``pipeline_fusion.warp_stage(kernel)`` says.  No alignment is asked of the images or of ``out``; ``out`` must not
     share memory with the images.  With ``out`` given a call on contiguous images allocates nothing and the host never waits;
     images that are not contiguous are copied first, which allocates."""
-    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
-        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
-                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
-    h, w = img_u8.shape[-3], img_u8.shape[-2]
+    n, h, w, lead = _bgr8_images(img_u8)
     mesh, k, (wh, ww), kernel = warp_check(warp, h, w, img_u8.device)
     if stage is None:
         from .codes.models.modules.pipeline_fusion import warp_stage
         stage = warp_stage(kernel)
     if isinstance(stage, bool) or stage not in (0, 1, 'gather', 'lds'):
         raise ValueError("warp stage %r: 'lds' / 1, 'gather' / 0 or None" % (stage,))
-    _need_gpu(img_u8, 'img')
-    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
-    if n > 65535:
-        raise ValueError('%d images in one call: at most 65535' % n)
-    img_u8 = img_u8.contiguous()
-    out = _u8_out(out, tuple(img_u8.shape[:-3]) + (wh, ww, 3), img_u8.device, 1)
-    if (out.data_ptr() < img_u8.data_ptr() + img_u8.numel() and img_u8.data_ptr() < out.data_ptr() + out.numel()):
-        raise ValueError('out shares memory with the images: a tile reads pixels other tiles would have overwritten')
+    img_u8 = _bgr8_batch(img_u8, n)
+    out = _u8_out(out, lead + (wh, ww, 3), img_u8.device, 1, img_u8, 'pixels')
     L.call('risp_bgr8_warp', _p(img_u8), _p(out), _p(mesh), k, mesh.shape[0], mesh.shape[1], WARP_KERNELS.index(kernel),
            int(stage in (1, 'lds')), n, h, w, wh, ww, _stream())
     return out
@@ -1254,24 +1268,13 @@ def bgr8_sharpen(img_u8, sharpen, nv12=None, channels='bgr', out=None):
     byte ``bgr8_to_nv12`` of the packed result (H, W even).  No alignment is asked of the images or of ``out``; ``out`` must not
     share memory with the images.  With ``out`` given a call on contiguous images allocates nothing and the host never waits;
     images that are not contiguous are copied first, which allocates."""
-    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() not in (3, 4) or img_u8.shape[-1] != 3:
-        raise ValueError('expected (N,H,W,3) or (H,W,3) uint8 images, got %s %s'
-                         % (getattr(img_u8, 'dtype', type(img_u8)), tuple(getattr(img_u8, 'shape', ()))))
-    if channels not in ('bgr', 'rgb'):
-        raise ValueError("channels %r: 'bgr' or 'rgb'" % (channels,))
+    n, h, w, lead = _bgr8_images(img_u8)
+    rgb = _channels(channels)
     coef = None if nv12 is None else nv12_matrix(nv12)
-    h, w = img_u8.shape[-3], img_u8.shape[-2]
     amount, threshold, limit, radius = sharpen_check(sharpen, coef is not None, h, w)
-    _need_gpu(img_u8, 'img')
-    n = img_u8.shape[0] if img_u8.dim() == 4 else 1
-    if n > 65535:
-        raise ValueError('%d images in one call: at most 65535' % n)
-    img_u8 = img_u8.contiguous()
-    out = _u8_out(out, tuple(img_u8.shape[:-3]) + ((h, w, 3) if coef is None else (h + h // 2, w)), img_u8.device, 1)
-    if (out.data_ptr() < img_u8.data_ptr() + img_u8.numel() and img_u8.data_ptr() < out.data_ptr() + out.numel()):
-        raise ValueError('out shares memory with the images: a tile reads pixels other tiles would have overwritten')
-    L.call('risp_bgr8_sharpen', _p(img_u8), _p(out), None if coef is None else (C.c_int * 12)(*coef), int(channels == 'rgb'),
-           radius, amount, threshold, limit, n, h, w, _stream())
+    img_u8 = _bgr8_batch(img_u8, n)
+    out = _u8_out(out, lead + ((h, w, 3) if coef is None else (h + h // 2, w)), img_u8.device, 1, img_u8, 'pixels')
+    L.call('risp_bgr8_sharpen', _p(img_u8), _p(out), _coef12(coef), rgb, radius, amount, threshold, limit, n, h, w, _stream())
     return out
 
 
@@ -1284,12 +1287,11 @@ def serve_nv12(raw_u16, divisor, ops, params, bilateral=None, matrix='bt601_full
     _check_counts(ops, params)
     black, code = _sensor(black_level, cfa)             # (4:2:0 asks for even axes below: no mirror check)
     coef = nv12_matrix(matrix)
-    if h % 2 or w % 2:
-        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
+    _check_420(h, w)
     out = _u8_out(out, (n, h + h // 2, w), raw_u16.device, 4)
     count, oparr, blocks, keep = _stage_args(ops, params)
     bil, keep_bil = _bilateral_args(bilateral)
-    L.call('risp_serve_nv12', _p(raw_u16), float(divisor), *bil, count, oparr, blocks, _p(out), (C.c_int * 12)(*coef), n, h, w,
+    L.call('risp_serve_nv12', _p(raw_u16), float(divisor), *bil, count, oparr, blocks, _p(out), _coef12(coef), n, h, w,
            black, code, _stream())
     return out
 
@@ -1304,12 +1306,11 @@ def serve_classical_nv12(raw_u16, divisor, demosaic, ops, params, matrix='bt601_
     kind = _demosaic_code(demosaic)
     black, code = _sensor(black_level, cfa)             # (4:2:0 asks for even axes below: no mirror check)
     coef = nv12_matrix(matrix)
-    if h % 2 or w % 2:
-        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
+    _check_420(h, w)
     out = _u8_out(out, (n, h + h // 2, w), raw_u16.device, 4)
     count, oparr, blocks, keep = _stage_args(ops, params)
-    L.call('risp_serve_classical_nv12', _p(raw_u16), float(divisor), kind, count, oparr, blocks, _p(out), (C.c_int * 12)(*coef),
-           n, h, w, black, code, _stream())
+    L.call('risp_serve_classical_nv12', _p(raw_u16), float(divisor), kind, count, oparr, blocks, _p(out), _coef12(coef), n, h, w,
+           black, code, _stream())
     return out
 
 
@@ -1387,9 +1388,8 @@ def _packed_out(matrix, reverse_channels, out, n, h, w, device):
         return None, _u8_out(out, (n, h, w, 3), device, 4)
     if reverse_channels:
         raise ValueError('reverse_channels has no meaning with a yuv matrix: the conversion knows the channel order')
-    if h % 2 or w % 2:
-        raise ValueError('a %d x %d image has no 4:2:0 form: H and W must be even' % (h, w))
-    return (C.c_int * 12)(*nv12_matrix(matrix)), _u8_out(out, (n, h + h // 2, w), device, 4)
+    _check_420(h, w)
+    return _coef12(nv12_matrix(matrix)), _u8_out(out, (n, h + h // 2, w), device, 4)
 
 
 def serve_packed(packed_u8, bits, width, divisor, ops, params, bilateral=None, reverse_channels=False, matrix=None, out=None,

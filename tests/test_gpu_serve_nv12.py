@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import nv12_reference as NR
+from bgr8_placement import _at_odd_address, _guards_intact
 
 pytestmark = pytest.mark.gpu
 
@@ -74,17 +75,14 @@ def test_bgr8_to_nv12_through_views_one_byte_off():
     n, h, w = 2, 34, 68
     img = _images(n, h, w, seed=5)['random']
     want = torch.from_numpy(NR.nv12(img.numpy(), NR.TABLE['bt709_video']))
-    size, osize = img.numel(), n * (h + h // 2) * w
-    big = torch.zeros(size + 8, dtype=torch.uint8, device='cuda')
-    view = big[1:1 + size].view(n, h, w, 3)
-    view.copy_(img)
+    view, _ = _at_odd_address(img, 1, 7, 0)
     assert view.data_ptr() % 2 == 1 and view.is_contiguous()
     got, calls = _counted(lambda: F.bgr8_to_nv12(view, 'bt709_video'))
     assert calls == {'risp_bgr8_to_nv12': 1} and torch.equal(got.cpu(), want)
-    obig = torch.full((osize + 8,), 0xA5, dtype=torch.uint8, device='cuda')
-    out = obig[3:3 + osize].view(n, h + h // 2, w)
+    out, obig = _at_odd_address(tuple(want.shape), 3, 5)
+    assert out.data_ptr() % 4 == 3
     assert F.bgr8_to_nv12(img.cuda(), 'bt709_video', out=out) is out
-    assert torch.equal(out.cpu(), want) and (obig[:3] == 0xA5).all().item() and (obig[3 + osize:] == 0xA5).all().item()
+    assert torch.equal(out.cpu(), want) and _guards_intact(obig, out)
 
 
 # ---------------------------------------------------------------- 2. the fused stores through the pipelines' serve()

@@ -15,6 +15,7 @@ import torch
 
 import nv12_reference as NR
 import resize_reference as RR
+from bgr8_placement import _at_odd_address, _guards_intact
 
 pytestmark = pytest.mark.gpu
 
@@ -125,28 +126,44 @@ def test_images_and_out_at_odd_addresses_and_nothing_outside_is_written():
     ci, kernel = 0, 'bicubic'
     (n, h, w), size, win = RR.CASES[ci]
     img, want = _image(ci), torch.from_numpy(_want(ci, kernel).copy())
-    big = torch.zeros(img.size + 8, dtype=torch.uint8, device='cuda')
-    view = big[1:1 + img.size].view(n, h, w, 3)
-    view.copy_(torch.from_numpy(img))
+    view, _ = _at_odd_address(img, 1, 7, 0)
     assert view.data_ptr() % 2 == 1 and view.is_contiguous()
     assert torch.equal(F.bgr8_resize(view, size, win, kernel).cpu(), want)
     for at in (1, 2, 3, 4):
-        obig = torch.full((want.numel() + 16,), 0xAA, dtype=torch.uint8, device='cuda')
-        out = obig[at:at + want.numel()].view(want.shape)
+        out, obig = _at_odd_address(tuple(want.shape), at, 16 - at, 0xAA)
+        assert out.data_ptr() % 4 == at % 4
         for _ in range(2):                                  # made twice: the second call finds the first one's bytes
             assert F.bgr8_resize(view, size, win, kernel, out=out) is out
             assert torch.equal(out.cpu(), want)
-        assert (obig[:at] == 0xAA).all().item() and (obig[at + want.numel():] == 0xAA).all().item()
+        assert _guards_intact(obig, out, 0xAA)
     # NV12 out: 4-byte aligned, and refused otherwise
     expect = torch.from_numpy(NR.nv12(want.numpy(), NR.TABLE['bt601_full']))
-    obig = torch.full((expect.numel() + 16,), 0xAA, dtype=torch.uint8, device='cuda')
-    out = obig[4:4 + expect.numel()].view(expect.shape)
+    out, obig = _at_odd_address(tuple(expect.shape), 4, 12, 0xAA)
     for _ in range(2):
         assert F.bgr8_resize(view, size, win, kernel, nv12='bt601_full', out=out) is out
         assert torch.equal(out.cpu(), expect)
-    assert (obig[:4] == 0xAA).all().item() and (obig[4 + expect.numel():] == 0xAA).all().item()
+    assert _guards_intact(obig, out, 0xAA)
     with pytest.raises(ValueError, match='aligned'):
         F.bgr8_resize(view, size, win, kernel, nv12='bt601_full', out=obig[2:2 + expect.numel()].view(expect.shape))
+
+
+def test_nv12_with_a_last_tile_of_two_columns():
+    """9 x 70 -> 6 x 66: OW % 4 == 2 and OW > 64, so the last column tile is two columns wide, its patches hold one quad and the
+    store takes the byte form.  (``TILED`` reaches a one-quad patch too - 214 columns - but with one image, one channel order and
+    no guard bytes.)"""
+    import reconfigisp_amd.functional as F
+    size = (6, 66)
+    assert size[1] % 4 == 2 and F.RESIZE_TILE_W < size[1] < F.RESIZE_TILE_W + 4
+    dev = torch.from_numpy(RR.make_image(2, 9, 70, seed=77)).cuda()
+    packed = F.bgr8_resize(dev, size, None, 'triangle')
+    assert np.array_equal(packed.cpu().numpy(), RR.resize(dev.cpu().numpy(), size, None, 'triangle'))
+    for channels in ('bgr', 'rgb'):
+        want = F.bgr8_to_nv12(packed, 'bt601_full', channels)
+        out, buf = _at_odd_address(tuple(want.shape), 4, 12, 0xAA)
+        assert out.data_ptr() % 4 == 0
+        assert F.bgr8_resize(dev, size, None, 'triangle', nv12='bt601_full', channels=channels, out=out) is out
+        assert torch.equal(out, want), (channels, (out != want).sum().item())
+        assert _guards_intact(buf, out, 0xAA), 'bytes outside out were written'
 
 
 def test_rgb_against_bgr_for_nv12():

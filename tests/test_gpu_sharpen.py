@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import nv12_reference as NR  # noqa: E402
+from bgr8_placement import _at_odd_address, _guards_intact  # noqa: E402
 import sharpen_reference as SR  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -35,14 +36,6 @@ def _counted(fn):
         L.CALLS = None
 
 
-def _at_odd_address(x, offset=1, tail=64, fill=0xA5):
-    """a contiguous view of x's shape that starts `offset` bytes into a larger buffer filled with `fill` -> (view, buffer)"""
-    buf = torch.full((x.numel() + offset + tail,), fill, dtype=torch.uint8, device='cuda')
-    view = buf[offset:offset + x.numel()].view(x.shape)
-    view.copy_(x)
-    return view, buf
-
-
 @pytest.mark.parametrize('case', SR.CASES, ids=[c['name'] for c in SR.CASES])
 def test_every_case_byte_for_byte(case):
     import reconfigisp_amd.functional as F
@@ -59,11 +52,11 @@ def test_every_case_byte_for_byte(case):
     # img and out at odd byte addresses inside larger buffers whose other bytes must survive
     for off_in, off_out in ((1, 3), (3, 2), (2, 1)):
         src, _ = _at_odd_address(dev, off_in)
-        out, buf = _at_odd_address(torch.zeros_like(dev), off_out)
+        out, buf = _at_odd_address(tuple(dev.shape), off_out)
         assert src.data_ptr() % 4 == off_in % 4 and out.data_ptr() % 4 == off_out % 4
         assert F.bgr8_sharpen(src, case['params'], channels=case['channels'], out=out) is out
         assert torch.equal(out, want), (off_in, off_out, (out != want).sum().item())
-        assert (buf[:off_out] == 0xA5).all() and (buf[off_out + dev.numel():] == 0xA5).all(), 'bytes outside out were written'
+        assert _guards_intact(buf, out), 'bytes outside out were written'
 
 
 @pytest.mark.parametrize('size', SR.NV12_SIZES, ids=['%dx%d' % s for s in SR.NV12_SIZES])
@@ -85,10 +78,10 @@ def test_the_nv12_store_is_the_conversion_of_the_sharpened_codes(size):
             assert torch.equal(F.bgr8_sharpen(dev[2], params, nv12=NR.TABLE[matrix], channels=channels), want[2])
             # an NV12 image at an odd address (the byte stores), its surroundings left alone
             src, _ = _at_odd_address(dev, 1)
-            out, buf = _at_odd_address(torch.zeros_like(want), 3)
+            out, buf = _at_odd_address(tuple(want.shape), 3)
             F.bgr8_sharpen(src, params, nv12=matrix, channels=channels, out=out)
             assert torch.equal(out, want)
-            assert (buf[:3] == 0xA5).all() and (buf[3 + want.numel():] == 0xA5).all()
+            assert out.data_ptr() - buf.data_ptr() == 3 and _guards_intact(buf, out)
 
 
 def test_refusals():

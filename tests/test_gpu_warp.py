@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import warp_reference as WR  # noqa: E402
+from bgr8_placement import _at_odd_address, _guards_intact  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -50,14 +51,9 @@ def test_bgr8_warp_equals_the_reference(ci, kernel, stage):
     import reconfigisp_amd.functional as F
     img, mesh, k, size = WR.case_inputs(ci)
     n, h, w = img.shape[:3]
-    rng = np.random.default_rng(ci)
-    host = rng.integers(0, 256, size=(img.size + 64,), dtype=np.uint8)
-    host[13:13 + img.size] = img.reshape(-1)
-    big = torch.from_numpy(host).cuda()
-    dev = big[13:13 + img.size].view(n, h, w, 3)
-    count = n * size[0] * size[1] * 3
-    guard = torch.full((count + 32,), 0x5A, device='cuda', dtype=torch.uint8)
-    out = guard[7:7 + count].view(n, size[0], size[1], 3)
+    dev, big = _at_odd_address(img, 13, 51, np.random.default_rng(ci))
+    host = big.cpu().numpy()
+    out, guard = _at_odd_address((n, size[0], size[1], 3), 7, 25, 0x5A)
     warp = (torch.from_numpy(mesh).cuda(), 1 << k, size, kernel)
     got, calls = _counted(lambda: F.bgr8_warp(dev, warp, out=out, stage=stage))
     assert got is out and calls == {'risp_bgr8_warp': 1}
@@ -65,7 +61,7 @@ def test_bgr8_warp_equals_the_reference(ci, kernel, stage):
     want = _want(ci, kernel)
     diff = got.cpu().numpy() != want
     assert not diff.any(), '%d bytes differ, the first at %s' % (diff.sum(), np.argwhere(diff)[0])
-    assert (guard[:7] == 0x5A).all().item() and (guard[7 + count:] == 0x5A).all().item(), 'the launch wrote outside its image'
+    assert _guards_intact(guard, out, 0x5A), 'the launch wrote outside its image'
     assert np.array_equal(big.cpu().numpy(), host), 'the launch wrote into its input'
 
 

@@ -75,6 +75,44 @@ def test_the_default_clock_is_timed():
     assert inspect.signature(SB.timed).parameters['warm'].default == 3
 
 
+def test_builds_are_compared_on_shared_buffers_then_timed_in_interleaved_rounds():
+    """``compare_builds`` under a fake clock: the entry point is rebound per build for the first calls and for every timing, the
+    results must agree before anything is timed, a warm round is dropped, the lines carry the rule's outcome, and the tree's
+    function is bound again afterwards - also when the builds disagree"""
+    import torch
+    from reconfigisp_amd import lib as L
+    entry, out, state = 'risp_no_such_entry', torch.zeros(4), torch.zeros(1)
+    builds = {'tree': {entry: 'T'}, 'fast': {entry: 'F'}, 'slow': {entry: 'S'}, 'same': {entry: 'E'}}
+    us = {'T': 20.0, 'F': 10.0, 'S': 30.0, 'E': 20.5}
+    seen, resets, lines = [], [], []
+
+    def leg():
+        seen.append(L._FN[entry])
+        out.copy_(state.expand(4) + 1)
+        state.add_(1)
+
+    def timed(fn, reps):
+        assert fn is leg
+        seen.append((L._FN[entry], reps))
+        return us[L._FN[entry]] + 0.25 * (len(seen) % 3)        # spreads of at most 0.5
+
+    won = SB.compare_builds(lines.append, 'a row', builds, entry, leg, (out,), 5, 3, lambda: (resets.append(1), state.zero_()), timed)
+    assert won == ['fast'] and len(resets) == 4 and L._FN[entry] == 'T'
+    assert seen == ['T', 'F', 'S', 'E'] + [('T', 5), ('F', 5), ('S', 5), ('E', 5)] * 4      # one call each, then 1 + 3 rounds
+    assert lines[0] == ' a row, 5 calls per round; us per call' and len(lines) == 5
+    assert [line.split()[0] for line in lines[1:]] == ['tree', 'fast', 'slow', 'same']
+    assert 'tree - ' not in lines[1] and lines[1].count('.') == 3 + 3       # median, min, spread and three kept rounds
+    assert lines[2].endswith(': BEATS the tree') and lines[3].endswith(': loses') and lines[4].endswith(': level')
+    assert 'tree - fast = +10.0 us against a spread of 0.5 us' in lines[2]
+    # a build whose first call gives other bytes: nothing is timed
+    seen.clear()
+    with pytest.raises(AssertionError, match='the builds disagree: a row'):
+        SB.compare_builds(lines.append, 'a row', builds, entry, leg, (out,), 5, 3, timed=timed)      # no reset: the state moves on
+    assert seen == ['T', 'F', 'S', 'E'] and L._FN.pop(entry) == 'T'
+    assert SB.beaten_line([]) == 'rows in which another build beats the tree: none'
+    assert SB.beaten_line(['a row by fast', 'b by fast']) == 'rows in which another build beats the tree: a row by fast; b by fast'
+
+
 def _tables():
     """(profile, table name, the table's members as the script words them, in the order the script emits them)"""
     from reconfigisp_amd.codes.models.modules import pipeline_fusion as PF

@@ -19,7 +19,6 @@ import torch
 
 import serve_bench as SB
 import reconfigisp_amd.functional as F
-from reconfigisp_amd import lib as L
 from bench_serve_defect import BLACK, CELL, LISTED, SLOPE, THRESHOLD, WHITE
 from bench_serve_stats import BINS, HI, LO, SHIFT
 from bench_serve_temporal import PARAMS
@@ -59,15 +58,10 @@ def main():
     ap.add_argument('--formats', default='u16,raw10', help='of ' + ', '.join(FORMATS))
     args = ap.parse_args()
     calls = {c: 'risp_raw_' + c for c in (CALLS if args.call == 'all' else (args.call,))}
-    own = {c: getattr(L.load(), name) for c, name in calls.items()}
-    fns = {'tree': own}
-    for item in args.builds:
-        name, path = item.split('=', 1)
-        other = SB.load_parent(path, list(calls.values()))
-        fns[name] = {c: getattr(other, entry) for c, entry in calls.items()}
+    builds = SB.load_builds(args.builds, calls.values())
     emit = SB.Report(args.out)
     emit('tools/bench_serve_defect_rows.py --call %s --formats %s %s   (%s)' % (
-        args.call, args.formats, ' '.join(n for n in fns if n != 'tree'), torch.cuda.get_device_name(0)))
+        args.call, args.formats, ' '.join(n for n in builds if n != 'tree'), torch.cuda.get_device_name(0)))
     beaten = []
     for call, entry in calls.items():
         for fmt in args.formats.split(','):
@@ -83,35 +77,10 @@ def main():
                     raw = big[1:1 + raw.numel()].view(n, h, w)
                     assert raw.data_ptr() % 8 == 2
                 reset, leg, filled = prepare(call, raw, bits, (n, h, w), seed)
-
-                def timed_build(k, reps):                   # a leg is a build's name
-                    L._FN[entry] = fns[k][call]
-                    return SB.timed(leg, reps)
-
-                try:
-                    first = {}
-                    for k in fns:                           # one call of every build from the same start: the same result
-                        reset()
-                        L._FN[entry] = fns[k][call]
-                        leg()
-                        first[k] = [t.clone() for t in filled]
-                    assert all(torch.equal(a, b) for o in first.values() for a, b in zip(o, first['tree'])), 'the builds disagree'
-                    res = SB.rounds_of({k: k for k in fns}, reps, args.rounds, True, timed_build)
-                finally:
-                    L._FN[entry] = own[call]
-                emit(' %s, %s, %d x %d x %d, %d calls per round; us per call' % (call, fmt, n, h, w, reps))
-                for name, v in res.items():
-                    tail = ''
-                    if name != 'tree':
-                        gain, noise = SB.margin(v, res['tree'])
-                        won = SB.beats(v, res['tree'])
-                        tail = '   tree - %s = %+.1f us against a spread of %.1f us: %s' % (
-                            name, gain, noise, 'BEATS the tree' if won else ('loses' if SB.beats(res['tree'], v) else 'level'))
-                        if won:
-                            beaten.append('%s %s %dx%dx%d by %s' % (call, fmt, n, h, w, name))
-                    emit('  %-10s median %.1f us  min %.1f  spread %.1f   rounds %s%s' % (
-                        name, SB.median(v), min(v), SB.spread(v), ' '.join('%.1f' % t for t in v), tail))
-    emit('rows in which another build beats the tree: %s' % ('; '.join(beaten) or 'none'))
+                won = SB.compare_builds(emit, '%s, %s, %d x %d x %d' % (call, fmt, n, h, w), builds, entry, leg, filled, reps,
+                                        args.rounds, reset)
+                beaten += ['%s %s %dx%dx%d by %s' % (call, fmt, n, h, w, name) for name in won]
+    emit(SB.beaten_line(beaten))
     emit.write()
 
 

@@ -182,3 +182,59 @@ def load_parent(path, names):
         fn = getattr(other, name)
         fn.restype, fn.argtypes = L.SIGNATURES[name]
     return other
+
+
+# ---- one entry point in several builds of the library (tools/bench_serve_defect_rows.py, tools/bench_output_builds.py)
+
+def load_builds(items, entries):
+    """{'tree': {entry: function}, NAME: {entry: function}, ..}: the in-tree library first, then every ``NAME=PATH`` of ``items``"""
+    from reconfigisp_amd import lib as L
+    builds = {'tree': {e: getattr(L.load(), e) for e in entries}}
+    for item in items:
+        name, path = item.split('=', 1)
+        other = load_parent(path, list(entries))
+        builds[name] = {e: getattr(other, e) for e in entries}
+    return builds
+
+
+def compare_builds(emit, row, builds, entry, leg, filled, reps, rounds, reset=lambda: None, timed=timed):
+    """One row of a build comparison -> the names of the builds that beat the tree in it.  ``leg()`` is one call of a wrapper that
+    ends in ``entry`` and fills the tensors ``filled``; every build fills the same tensors (where a buffer lies moves a call by
+    more than builds differ).  First one call per build from the same start (``reset()``), and the results must be equal; then
+    ``rounds`` interleaved rounds after one that is dropped; then a line per build with the outcome of ``beats`` against the tree."""
+    from reconfigisp_amd import lib as L
+
+    def timed_build(name, reps):                                # a leg of rounds_of is a build's name
+        L._FN[entry] = builds[name][entry]
+        return timed(leg, reps)
+
+    try:
+        first = {}
+        for name in builds:
+            reset()
+            L._FN[entry] = builds[name][entry]
+            leg()
+            first[name] = [t.clone() for t in filled]
+        assert all(torch.equal(a, b) for o in first.values() for a, b in zip(o, first['tree'])), 'the builds disagree: ' + row
+        res = rounds_of({name: name for name in builds}, reps, rounds, True, timed_build)
+    finally:
+        L._FN[entry] = builds['tree'][entry]
+    emit(' %s, %d calls per round; us per call' % (row, reps))
+    beaten = []
+    for name, v in res.items():
+        tail = ''
+        if name != 'tree':
+            gain, noise = margin(v, res['tree'])
+            won = beats(v, res['tree'])
+            tail = '   tree - %s = %+.1f us against a spread of %.1f us: %s' % (
+                name, gain, noise, 'BEATS the tree' if won else ('loses' if beats(res['tree'], v) else 'level'))
+            if won:
+                beaten.append(name)
+        emit('  %-10s median %.1f us  min %.1f  spread %.1f   rounds %s%s' % (
+            name, median(v), min(v), spread(v), ' '.join('%.1f' % t for t in v), tail))
+    return beaten
+
+
+def beaten_line(rows):
+    """the closing line of a build comparison; ``rows``: '<row> by <build>' for every row in which a build beat the tree"""
+    return 'rows in which another build beats the tree: %s' % ('; '.join(rows) or 'none')
