@@ -147,6 +147,8 @@ int risp_chain_fwd(const float *in, int n_ops, const int *ops, const float *cons
  * y = sum_k w[k] * o_k  over K op outputs of one slot (w = pruned, renormalised probs,
  * host array).  bwd: go_k = w[k]*gy (written only where go[k] != NULL) and
  * gw[k] = <gy, o_k> (device, K floats, fully written).
+ * numel % 4 == 0; every o_k, go[k], gy and y 16-byte aligned (both kernels walk them in
+ * 16-byte vectors): anything else is refused before a launch.
  * ------------------------------------------------------------------------- */
 #define RISP_MAX_MIX 16
 int risp_mix_fwd(const float *const *outs, const float *w, int K, float *y, size_t numel, void *stream);
@@ -443,7 +445,8 @@ size_t risp_conv_wgrad_scratch_floats(int cin, int cout, int ksize);
 int risp_conv2d_wgrad(const risp_conv_desc *d, const float *gy, float *dw, float *scratch, size_t scratch_floats, void *stream);
 
 /* sum over H,W of channels [c0, c0+nc) of an (N,C,H,W) tensor -> out (N,nc) (SRCNNRes
- * gradient of the broadcast parameter planes). */
+ * gradient of the broadcast parameter planes).  16-byte loads where HW % 4 == 0 and x is 16-byte
+ * aligned, element loads otherwise (as risp_channel_stats). */
 int risp_plane_sums(const float *x, float *out, int N, int C, int c0, int nc, int HW, void *stream);
 
 /* ---------------------------------------------------------------------------

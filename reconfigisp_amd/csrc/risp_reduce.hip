@@ -491,6 +491,9 @@ static int mix_args(const char *name, const float *const *outs, const float *w, 
         a.go[k] = (k < K && go) ? go[k] : nullptr;
         a.w[k] = k < K ? w[k] : 0.f;
         RISP_CHECK_ARG(k >= K || a.o[k], "%s: null operand %d", name, k);
+        // both kernels walk o[k] and go[k] in 16-byte vectors (a NULL go[k] passes)
+        RISP_CHECK_ARG(((reinterpret_cast<uintptr_t>(a.o[k]) | reinterpret_cast<uintptr_t>(a.go[k])) & 15) == 0,
+                       "%s: operand %d or its gradient is not 16-byte aligned", name, k);
     }
     return 0;
 }
@@ -504,6 +507,7 @@ int risp_mix_fwd(const float *const *outs, const float *w, int K, float *y, size
     MixArgs a;
     if (int e = mix_args("risp_mix_fwd", outs, w, K, nullptr, a, numel)) return e;
     RISP_CHECK_ARG(y, "risp_mix_fwd: null output");
+    RISP_CHECK_ARG((reinterpret_cast<uintptr_t>(y) & 15) == 0, "risp_mix_fwd: the output is not 16-byte aligned");
     hipLaunchKernelGGL(mix_fwd_kernel, dim3(mix_grid(numel / 4)), dim3(256), 0, (hipStream_t)stream, a, y, numel / 4);
     RISP_LAUNCH_CHECK("risp_mix_fwd");
     return 0;
@@ -516,6 +520,7 @@ int risp_mix_bwd(const float *const *outs, const float *w, int K, const float *g
     MixArgs a;
     if (int e = mix_args("risp_mix_bwd", outs, w, K, go, a, numel)) return e;
     RISP_CHECK_ARG(gy && gw && scratch, "risp_mix_bwd: null argument");
+    RISP_CHECK_ARG((reinterpret_cast<uintptr_t>(gy) & 15) == 0, "risp_mix_bwd: gy is not 16-byte aligned");
     size_t b = (numel / 4 + 1023) / 1024;
     int grid = (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
     hipLaunchKernelGGL(mix_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, gy, scratch, numel / 4);
@@ -528,7 +533,9 @@ int risp_plane_sums(const float *x, float *out, int N, int C, int c0, int nc, in
     RISP_CHECK_ARG(x && out && N > 0 && C > 0 && c0 >= 0 && nc > 0 && c0 + nc <= C && HW > 0 && N * nc <= 65535,
                    "risp_plane_sums: bad arguments");
     const int bx = 1;                                   // one workgroup per plane: deterministic, no atomics
-    if (HW % 4 == 0)
+    // the 16-byte loads need an aligned x (as risp_channel_stats, risp_histc and stats_bwd_launch decide): any other base
+    // takes the element loads
+    if (HW % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0)
         hipLaunchKernelGGL(plane_sums_kernel, dim3(bx, N * nc), dim3(256), 0, (hipStream_t)stream, x, out, C, c0, nc,
                            HW / 4);
     else

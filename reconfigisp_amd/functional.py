@@ -208,7 +208,7 @@ class _Mix(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w, w_host, stacks, *outs):
-        outs = [_dev(o) for o in outs]
+        outs = [_aligned16(_dev(o)) for o in outs]      # risp_mix_* refuse a view that sits off a 16-byte boundary: such a view is copied
         k = len(outs)
         ctx.stacks = stacks
         if w_host is None:                  # the caller usually has the values on the host already (no second D2H)
@@ -227,7 +227,7 @@ class _Mix(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         outs = ctx.saved_tensors
-        gy = _dev(gy, 'grad')
+        gy = _aligned16(_dev(gy, 'grad'))
         k = len(outs)
         need = ctx.needs_input_grad[3:]
         gos = [None] * k
@@ -2299,7 +2299,7 @@ class _FanOut(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gs):
-        live = [_dev(g, 'grad') for g in gs if g is not None]
+        live = [_aligned16(_dev(g, 'grad')) for g in gs if g is not None]
         if not live:
             return None, None
         if len(live) == 1:
@@ -2840,8 +2840,8 @@ _TONEMAP = {'reinhard': (0, 'white_point', 'middle_grey'), 'crysisengine': (1, '
 
 
 def _aligned16(x):
-    """risp_origin_tonemap reads its planes in 16-byte vectors and refuses any other pointer: a contiguous view whose
-    storage offset is no multiple of 4 floats is copied to a fresh tensor first"""
+    """risp_origin_tonemap and risp_mix_fwd / _bwd read their planes in 16-byte vectors and refuse any other pointer: a
+    contiguous view whose storage offset is no multiple of 4 floats is copied to a fresh tensor first"""
     return x.clone() if x.data_ptr() % 16 else x
 
 
