@@ -192,12 +192,6 @@ __global__ __launch_bounds__(256) void serve_classical_kernel(const typename cla
     for (int p = 0; p < 2; ++p) store_bgr4(a.out, n, H, W, py + p, px, flip, a.reverse, pix[p]);
 }
 
-template <int KIND, bool NV12, int PACK, bool SHADE, class Args>
-void launch_kind(bool wbq, dim3 grid, hipStream_t s, const Args &a) {
-    if (wbq) hipLaunchKernelGGL((serve_classical_kernel<KIND, true, NV12, PACK, SHADE>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((serve_classical_kernel<KIND, false, NV12, PACK, SHADE>), grid, dim3(256), 0, s, a);
-}
-
 // the rules the entry points share; `raw_align` 1: packed bytes
 int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const void *raw, float divisor, int demosaic, int n_ops, const int *ops,
                    const float *const *params, uint8_t *out, int reverse_channels, int N, int H, int W, int black_level, int cfa,
@@ -213,10 +207,10 @@ int classical_args_fill(const char *name, ClassicalArgs &a, bool &wbq, const voi
 
 template <bool NV12, int PACK = 0, bool SHADE = false, class Args>
 void launch_classical(int demosaic, bool wbq, hipStream_t s, const Args &a) {
-    const dim3 grid = patch_grid(a.N, a.H, a.W);
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, NV12, PACK, SHADE>(wbq, grid, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, NV12, PACK, SHADE>(wbq, grid, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST, NV12, PACK, SHADE>(wbq, grid, s, a);
+    with_form(demosaic, wbq, [&](auto kind_c, auto wbq_c) {
+        hipLaunchKernelGGL((serve_classical_kernel<decltype(kind_c)::value, decltype(wbq_c)::value, NV12, PACK, SHADE>),
+                           patch_grid(a.N, a.H, a.W), dim3(256), 0, s, a);
+    });
 }
 
 }  // namespace

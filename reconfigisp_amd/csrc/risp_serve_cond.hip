@@ -157,12 +157,6 @@ int make_shape(const int *widths, int n_layers, FcShape &s, const char *who) {
     return 0;
 }
 
-template <int KIND>
-void launch_kind(bool wbq, dim3 grid, size_t lds, hipStream_t s, const CondArgs &a) {
-    if (wbq) hipLaunchKernelGGL((serve_cond_hist_kernel<KIND, true>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((serve_cond_hist_kernel<KIND, false>), grid, dim3(256), lds, s, a);
-}
-
 }  // namespace
 
 extern "C" int risp_serve_cond_hist(const uint16_t *raw, float divisor, int demosaic, int n_ops, const int *ops,
@@ -194,11 +188,10 @@ extern "C" int risp_serve_cond_hist(const uint16_t *raw, float divisor, int demo
         risp_set_error("%s: memset failed", name);
         return 2;
     }
-    const dim3 grid = patch_grid(N, H, W);
     const size_t lds = sizeof(unsigned int) * 3 * bins * copies;
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN>(wbq, grid, lds, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR>(wbq, grid, lds, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST>(wbq, grid, lds, s, a);
+    with_form(demosaic, wbq, [&](auto kind_c, auto wbq_c) {
+        hipLaunchKernelGGL((serve_cond_hist_kernel<decltype(kind_c)::value, decltype(wbq_c)::value>), patch_grid(N, H, W), dim3(256), lds, s, a);
+    });
     RISP_LAUNCH_CHECK("risp_serve_cond_hist");
     return 0;
 }

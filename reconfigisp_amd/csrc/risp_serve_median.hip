@@ -15,8 +15,9 @@
 //     patches    324    360    360    440    440    480     against the 256 inside the tile
 //
 //   phase 1  the patches of 2 x 4 pixels that cover the LDS image - demosaic and the P stages as every route evaluates a patch
-//            (risp_serve_patch.h: the loads, reflection inside the mosaic, per-site expressions, 8-bit rounding, tone curves) - stored as the codes q8(value x 255), the median's
-//            input (stage_tile4<true> / median4_kernel's staging form them from the fp32 planes of the composed route).
+//            (risp_serve_dentile.h's front_patches, the walk the 3 x 3 denoisers' kernel takes) - stored as the codes
+//            q8(value x 255), the median's input (stage_tile4<true> / median4_kernel's staging form them from the fp32 planes
+//            of the composed route).
 //            Patches outside the image are skipped; after a barrier the ring positions outside the image that a window can
 //            reach copy the code at the reflect-101 IMAGE coordinate from LDS.  H > K/2 and W > K/2 make that a single
 //            reflection, and its source lies in the same workgroup's LDS image: above the image the source row -y <= K/2 lies
@@ -32,7 +33,7 @@
 // With -ffp-contract=off the bytes are the composed route's (tests/test_gpu_serve_median.py, torch.equal).  Black level and
 // Bayer phase as in risp_serve_u8_cfa: the phase is a mirror of addresses; coordinates, reflection, parity and the tile grid
 // live in the mirrored (RGGB) image.
-#include "risp_serve_patch.h"
+#include "risp_serve_dentile.h"
 
 namespace {
 
@@ -47,6 +48,7 @@ struct MedianArgs : PatchArgs {
 template <int KIND, int K, bool WBQ>
 __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
     constexpr int R = K / 2;
+    // the LDS image of this K (the names hide risp_serve_dentile.h's, which are the 3 x 3 denoisers' image)
     constexpr int RING_Y = (R + 1) & ~1, RING_X = R <= 4 ? 4 : 8;          // LDS rows above / columns left of the tile (whole patches)
     constexpr int LWD = (TILE_W + 2 * RING_X) / 4, LH = TILE_H + 2 * RING_Y, LPLANE = LH * LWD;   // dwords per row, rows, dwords per channel
     constexpr int PCOLS = LWD, PROWS = LH / 2;
@@ -59,18 +61,8 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
     const int flip = a.flip;
     const Mosaic mo(a, n);
 
-    // ---- phase 1: demosaic and the stages in front of the median for every patch of the LDS image that lies in the image
-#pragma unroll 1
-    for (int t = threadIdx.x; t < PROWS * PCOLS; t += 256) {
-        const int pr = t / PCOLS, pc = t - pr * PCOLS;
-        const int px = x0 - RING_X + pc * PXT, py = y0 - RING_Y + pr * 2;
-        if (px < 0 || px >= W || py < 0 || py >= H) continue;      // W % 4 == 0, H % 2 == 0: a patch is in or out as a whole
-        const Patch d = mo.patch<KIND>(px, py);
-        f3 pix[2][PXT];                                            // (the patch is copied into the kernel's own array: risp_serve_patch.h)
-#pragma unroll
-        for (int i = 0; i < 2 * PXT; ++i) (&pix[0][0])[i] = (&d.p[0][0])[i];
-        run_stages<2 * PXT, WBQ>(a, 0, a.n_pre, n, &pix[0][0]);
-        // the median's domain: the 8-bit code of value x in_scale (255), four of a row to a dword
+    // ---- phase 1, stored in the median's domain: the 8-bit code of value x in_scale (255), four of a row to a dword
+    front_patches<KIND, WBQ, false, RING_X, RING_Y, PCOLS, PROWS>(a, mo, n, x0, y0, [&](int pr, int pc, const f3 (&pix)[2][PXT]) {
         auto code = [&](float v) { return (unsigned)q8(v * 255.f); };
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
@@ -79,14 +71,14 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
             dst[LPLANE] = code(pix[p][0].g) | code(pix[p][1].g) << 8 | code(pix[p][2].g) << 16 | code(pix[p][3].g) << 24;
             dst[2 * LPLANE] = code(pix[p][0].r) | code(pix[p][1].r) << 8 | code(pix[p][2].r) << 16 | code(pix[p][3].r) << 24;
         }
-    }
+    });
     __syncthreads();
 
     // ---- ring positions outside the image within a window's reach: the code at the reflect-101 image coordinate.  A dword
     // lies inside the image or outside it as a whole (its first column is a multiple of 4, and so is W); the dwords written
     // here lie outside, the bytes read inside.  Only tiles on the image border have any (a workgroup-uniform condition: the
     // barrier inside is reached by all or by none)
-    if (y0 == 0 || x0 == 0 || y0 + TILE_H + R > H || x0 + TILE_W + R > W) {
+    if (border_tile(x0, y0, H, W, R)) {
         const unsigned char *codes = reinterpret_cast<const unsigned char *>(tile);
         // the columns of the image this LDS image holds: a byte beyond the reach is read by no window, its source only has to exist
         const int cx0 = x0 - RING_X > 0 ? x0 - RING_X : 0, cx1 = (x0 + TILE_W + RING_X < W ? x0 + TILE_W + RING_X : W) - 1;
@@ -95,13 +87,12 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
             const int gy = y0 - RING_Y + r, gx = x0 - RING_X + 4 * dj;
             if (gy < -R || gy >= H + R || gx + 3 < -R || gx >= W + R) continue;
             if (gy >= 0 && gy < H && gx >= 0 && gx < W) continue;
-            const int sy = gy < 0 ? -gy : (gy >= H ? 2 * H - 2 - gy : gy);
+            const int sy = reflect101(gy, H);
             const int srow = (sy - y0 + RING_Y) * LWD * 4 - x0 + RING_X;
             unsigned v[3] = {0u, 0u, 0u};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int x = gx + k;
-                int sx = x < 0 ? -x : (x >= W ? 2 * W - 2 - x : x);
+                int sx = reflect101(gx + k, W);
                 sx = sx < cx0 ? cx0 : (sx > cx1 ? cx1 : sx);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) v[c] |= (unsigned)codes[c * LPLANE * 4 + srow + sx] << (8 * k);
@@ -196,20 +187,15 @@ __global__ __launch_bounds__(256) void serve_median_kernel(const MedianArgs a) {
     }
 }
 
-template <int KIND, int K>
-void launch_form(bool wbq, dim3 grid, hipStream_t s, const MedianArgs &a) {
-    if (wbq) hipLaunchKernelGGL((serve_median_kernel<KIND, K, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((serve_median_kernel<KIND, K, false>), grid, dim3(256), 0, s, a);
-}
-
-template <int KIND>
-void launch_kind(int size, bool wbq, dim3 grid, hipStream_t s, const MedianArgs &a) {
-    if (size == 5) launch_form<KIND, 5>(wbq, grid, s, a);
-    else if (size == 7) launch_form<KIND, 7>(wbq, grid, s, a);
-    else if (size == 9) launch_form<KIND, 9>(wbq, grid, s, a);
-    else if (size == 11) launch_form<KIND, 11>(wbq, grid, s, a);
-    else if (size == 13) launch_form<KIND, 13>(wbq, grid, s, a);
-    else launch_form<KIND, 15>(wbq, grid, s, a);
+// calls f(std::integral_constant<int, K>) for the median's size (as the entry point passed it)
+template <class F>
+void with_size(int size, F &&f) {
+    if (size == 5) f(std::integral_constant<int, 5>{});
+    else if (size == 7) f(std::integral_constant<int, 7>{});
+    else if (size == 9) f(std::integral_constant<int, 9>{});
+    else if (size == 11) f(std::integral_constant<int, 11>{});
+    else if (size == 13) f(std::integral_constant<int, 13>{});
+    else f(std::integral_constant<int, 15>{});
 }
 
 }  // namespace
@@ -233,11 +219,12 @@ extern "C" int risp_serve_median_u8(const uint16_t *raw, float divisor, int demo
         return e;
     a.out = out;
     a.reverse = reverse_channels ? 1 : 0;
-    const dim3 grid = patch_grid(N, H, W);
-    hipStream_t s = (hipStream_t)stream;
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN>(size, wbq, grid, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR>(size, wbq, grid, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST>(size, wbq, grid, s, a);
+    with_form(demosaic, wbq, [&](auto kind_c, auto wbq_c) {
+        with_size(size, [&](auto size_c) {
+            hipLaunchKernelGGL((serve_median_kernel<decltype(kind_c)::value, decltype(size_c)::value, decltype(wbq_c)::value>),
+                               patch_grid(N, H, W), dim3(256), 0, (hipStream_t)stream, a);
+        });
+    });
     RISP_LAUNCH_CHECK("risp_serve_median_u8");
     return 0;
 }

@@ -12,9 +12,12 @@
 // patch through a reference to the caller's array costs half the occupancy (99 .. 104 VGPRs; profiles/serve_patch_resources.txt,
 // DESIGN 4.6).  So a helper here RETURNS its patch or window by value.
 //
-// Host side: the argument block every route's block starts with, the rules of include/risp.h every entry point repeats, and the
-// launch grid.
+// Host side: the argument block every route's block starts with, the rules of include/risp.h every entry point repeats, the
+// launch grid and the dispatch over demosaic kind x WbQuadratic (with_form).  The tile routes' walk and the 3 x 3 denoisers' kernel
+// are risp_serve_dentile.h's.
 #pragma once
+#include <type_traits>
+
 #include "risp_common.h"
 #include "risp_ops.h"
 
@@ -282,6 +285,18 @@ __device__ __forceinline__ void block_reduce3(float (&v)[3], float *lds) {
 // ---- host side
 // the patch grid (W / 4, H / 2) in workgroups of STX x STY threads; the tile routes' grid of 64 x 32 pixel tiles is the same
 inline dim3 patch_grid(int N, int H, int W) { return dim3((W / 4 + STX - 1) / STX, (H / 2 + STY - 1) / STY, N); }
+
+// calls f(std::integral_constant<int, KIND>, std::bool_constant<WBQ>) for the form a launch takes (demosaic as serve_args passed it)
+template <class F>
+inline void with_form(int demosaic, bool wbq, F &&f) {
+    auto kind = [&](auto kind_c) {
+        if (wbq) f(kind_c, std::true_type{});
+        else f(kind_c, std::false_type{});
+    };
+    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) kind(std::integral_constant<int, RISP_DEMOSAIC_LAPLACIAN>{});
+    else if (demosaic == RISP_DEMOSAIC_BILINEAR) kind(std::integral_constant<int, RISP_DEMOSAIC_BILINEAR>{});
+    else kind(std::integral_constant<int, RISP_DEMOSAIC_NEAREST>{});
+}
 
 // what differs between the entry points' rules
 struct ArgRules {

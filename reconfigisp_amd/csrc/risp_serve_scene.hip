@@ -188,17 +188,11 @@ __global__ __launch_bounds__(64) void scene_finish_kernel(int stat, const float 
     *reinterpret_cast<float4 *>(consts + (size_t)n * 4) = float4{p0, p1, p2, 0.f};
 }
 
-template <int KIND, bool STATS>
-void launch_kind(bool wbq, dim3 grid, hipStream_t s, const SceneArgs &a) {
-    if (wbq) hipLaunchKernelGGL((serve_scene_kernel<KIND, true, STATS>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((serve_scene_kernel<KIND, false, STATS>), grid, dim3(256), 0, s, a);
-}
-
 template <bool STATS>
 void launch(int demosaic, bool wbq, dim3 grid, hipStream_t s, const SceneArgs &a) {
-    if (demosaic == RISP_DEMOSAIC_LAPLACIAN) launch_kind<RISP_DEMOSAIC_LAPLACIAN, STATS>(wbq, grid, s, a);
-    else if (demosaic == RISP_DEMOSAIC_BILINEAR) launch_kind<RISP_DEMOSAIC_BILINEAR, STATS>(wbq, grid, s, a);
-    else launch_kind<RISP_DEMOSAIC_NEAREST, STATS>(wbq, grid, s, a);
+    with_form(demosaic, wbq, [&](auto kind_c, auto wbq_c) {
+        hipLaunchKernelGGL((serve_scene_kernel<decltype(kind_c)::value, decltype(wbq_c)::value, STATS>), grid, dim3(256), 0, s, a);
+    });
 }
 
 bool stat_ok(int stat) { return stat == RISP_SCENE_MEAN3 || stat == RISP_SCENE_MAX3 || stat == RISP_SCENE_LOGLUM; }

@@ -18,7 +18,7 @@ for line in sys.stdin:
         if k.strip().startswith('LDS Size'):
             import subprocess
             name = subprocess.run(['c++filt', cur['name']], capture_output=True, text=True).stdout.strip()
-            name = name.replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0]
+            name = name.replace('(anonymous namespace)::', '').replace('risp_patch::', '').replace('void ', '').split('(')[0]
             print('%-52s VGPR %4s  AGPR %3s  SGPR %4s  scratch %5s  waves/SIMD %2s  LDS %6s' % (
                 name[:52], cur.get('VGPRs'), cur.get('AGPRs'), cur.get('TotalSGPRs'), cur.get('ScratchSize [bytes/lane]'),
                 cur.get('Occupancy [waves/SIMD]'), cur.get('LDS Size [bytes/block]')))
